@@ -6,7 +6,9 @@ InstanceNorm2d, Linear head), synthetic 3x32x32, batch 256 per GPU (BASELINE.jso
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" = zero grads, forward, CrossEntropy loss, backward (+ bucketed RCCL all-reduce of the gradients for N>1);
-no optimizer step.  Rank 0 prints ONE JSON line.
+no optimizer step.  Rank 0 prints ONE JSON line; `ms_per_step` in it is the time of one of the K timed steps.
+`--dump-outputs DIR` also writes what the last timed step computed as DIR/<name>.npy (inputs and weights are seeded, so two builds
+run with the same arguments can be compared array by array).
 """
 import argparse
 import json
@@ -77,23 +79,29 @@ def build_model(device, workload="kan_vgg11"):
         def forward(self, x):
             return self.layer(x)
 
-        def step(self, x):
+        def step(self, x, keep=None):
             y = self.layer(x)
             if self.upstream is None or self.upstream.shape != y.shape:
                 self.upstream = torch.randn(y.shape, device=y.device, generator=torch.Generator(device=y.device).manual_seed(2))
             y.backward(self.upstream)
+            if keep is not None:
+                keep["output"] = y.detach()
             return y.detach().flatten()[0]
     return OneLayer().to(device).train()
 
 
-def one_step(model, x, t, reducer=None):
+def one_step(model, x, t, reducer=None, keep=None):
+    """`keep`: a dict that receives the step's forward output (--dump-outputs); the gradients stay in p.grad."""
     model.zero_grad(set_to_none=True)
     if hasattr(model, "step"):                             # single-layer workload: its own step (no loss head)
-        return model.step(x)
-    loss = F.cross_entropy(model(x), t)
+        return model.step(x, keep)
+    logits = model(x)
+    loss = F.cross_entropy(logits, t)
     loss.backward()
     if reducer is not None:
         reducer.finish()
+    if keep is not None:
+        keep["logits"] = logits.detach()
     return loss
 
 
@@ -276,7 +284,7 @@ def summarise(prof, elapsed_s, steps, batch, world, gflop_per_image):
     return ips, roof
 
 
-def timed_steps(model, x, t, steps, warmup, reducer=None, barrier=None):
+def timed_steps(model, x, t, steps, warmup, reducer=None, barrier=None, keep=None):
     _load_torch()
     from convkan_amd import ops
     barrier = barrier or torch.cuda.synchronize
@@ -286,11 +294,36 @@ def timed_steps(model, x, t, steps, warmup, reducer=None, barrier=None):
     ops.PROFILE = []                                  # HIP events around every conv-kernel launch of the timed steps
     t0 = time.perf_counter()
     for _ in range(steps):
-        loss = one_step(model, x, t, reducer)
+        loss = one_step(model, x, t, reducer, keep)
     barrier()
     elapsed = time.perf_counter() - t0
     prof, ops.PROFILE = ops.PROFILE, None
     return elapsed, prof, loss
+
+
+DUMP_BUDGET_BYTES = 48 << 20                          # payload of all --dump-outputs files together (the contract allows 64 MB)
+
+
+def dump_outputs(path, arrays):
+    """Write each array as <path>/<name>.npy in float32.  An array larger than its even share of DUMP_BUDGET_BYTES is written as a sample:
+    that many elements of its flattened values, at sorted indices drawn by a generator seeded from the array's name, so every run and every
+    build of the project picks the same positions.  Returns the summary for the result line."""
+    import zlib
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // 4 // max(1, len(arrays))
+    total, sampled = 0, []
+    for name, a in arrays.items():
+        a = a.detach().float()
+        if a.numel() > share:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            idx = torch.randperm(a.numel(), generator=g)[:share].sort().values
+            a = a.reshape(-1)[idx.to(a.device)]
+            sampled.append(name)
+        fn = os.path.join(path, name + ".npy")
+        np.save(fn, a.cpu().numpy())
+        total += os.path.getsize(fn)
+    return {"dir": path, "arrays": len(arrays), "bytes": total, "sampled": sampled}
 
 
 def hip_graph_replay(model, x, t, iters: int = 100):
@@ -497,7 +530,12 @@ def main():
     ap.add_argument("--bucket-mb", type=int, default=96)
     ap.add_argument("--force-dp", action="store_true", help="run the bucketed all-reduce path even with one rank (path rehearsal)")
     ap.add_argument("--spawn", action="store_true", help="start the ranks through the launcher even for --gpus 1")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, rank 0 writes what the last timed step computed (loss, logits or "
+                                                          "layer output, every parameter gradient) as DIR/<name>.npy, float32, large arrays as a "
+                                                          "fixed seeded sample (dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     world_env = os.environ.get("WORLD_SIZE")
     if (args.gpus > 1 or args.spawn) and world_env is None:
@@ -547,9 +585,17 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    elapsed, prof, loss = timed_steps(model, x, t, args.steps, args.warmup, reducer, barrier)
+    keep = {} if args.dump_outputs else None
+    elapsed, prof, loss = timed_steps(model, x, t, args.steps, args.warmup, reducer, barrier, keep)
+    dumped = None
     if rank == 0:
         print(f"[bench] {args.steps} steps in {elapsed:.3f}s on {world} GPU(s)", file=sys.stderr, flush=True)
+        if keep is not None:                             # before anything else runs a step or moves the weights
+            if not hasattr(model, "step"):
+                keep["loss"] = loss
+            keep.update(("grad." + n, p.grad) for n, p in model.named_parameters() if p.grad is not None)
+            dumped = dump_outputs(args.dump_outputs, keep)
+    keep = None                                          # drop the references to the gradients before the auxiliary legs
     per_rank, trace = [elapsed], {}
     if use_dist:
         tt = torch.tensor([elapsed], device=device, dtype=torch.float64)
@@ -578,6 +624,8 @@ def main():
             "launcher": "bench.py -> torch.distributed.run" if os.environ.get("KAN_BENCH_LAUNCHED") else ("torch.distributed.run" if world_env else "none"),
             "roofline": roof,
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         del prof
         if reducer is not None:
             out["allreduce"] = {"buckets": len(reducer.buckets), "bucket_mb": args.bucket_mb,
