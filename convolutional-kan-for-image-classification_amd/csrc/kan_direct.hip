@@ -481,11 +481,10 @@ int posmod(int a, int b) { return a - floordiv(a, b) * b; }
 
 double band_slab_cost(double slab_bytes) { const double bw = slab_bytes / 4.0e6; return bw > 1.0 / 6.0 ? bw : 1.0 / 6.0; }
 
-// Instantiated (compile-time spec, channels per group, tile) combinations.
+// Instantiated (channels per group, tile) combinations (the compile-time specs: ON_BAND_FWD in kan_internal.h).
 bool band_has_kernel(int fast, int NG, int WO, int MO, int WP) {
     const bool tile = WO == 2 && ((WP == 2 && MO >= 1 && MO <= 3) || (WP == 4 && MO == 1));
-    if (!tile || NG < 1 || NG > 3) return false;
-    return fast == 1 || fast == 2 || fast == 3 || fast == 4 || fast == 5 || fast == 6;
+    return tile && NG >= 1 && NG <= 3 && fast_has(fast, ON_BAND_FWD);
 }
 
 }  // namespace
@@ -645,7 +644,7 @@ static void band_cfg_pass(const KanGeom* g, const KanBasis* b, int fast, KanBand
     // and a half-empty tile is half-wasted matrix work: below 3/4 filled the tap-major kernel keeps the layer (measured there: 1.0 vs 1.8 ms)
     // (small launches -- under 2 GFLOP -- are latency-bound either way and keep the band kernel: one code path for a layer's forward and gradient)
     const double dense_flops = 2.0 * g->B * g->O * g->Ho * g->Wo * (double)g->C * c->P * T * ngroups(g);
-    const bool bw_kernel = (fast >= 1 && fast <= 4) && (dense_flops < 2.0e9 || 4LL * c->n_steps * c->NPLE >= 3LL * rt * TR);
+    const bool bw_kernel = fast_has(fast, ON_BAND_BWD_WEIGHT) && (dense_flops < 2.0e9 || 4LL * c->n_steps * c->NPLE >= 3LL * rt * TR);
     if (bw_kernel && need <= 6 && c->bw_lds_bytes <= 80 * 1024 && rt < 65535 && (long long)c->bw_tiles_o * ngroups(g) <= 65535) {
         int wg = 160 * 1024 / c->bw_lds_bytes;
         const int by_thr = 2048 / c->bw_NT, by_reg = c->bw_NI == 6 ? (c->bw_NT <= 256 ? 3 : 1) : (c->bw_NT <= 256 ? 4 : 2);
@@ -667,7 +666,6 @@ static void band_cfg_pass(const KanGeom* g, const KanBasis* b, int fast, KanBand
 
 int kan_band_fwd_launch(const float* x, const float* xn, const float* wp, float* z, const KanGeom* g, const KanBasis* b,
                         const KanBandCfg* c, int splits, long long slab_elems, void* stream) {
-    if (!c->ok) return kan_fail_msg("internal: band forward launched without a valid configuration%s", "");
     DevGeom dg = dev_geom(g); DevBasis db = dev_basis(b);
     BandTab tb;
     memset(&tb, 0, sizeof(tb));
@@ -679,51 +677,27 @@ int kan_band_fwd_launch(const float* x, const float* xn, const float* wp, float*
         tb.ph_pack[ph] = (unsigned)c->ph_a[ph] | ((unsigned)c->ph_b[ph] << 8) | ((unsigned)c->ph_tap0[ph] << 16) |
                          ((unsigned)(c->ph_tap0[ph + 1] - c->ph_tap0[ph]) << 24);
     for (int i = 0; i < c->n_taps; ++i) tb.tap_shift[i] = c->tap_shift[i];
-    if (splits < 1) return kan_fail_msg("internal: band forward needs at least one slab%s", "");
     const int Opad = round_up(g->O, 64), NGI = c->n_phase * c->NGR, gps = ceil_div(NGI, splits);        // grid.z = the PLAN's slab count (what the caller allocated)
     if ((long long)c->tiles_o * ngroups(g) > 65535) return kan_fail_msg("groups * output tiles exceed the grid limit%s", "");
     const dim3 grid(c->tiles_p, c->tiles_o * ngroups(g), splits);
     const unsigned x_bytes = (unsigned)((long long)g->B * g->x_bstride * 4);
     hipStream_t st = (hipStream_t)stream;
-#define BAND_LAUNCH(KIND, F, NGV, MOV, WPV, SL)                                                                                         \
-    do {                                                                                                                                \
-        static int lds_raised = 0;      /* one-time kernel attribute setup: dynamic LDS above the 64 KB default */                         \
-        if (c->lds_bytes > 64 * 1024 && lds_raised < c->lds_bytes) {                                                                        \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_band_fwd<KIND, F, NGV, 2, MOV, WPV, SL, 1>),                           \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess)                                   \
-                return kan_fail_msg("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed%s", "");                                        \
-            lds_raised = 80 * 1024;                                                                                                         \
-        }                                                                                                                                   \
-        hipLaunchKernelGGL((k_band_fwd<KIND, F, NGV, 2, MOV, WPV, SL, 1>), grid, dim3(2 * WPV * 64), (size_t)c->lds_bytes, st, x, xn, wp, z, \
-                           dg, db, tb, Opad, gps, slab_elems, x_bytes, c->tiles_o);                                                         \
-    } while (0)
-#define BAND_SLOTS(KIND, F, NGV, MOV, WPV) BAND_LAUNCH(KIND, F, NGV, MOV, WPV, 6)
-#define BAND_TILE(KIND, F, NGV)                                                                \
-    do {                                                                                       \
-        if (c->MO == 1 && c->WP == 4) BAND_SLOTS(KIND, F, NGV, 1, 4);                           \
-        else if (c->MO == 1) BAND_SLOTS(KIND, F, NGV, 1, 2);                                    \
-        else if (c->MO == 2) BAND_SLOTS(KIND, F, NGV, 2, 2);                                    \
-        else BAND_SLOTS(KIND, F, NGV, 3, 2);                                                    \
-    } while (0)
-#define BAND_NG(KIND, F)                                                                       \
-    do {                                                                                       \
-        if (c->NG == 1) BAND_TILE(KIND, F, 1);                                                  \
-        else if (c->NG == 2) BAND_TILE(KIND, F, 2);                                             \
-        else BAND_TILE(KIND, F, 3);                                                             \
-    } while (0)
-    switch (c->fast) {
-        case 1: BAND_NG(KAN_BASIS_BSPLINE, 1); break;
-        case 2: BAND_NG(KAN_BASIS_BSPLINE, 2); break;
-        case 3: BAND_NG(KAN_BASIS_RBF, 3); break;
-        case 4: BAND_NG(KAN_BASIS_CHEBY, 4); break;
-        case 5: BAND_NG(KAN_BASIS_CHEBY, 5); break;
-        case 6: BAND_NG(KAN_BASIS_POLY, 6); break;
-        default: return kan_fail_msg("internal: no band forward kernel for this basis%s", "");
-    }
-#undef BAND_NG
-#undef BAND_TILE
-#undef BAND_SLOTS
-#undef BAND_LAUNCH
+    int rc = 0;
+    dispatch_fast<ON_BAND_FWD>(c->fast, [&](auto fv) {
+        constexpr int F = decltype(fv)::value;
+        pick<1, 2, 3>(c->NG, [&](auto ng) {
+            auto launch = [&](auto mo, auto wp_) {           // (32-output blocks per wave, waves along the pixels); six expansion slots
+                constexpr int WPV = decltype(wp_)::value;
+                const void* k = reinterpret_cast<const void*>(&k_band_fwd<fast_kind(F), F, decltype(ng)::value, 2, decltype(mo)::value, WPV, 6, 1>);
+                if (c->lds_bytes > 64 * 1024 && kan_raise_lds_limit(k, 80 * 1024)) { rc = -1; return; }      // dynamic LDS above the 64 KB default
+                hipLaunchKernelGGL((k_band_fwd<fast_kind(F), F, decltype(ng)::value, 2, decltype(mo)::value, WPV, 6, 1>), grid, dim3(2 * WPV * 64),
+                                   (size_t)c->lds_bytes, st, x, xn, wp, z, dg, db, tb, Opad, gps, slab_elems, x_bytes, c->tiles_o);
+            };
+            if (c->MO == 1 && c->WP == 4) launch(IC<1>{}, IC<4>{});
+            else pick<1, 2, 3>(c->MO, [&](auto mo) { launch(mo, IC<2>{}); });
+        });
+    });
+    if (rc) return kan_fail_msg("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed%s", "");
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { kan_fail_msg("launch failed: %s", hipGetErrorString(e)); return -2; }
     return 0;
@@ -731,7 +705,6 @@ int kan_band_fwd_launch(const float* x, const float* xn, const float* wp, float*
 
 int kan_band_bwd_weight_launch(const float* dz, const float* x, const float* xn, float* dwp, const KanGeom* g, const KanBasis* b,
                                const KanBandCfg* c, int splits, long long slab_elems, void* stream) {
-    if (!c->ok || !c->bw_ok) return kan_fail_msg("internal: band weight gradient launched without a valid configuration%s", "");
     DevGeom dg = dev_geom(g); DevBasis db = dev_basis(b);
     BandWTab tb;
     memset(&tb, 0, sizeof(tb));
@@ -743,48 +716,33 @@ int kan_band_bwd_weight_launch(const float* dz, const float* x, const float* xn,
                          ((unsigned)(c->ph_tap0[ph + 1] - c->ph_tap0[ph]) << 24);
     for (int ph = 0; ph <= c->n_phase; ++ph) tb.ph_rt0[ph] = c->bw_ph_rt0[ph];
     for (int i = 0; i < c->n_taps; ++i) tb.tap_shift[i] = c->tap_shift[i];
-    if (splits < 1) return kan_fail_msg("internal: band weight gradient needs at least one slab%s", "");
     const int Opad = round_up(g->O, 64), Kpad = c->n_steps * c->NPLE, pps = ceil_div(c->bw_ptiles, splits);   // grid.z = the PLAN's slab count
     const dim3 grid(c->bw_row_tiles, c->bw_tiles_o * ngroups(g), splits);
     const unsigned x_bytes = (unsigned)((long long)g->B * g->x_bstride * 4), dz_bytes = (unsigned)((long long)g->B * g->y_bstride * 4);
     hipStream_t st = (hipStream_t)stream;
-#define BANDW_LAUNCH(KIND, F, NGV, WRV, NIV, SL)                                                                                                   \
-    do {                                                                                                                                           \
-        static int lds_raised = 0;                                                                                                                 \
-        if (c->bw_lds_bytes > 64 * 1024 && lds_raised < c->bw_lds_bytes) {                                                                         \
-            if (hipFuncSetAttribute(reinterpret_cast<const void*>(&k_band_bwd_weight<KIND, F, NGV, WRV, NIV, SL>),                                 \
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess)                                          \
-                return kan_fail_msg("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed%s", "");                                               \
-            lds_raised = 80 * 1024;                                                                                                                \
-        }                                                                                                                                          \
-        hipLaunchKernelGGL((k_band_bwd_weight<KIND, F, NGV, WRV, NIV, SL>), grid, dim3(WRV * 64), (size_t)c->bw_lds_bytes, st, dz, x, xn, dwp, dg, db, \
-                           tb, Kpad, Opad, pps, slab_elems, x_bytes, dz_bytes, c->bw_tiles_o);                                                    \
-    } while (0)
-#define BANDW_SLOTS(KIND, F, NGV, WRV, NIV) do { if (c->bw_slots <= 3) BANDW_LAUNCH(KIND, F, NGV, WRV, NIV, 3); else BANDW_LAUNCH(KIND, F, NGV, WRV, NIV, 6); } while (0)
-#define BANDW_TILE(KIND, F, NGV)                                                                \
-    do {                                                                                        \
-        if (c->bw_NI == 2 && c->bw_WR == 4) BANDW_SLOTS(KIND, F, NGV, 4, 2);                     \
-        else if (c->bw_NI == 2) BANDW_SLOTS(KIND, F, NGV, 8, 2);                                 \
-        else if (c->bw_NI == 4) BANDW_SLOTS(KIND, F, NGV, 4, 4);                                 \
-        else BANDW_SLOTS(KIND, F, NGV, 4, 6);                                                    \
-    } while (0)
-#define BANDW_NG(KIND, F)                                                                       \
-    do {                                                                                        \
-        if (c->NG == 1) BANDW_TILE(KIND, F, 1);                                                  \
-        else if (c->NG == 2) BANDW_TILE(KIND, F, 2);                                             \
-        else BANDW_TILE(KIND, F, 3);                                                             \
-    } while (0)
-    switch (c->fast) {
-        case 1: BANDW_NG(KAN_BASIS_BSPLINE, 1); break;
-        case 2: BANDW_NG(KAN_BASIS_BSPLINE, 2); break;
-        case 3: BANDW_NG(KAN_BASIS_RBF, 3); break;
-        case 4: BANDW_NG(KAN_BASIS_CHEBY, 4); break;
-        default: return kan_fail_msg("internal: no band weight-gradient kernel for this basis%s", "");
-    }
-#undef BANDW_NG
-#undef BANDW_TILE
-#undef BANDW_SLOTS
-#undef BANDW_LAUNCH
+    int rc = 0;
+    dispatch_fast<ON_BAND_BWD_WEIGHT>(c->fast, [&](auto fv) {
+        constexpr int F = decltype(fv)::value;
+        pick<1, 2, 3>(c->NG, [&](auto ng) {
+            auto launch = [&](auto wr, auto ni) {            // (waves along the rows, 32-output blocks per wave)
+                auto slots = [&](auto sl) {
+                    constexpr int WRV = decltype(wr)::value;
+                    const void* k = reinterpret_cast<const void*>(&k_band_bwd_weight<fast_kind(F), F, decltype(ng)::value, WRV, decltype(ni)::value, decltype(sl)::value>);
+                    if (c->bw_lds_bytes > 64 * 1024 && kan_raise_lds_limit(k, 80 * 1024)) { rc = -1; return; }
+                    hipLaunchKernelGGL((k_band_bwd_weight<fast_kind(F), F, decltype(ng)::value, WRV, decltype(ni)::value, decltype(sl)::value>), grid,
+                                       dim3(WRV * 64), (size_t)c->bw_lds_bytes, st, dz, x, xn, dwp, dg, db, tb, Kpad, Opad, pps, slab_elems, x_bytes,
+                                       dz_bytes, c->bw_tiles_o);
+                };
+                if (c->bw_slots <= 3) slots(IC<3>{});
+                else slots(IC<6>{});
+            };
+            if (c->bw_NI == 2 && c->bw_WR == 4) launch(IC<4>{}, IC<2>{});
+            else if (c->bw_NI == 2) launch(IC<8>{}, IC<2>{});
+            else if (c->bw_NI == 4) launch(IC<4>{}, IC<4>{});
+            else launch(IC<4>{}, IC<6>{});
+        });
+    });
+    if (rc) return kan_fail_msg("hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed%s", "");
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) { kan_fail_msg("launch failed: %s", hipGetErrorString(e)); return -2; }
     return 0;

@@ -1,12 +1,99 @@
 // Host-side interfaces between the translation units of libkanconv (not part of the C ABI; nothing here is exported).
-//   kanconv.hip     C-ABI entry points, planning, the tap-major / halo / position-major GEMM kernels, layout and norm kernels
+//   kanconv.hip     C-ABI entry points, the tap-major / halo / position-major GEMM kernels and their launchers, layout and norm kernels
+//   kan_plan.hip    host only: argument checks and the planner (plan_conv) -- the one place that picks a route and a tile for each stage
 //   kan_direct.hip  band kernels: layers of few input channels (first layers: 3 -> 64) and layers whose output count fills no 128-wide
 //                   tile (64 -> 192), any kernel size / stride / dilation / padding
+//   kan_split.hip   opt-in split-precision forward
 #pragma once
+#include <type_traits>
 #include "kanconv.h"
 
 // sets the thread-local message behind kan_last_error() and returns -1 (defined in kanconv.hip)
 int kan_fail_msg(const char* fmt, const char* a);
+// Raises `kernel`'s dynamic-LDS limit to `bytes` once per (kernel, device) -- the only mutable global state of the library (a mutex-guarded
+// list); later calls on the same device return at once, so a launch stays a plain launch (and graph capture sees nothing new).  0 or -1.
+int kan_raise_lds_limit(const void* kernel, int bytes);
+
+// ---------------------------------------------------------------------------------------------------------------- compile-time basis specs
+// A fast variant is a basis (kind, planes, activation) with compile-time kernels (template parameter FAST; 0 = the generic kernels).
+// The values are part of the kernel names: never renumber.
+enum : int {
+    FAST_GENERIC = 0,
+    FAST_BSPLINE_SILU = 1,    // B-spline grid 5 order 3, SiLU base (P = 9)
+    FAST_BSPLINE_GELU = 2,    // B-spline grid 5 order 3, GELU base
+    FAST_RBF8 = 3,            // FastKAN, 8 centres, SiLU base (P = 9)
+    FAST_CHEBY5 = 4,          // ChebyKAN degree 4 (P = 5)
+    FAST_CHEBY4 = 5,          // ChebyKAN degree 3 (P = 4)
+    FAST_POLY4 = 6,           // recurrence families degree 3, with base (P = 5)
+    FAST_POLY3 = 7,           // recurrence families degree 2, with base (P = 4)
+    FAST_RBF5 = 8,            // FastKAN, 5 centres (kan_vgg.py's grid_size 5), SiLU base (P = 6)
+    FAST_RELU8 = 9,           // ReLU-KAN g + k = 8, SiLU base (P = 9; halo and expanded kernels only)
+    FAST_GRAM4 = 10,          // GRAM-KAN degree 3, SiLU base (P = 5; halo and expanded kernels only)
+    FAST_POLY1 = 11,          // recurrence families degree 0, with base (P = 2)
+    FAST_LAST = 11
+};
+// The kernel families instantiated for each fast variant (the one table: the planner asks it which routes a basis may take, the
+// launchers instantiate exactly these kernels).
+enum : unsigned {
+    ON_TAP_MAJOR = 1u << 0,          // k_conv_fwd / k_conv_bwd_data / k_conv_bwd_weight with FAST = F
+    ON_BIG_TILES = 1u << 1,          // 256-output tiles of the tap-major and halo kernels
+    ON_HALO_FWD = 1u << 2,           // k_conv_fwd_halo
+    ON_HALO_BWD_WEIGHT = 1u << 3,    // k_conv_bwd_weight_halo
+    ON_BAND_FWD = 1u << 4,           // k_band_fwd
+    ON_BAND_BWD_WEIGHT = 1u << 5,    // k_band_bwd_weight
+    ON_EXPANDED_FWD = 1u << 6,       // k_conv_fwd_pmdma on the expanded copy
+    ON_EXPANDED = 1u << 7,           // k_expand_pm + k_conv_bwd_weight_pmdma
+    ON_ROWBLK_BWD_DATA = 1u << 8,    // k_conv_bwd_data with row-ordered pixel blocks (RB = 1)
+};
+constexpr unsigned fast_routes(int f) {
+    constexpr unsigned bspline = ON_TAP_MAJOR | ON_BIG_TILES | ON_HALO_FWD | ON_HALO_BWD_WEIGHT | ON_BAND_FWD | ON_BAND_BWD_WEIGHT |
+                                 ON_EXPANDED_FWD | ON_EXPANDED | ON_ROWBLK_BWD_DATA;
+    switch (f) {
+        case FAST_BSPLINE_SILU: case FAST_BSPLINE_GELU: return bspline;
+        case FAST_RBF8: return ON_TAP_MAJOR | ON_BAND_FWD | ON_BAND_BWD_WEIGHT;
+        case FAST_CHEBY5: return ON_TAP_MAJOR | ON_BIG_TILES | ON_BAND_FWD | ON_BAND_BWD_WEIGHT;
+        case FAST_CHEBY4: return ON_TAP_MAJOR | ON_HALO_FWD | ON_BAND_FWD;
+        case FAST_POLY4: return ON_TAP_MAJOR | ON_BIG_TILES | ON_HALO_FWD | ON_BAND_FWD;
+        case FAST_POLY3: case FAST_RBF5: case FAST_POLY1: return ON_TAP_MAJOR;
+        case FAST_RELU8: return ON_HALO_FWD | ON_HALO_BWD_WEIGHT | ON_EXPANDED_FWD | ON_EXPANDED;
+        case FAST_GRAM4: return ON_HALO_FWD | ON_HALO_BWD_WEIGHT | ON_EXPANDED;
+        default: return 0;
+    }
+}
+constexpr bool fast_has(int f, unsigned routes) { return (fast_routes(f) & routes) == routes && f != FAST_GENERIC; }
+constexpr int fast_kind(int f) {
+    return (f == FAST_RBF8 || f == FAST_RBF5) ? KAN_BASIS_RBF : (f == FAST_CHEBY5 || f == FAST_CHEBY4) ? KAN_BASIS_CHEBY
+         : (f == FAST_POLY4 || f == FAST_POLY3 || f == FAST_POLY1) ? KAN_BASIS_POLY : f == FAST_RELU8 ? KAN_BASIS_RELU
+         : f == FAST_GRAM4 ? KAN_BASIS_GRAM : KAN_BASIS_BSPLINE;
+}
+constexpr int fast_kc(int f) { return fast_kind(f) == KAN_BASIS_BSPLINE || fast_kind(f) == KAN_BASIS_RBF ? 18 : 16; }   // tap-major LDS step
+
+// ---------------------------------------------------------------------------------------------------------------- dispatch helpers
+template <int V> using IC = std::integral_constant<int, V>;
+// fn(IC<F>) for the variant F == f if F has every bit of ROUTES; false (nothing called) otherwise.  Instantiates fn for those F only.
+template <unsigned ROUTES, int F = 1, class Fn>
+bool dispatch_fast(int f, Fn&& fn) {
+    if constexpr (F > FAST_LAST) {
+        return false;
+    } else {
+        if constexpr (fast_has(F, ROUTES)) {
+            if (f == F) { fn(IC<F>{}); return true; }
+        }
+        return dispatch_fast<ROUTES, F + 1>(f, fn);
+    }
+}
+// fn(IC<V>) for the first listed V equal to v, else for the last one.
+template <int V, int... REST, class Fn>
+void pick(int v, Fn&& fn) {
+    if constexpr (sizeof...(REST) == 0) fn(IC<V>{});
+    else if (v == V) fn(IC<V>{});
+    else pick<REST...>(v, fn);
+}
+// fn(IC<kind>) over the basis kinds of the generic kernels (anything else runs as ChebyKAN, as the kernels read it)
+template <class Fn>
+void dispatch_kind(int kind, Fn&& fn) {
+    pick<KAN_BASIS_BSPLINE, KAN_BASIS_RBF, KAN_BASIS_POLY, KAN_BASIS_FOURIER, KAN_BASIS_RELU, KAN_BASIS_GRAM, KAN_BASIS_CHEBY>(kind, fn);
+}
 
 // ---------------------------------------------------------------------------------------------------------------- band kernels
 // The tap-major kernels expand every input value once per TAP it is used under (9x for 3x3, 121x for 11x11) -- vector-ALU work the fp32
@@ -50,11 +137,50 @@ typedef struct KanBandCfg {
                                                                                step(c, tap) = tap_step[tap] + (c / NG) * tap_nt[tap] */
 } KanBandCfg;
 
-/* Fill cfg for (geom, basis); `fast` = the compile-time spec of the basis (0: none -> cfg->ok = 0).  Pure host arithmetic. */
+/* Fill cfg for (geom, basis); `fast` = the compile-time spec of the basis (0: none -> cfg->ok = 0).  Pure host arithmetic (the planner's). */
 void kan_band_cfg(const KanGeom* g, const KanBasis* b, int fast, KanBandCfg* cfg);
+/* The band launchers take the plan's configuration and slab count; the planner picked the band route, so cfg->ok (and bw_ok) hold. */
 /* dwp: bw_splits slabs of G * Kpad * Opad floats in band order (rows as the packed forward weights: kan_unpack_wgrad follows the plan). */
 int kan_band_bwd_weight_launch(const float* dz, const float* x, const float* xn, float* dwp, const KanGeom* g, const KanBasis* b,
                                const KanBandCfg* cfg, int splits, long long slab_elems, void* stream);
 /* z slabs [fwd_splits][B][O_total][Ho][Wo] as kan_conv_fwd; wp in band order. */
 int kan_band_fwd_launch(const float* x, const float* xn, const float* wp, float* z, const KanGeom* g, const KanBasis* b,
                         const KanBandCfg* cfg, int splits, long long slab_elems, void* stream);
+
+// ---------------------------------------------------------------------------------------------------------------- the plan
+// Direct depthwise kernels (kanconv.hip): taps and taps * planes they hold
+constexpr int DW_T = 9;
+constexpr int DW_MAX_TP = 96;                      // taps * planes held in registers by the weight-gradient kernel
+
+// Route of one stage.  EXPANDED: the stage has its own entry on the expanded position-major copy (kan_conv_fwd_expanded /
+// kan_conv_bwd_weight_expanded); kan_conv_fwd / kan_conv_bwd_weight then run the tap-major kernel.
+enum class Route { TAP_MAJOR, DW, BAND, HALO, EXPANDED };
+
+struct FwdCfg { int TO, TP, tiles_o, tiles_p, chunks, splits, slots; };
+struct BdCfg { int CH, tiles_c, tiles_p, n_ob, Opad32, chunks, splits; };   // Opad32: rows per tap of wd (multiple of 32)
+struct BwCfg { int TR, TO, tiles_r, tiles_o, chunks, splits, slots; };
+struct BwHaloCfg { int R, nimg, spb, n_bands, tiles_r, tiles_o, splits, bands_per_split; };
+
+// Everything a launcher needs to know about (geom, basis): plan_conv fills it, every entry point reads it and decides nothing else
+// (except what depends on the pointers the caller passed: position-major copies, x != xn, dxn).
+struct ConvPlan {
+    KanPlan pub;                          // the public plan (kan_plan)
+    int fast;                             // compile-time spec (FAST_*)
+    Route fwd, bwd_data, bwd_weight;
+    bool pm_fwd, pm_bwd_data, pm_bwd_weight;     // position-major launches offered (taken when the caller passes the copies)
+    bool rowblk_bwd_data;                 // 4x4 planes: row-ordered pixel blocks in the image-major bwd-data launch
+    bool pmdma_xcd, pm_lpt, pm_xcd;       // expanded launches: XCD order of the forward, longest-first and XCD order of the weight gradient
+    FwdCfg fc;                            // tap-major / halo / expanded forward tiles
+    BdCfg bd;                             // bwd-data tiles
+    BwCfg bw;                             // tap-major / expanded weight-gradient tiles
+    BwHaloCfg bwh;                        // halo weight-gradient bands (Route::HALO)
+    KanBandCfg band;                      // band kernels (fwd or bwd_weight Route::BAND)
+};
+int plan_conv(const KanGeom* g, const KanBasis* b, ConvPlan* cp);       // 0, or the checks' error (message set)
+
+// live work of position-major tiles (kan_plan.hip)
+int live_taps_out(const KanGeom* g, int hw);
+int live_taps_in(const KanGeom* g, int hw);
+int live_positions_for_tap(const KanGeom* g, int tap);
+// XCD-balanced dispatch order of n <= PERM_MAX pixel tiles of the given weights into idx; returns n, or 0 (identity order)
+int balance_tiles(const int* weight, int n, unsigned short* idx);

@@ -350,13 +350,8 @@ int kan_conv_fwd_split(const float* x, const void* wc, float* z, const KanGeom* 
     const char* why = split_reject(g, b);
     if (why) return kan_fail_msg("%s", why);
     if (!x || !wc || !z) return kan_fail_msg("kan_conv_fwd_split: null pointer%s", "");
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)k_split_fwd<8>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes<8>()) != hipSuccess ||
-            hipFuncSetAttribute((const void*)k_split_fwd<16>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes<16>()) != hipSuccess)
-            return kan_fail_msg("kan_conv_fwd_split: cannot reserve %s of LDS", "158 KB");
-        attr_set = true;
-    }
+    if (kan_raise_lds_limit((const void*)k_split_fwd<8>, lds_bytes<8>()) || kan_raise_lds_limit((const void*)k_split_fwd<16>, lds_bytes<16>()))
+        return kan_fail_msg("kan_conv_fwd_split: cannot reserve %s of LDS", "158 KB");
     const DevBasis db = dev_basis(b);
     const int o_tiles = g->O / 128;
     if (g->H == 8)

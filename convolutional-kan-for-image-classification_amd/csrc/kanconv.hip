@@ -19,7 +19,9 @@
 #include <cstring>
 #include <cmath>
 #include <cstdint>
+#include <mutex>
 #include <type_traits>
+#include <vector>
 #include "kanconv.h"
 #include "kan_device.h"
 
@@ -36,6 +38,20 @@ int fail(const char* fmt, const char* a = "") {
 }
 }  // namespace
 int kan_fail_msg(const char* fmt, const char* a) { return fail(fmt, a); }      // for the other translation units (kan_internal.h)
+
+int kan_raise_lds_limit(const void* kernel, int bytes) {
+    struct Raised { const void* kernel; int device, bytes; };
+    static std::mutex mu;
+    static std::vector<Raised> raised;                       // (kernel, device) pairs whose limit is up: a handful per process
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return -1;
+    std::lock_guard<std::mutex> lock(mu);
+    for (const Raised& r : raised)
+        if (r.kernel == kernel && r.device == dev && r.bytes >= bytes) return 0;
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return -1;
+    raised.push_back(Raised{kernel, dev, bytes});
+    return 0;
+}
 namespace {
 
 // ============================================================================ pack / unpack
@@ -1447,7 +1463,7 @@ __global__ __launch_bounds__(WR * WC * 64, (WR * WC > 4 ? 2 : 4)) void k_conv_bw
 //     consecutive outputs at one pixel hit 32 distinct banks.  The swizzle is not additive, so a lane keeps its eight
 //     k-pair addresses in registers.
 // Per step and wave: 32 MFMA, 32 ds_read_b32, 8 DMA instructions, ~0.3 expansions -- about 0.4 vector instructions per
-// MFMA.  The weight gradient comes out in the channel-major flat order; kan_unpack_wgrad knows (halo_bwd_weight()).
+// MFMA.  The weight gradient comes out in the channel-major flat order; kan_unpack_wgrad knows (the plan's HALO weight-gradient route).
 #define LDS_READ4W(r0, r1, r2, r3, a0, a1, b, oA, oB0, oB1)                                                              \
     asm volatile("ds_read_b32 %0, %4 offset:%7\n\tds_read_b32 %1, %5 offset:%7\n\tds_read_b32 %2, %6 offset:%8\n\tds_read_b32 %3, %6 offset:%9" \
                  : "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3) : "v"(a0), "v"(a1), "v"(b), "n"(oA), "n"(oB0), "n"(oB1) : "memory")
@@ -1935,7 +1951,7 @@ __global__ __launch_bounds__(256, 4) void k_conv_bwd_weight_pmdma(
 // utilisation; these direct kernels do the same arithmetic per output element instead.  They are HBM / VALU bound
 // (T*P multiply-adds per element), read the SAME packed weights (wp: row k(tap, p), column o, one block per group) and
 // write the same slab layouts, so nothing else in the pipeline changes.  One block = 256 elements of one group.
-constexpr int DW_MAX_TP = 96;                      // taps * planes held in registers by the weight-gradient kernel
+// (DW_MAX_TP, DW_T: kan_internal.h -- the planner routes a layer here only within them)
 
 __device__ __forceinline__ int dw_krow(int tap, int p, int IPC, int KC, int P) {   // packed row of (item = tap, plane p) when C == 1
     const int chunk = tap / IPC;
@@ -2020,7 +2036,6 @@ __global__ __launch_bounds__(256) void k_dw_bwd_data(const float* __restrict__ d
 // Weight gradient: block (chunk, group) walks its share of the group's B*Ho*Wo pixels with one accumulator per (tap, plane)
 // in registers (statically indexed: T <= 9, planes padded to KAN_PMAX), one output of the group after the other, reduces
 // them over the block in a fixed order and writes slab `chunk`.
-constexpr int DW_T = 9;
 template <int KIND>
 __global__ __launch_bounds__(256) void k_dw_bwd_weight(const float* __restrict__ dz, const float* __restrict__ x, const float* __restrict__ xn,
                                                        float* __restrict__ dwp, DevGeom g, DevBasis bs, int Krows, int Opad,
@@ -2559,96 +2574,6 @@ __global__ __launch_bounds__(NT) void k_in_prelu_bwd_regs(const float* __restric
 
 // ============================================================================ host side
 
-int check(const KanGeom* g, const KanBasis* b) {
-    if (!g || !b) return fail("null geometry/basis");
-    if (g->groups < 0 || g->groups > 65535) return fail("groups out of range");
-    if (g->B <= 0 || g->C <= 0 || g->O <= 0 || g->H <= 0 || g->W <= 0 || g->Ho <= 0 || g->Wo <= 0) return fail("non-positive dimension");
-    if (g->kh <= 0 || g->kw <= 0 || g->sh <= 0 || g->sw <= 0 || g->dh <= 0 || g->dw <= 0 || g->ph < 0 || g->pw < 0) return fail("bad conv parameters");
-    if (g->kh > 255 || g->kw > 255 || g->C > 65535) return fail("kernel size / channel count out of supported range");
-    if ((g->H + 2 * g->ph - g->dh * (g->kh - 1) - 1) / g->sh + 1 != g->Ho || (g->W + 2 * g->pw - g->dw * (g->kw - 1) - 1) / g->sw + 1 != g->Wo)
-        return fail("Ho/Wo inconsistent with H/W, kernel, stride, padding, dilation");
-    if ((long long)g->B * g->Ho * g->Wo >= (1ll << 31) || (long long)g->B * g->H * g->W >= (1ll << 31)) return fail("pixel count exceeds int32");
-    if ((long long)g->B * g->x_bstride * 4 >= (1ll << 31) || (long long)g->B * g->y_bstride * 4 >= (1ll << 31))
-        return fail("activation tensors must be smaller than 2 GiB (32-bit buffer offsets)");
-    if (g->x_bstride < (long long)ngroups(g) * g->C * g->H * g->W || g->y_bstride < (long long)ngroups(g) * g->O * g->Ho * g->Wo)
-        return fail("batch stride smaller than groups * channels * plane");
-    if (b->kind < 0 || b->kind > KAN_BASIS_GRAM) return fail("unknown basis kind");
-    if (b->kind == KAN_BASIS_GRAM && (b->order < 0 || b->order >= b->n_basis || b->n_basis < 2 || b->act == KAN_ACT_NONE))
-        return fail("Gram basis needs degree >= 1, an activation, and a mode (order) in 0..degree-1");
-    if (b->kind == KAN_BASIS_RELU && (b->order < 0 || b->order > 2)) return fail("ReLU basis mode (order) must be 0, 1 or 2");
-    if (b->kind == KAN_BASIS_FOURIER && (b->n_basis & 1)) return fail("Fourier basis needs an even plane count (cos and sin per frequency)");
-    if (b->kind == KAN_BASIS_POLY && (b->n_basis > 11 || b->order < 0 || b->order > 1)) return fail("bad recurrence-basis parameters");
-    if (b->act < KAN_ACT_NONE || b->act > KAN_ACT_GELU_TANH) return fail("unknown activation");
-    int P = b->n_basis + (b->act != KAN_ACT_NONE);
-    if (b->n_basis < 1 || P > KAN_MAX_PLANES) return fail("planes per channel exceed KAN_MAX_PLANES");
-    if ((long long)g->C * g->kh * g->kw * P >= (1ll << 30)) return fail("GEMM depth too large");
-    if (b->kind == KAN_BASIS_BSPLINE) {
-        if (b->order < 0 || b->order > 3) return fail("spline_order must be in 0..3");
-        const int nk = b->n_basis + b->order + 1;
-        if (nk > KAN_MAX_TABLE) return fail("too many knots");
-        if (b->n_basis - b->order < 1) return fail("grid_size must be >= 1");
-        const float h = (b->table[nk - 1] - b->table[0]) / (float)(nk - 1);
-        if (!(h > 0.f)) return fail("knots must be increasing");
-        for (int i = 0; i < nk; ++i) {          // the closed-form basis assumes torch.linspace knots (kan_layers.py:184-190)
-            float d = b->table[i] - (b->table[0] + h * (float)i);
-            if (d < 0) d = -d;
-            if (d > 1e-4f * h) return fail("knots must be uniform (torch.linspace), as the reference always builds them");
-        }
-    }
-    if (b->kind == KAN_BASIS_RBF && (b->n_basis > KAN_MAX_TABLE || !(b->p0 != 0.f))) return fail("bad RBF parameters");
-    return 0;
-}
-
-// Position-major pixel order (and with it tap skipping) is offered on small padded planes (<= 16 positions: 31 % of
-// the products are dead on 4x4, 56 % on 2x2).  Lanes then walk images, so the kernels must be given the [C*H*W][B]
-// copies of their gathered inputs (kan_position_major); without a copy they stay on the image-major path (on NCHW the
-// strided 4-byte gathers cost more than 4x4 skipping saves).  Masks are 32-bit.  Not for FastKAN (second input tensor).
-// Measured on KAN-VGG11 (bs 256): the weight-gradient kernel gains 27 % on 4x4 planes and 65 % on 2x2; forward and
-// bwd-data gain 40-60 % on 2x2 but nothing on 4x4 (their step latency, not the step count, sets the time there), so
-// they take the position-major path only up to 4 positions.
-enum { PM_FWD = 0, PM_BWD_DATA = 1, PM_BWD_WEIGHT = 2 };
-int fast_variant(const KanBasis* b);
-inline bool tuning_off(const char* name);
-inline bool tuning_on(const char* name);
-// The DMA-only forward on the expanded position-major operand (k_conv_fwd_pmdma): default B-spline specs (P = 9: 18-row steps),
-// channel pairs, 128-image and 128-output tiles.  Measured on 4x4 planes it LOSES to the dense halo forward (256->512: 0.76 vs 0.63 ms,
-// 512->512: 1.36 vs 1.24 -- 16 positions x 2 image tiles walk the 85 MB weight stream out of step), so the forward's position-major
-// limit stays at 4 positions (2x2 planes: 0.247 -> 0.211 ms); -DKAN_TUNING_KNOBS + KAN_PMDMA_FWD16=1 re-runs the experiment.
-bool pmdma_fwd_shape(const KanGeom* g, const KanBasis* b) {
-    const int f = fast_variant(b);
-    return !tuning_off("KAN_PMDMA_FWD") && (f == 1 || f == 2 || f == 9) && g->C % 2 == 0 && g->B % 128 == 0 && ((g->O + 63) / 64 * 64) % 128 == 0 &&
-           (long long)g->C * g->H * g->W * 9 * g->B * 4 < (1ll << 31);
-}
-bool want_pix_major(const KanGeom* g, const KanBasis* b, int which) {
-    const int plane = which == PM_BWD_DATA ? g->H * g->W : g->Ho * g->Wo;
-    const int limit = which == PM_BWD_WEIGHT ? 16 : (which == PM_FWD && pmdma_fwd_shape(g, b) && tuning_on("KAN_PMDMA_FWD16")) ? 16 : 4;
-    return b->kind != KAN_BASIS_RBF && plane <= limit && g->kh * g->kw <= 32 && (g->ph > 0 || g->pw > 0) && g->B >= 16;
-}
-
-// Split-K factor.  The conv kernels keep 4 workgroups per CU resident (1024 on the chip), so a grid of W workgroups
-// runs in ceil(W/1024) rounds and wastes the empty part of the last one (1184 workgroups = 58 % efficiency).  Model the
-// time of s splits as rounds(s) * (steps per workgroup + a fixed per-workgroup cost of ~6 steps for prologue, tile
-// store and the extra slab) and take the cheapest s with at least min_chunks steps per split and no empty split.
-// One slab costs its consumer a pass over `slab_bytes` (~4 TB/s => bytes/4e6 step-units of ~1 us) and never less
-// than ~1/6 of a step (latency of the serial slab loop on tiny outputs).
-double slab_cost_steps(double slab_bytes) { const double bw = slab_bytes / 4.0e6; return bw > 1.0 / 6.0 ? bw : 1.0 / 6.0; }
-
-int pick_splits(long long tiles, int chunks, int min_chunks, double slab_bytes, long long SLOTS = 1024) {
-    int cap = chunks / min_chunks; if (cap < 1) cap = 1;
-    if (cap > 1024) cap = 1024;
-    int best = 1; double best_cost = -1;
-    for (int s = 1; s <= cap; ++s) {
-        const int cps = ceil_div(chunks, s);
-        if (ceil_div(chunks, cps) != s) continue;            // would leave an empty split
-        const long long rounds = (tiles * s + SLOTS - 1) / SLOTS;
-        // + the consumer's serial pass over the s slabs (measured: 1024 slabs of a 62 KB tile cost the reducer 170 us,
-        // i.e. ~1/6 of a step each) -- only matters for tiny outputs split hundreds of ways (layer 0's weight gradient)
-        const double cost = (double)(rounds * (cps + 6)) + s * slab_cost_steps(slab_bytes);
-        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = s; }
-    }
-    return best;
-}
-
 int launch_ok(const char* what) {
     hipError_t e = hipGetLastError();
     (void)what;
@@ -2656,367 +2581,32 @@ int launch_ok(const char* what) {
     return 0;
 }
 
-int fast_variant(const KanBasis* b);
-// A/B switches for kernel experiments (NAME=0 turns a code path off).  The shipped library has none: it reads no
-// environment variable and keeps no mutable global state (include/kanconv.h).  Build with -DKAN_TUNING_KNOBS to get them.
-inline bool tuning_off(const char* name) {
-#ifdef KAN_TUNING_KNOBS
-    const char* e = getenv(name);
-    return e && atoi(e) == 0;
-#else
-    (void)name;
-    return false;
-#endif
-}
-inline bool tuning_on(const char* name) {              // opt-in experiments (NAME=1), same build flag
-#ifdef KAN_TUNING_KNOBS
-    const char* e = getenv(name);
-    return e && atoi(e) != 0;
-#else
-    (void)name;
-    return false;
-#endif
-}
-// 256-output tiles (512 threads, 2 workgroups per CU): every expanded input value then feeds 256 outputs instead of 128,
-// which halves the staging work (basis evaluation + LDS writes: ~13 % of the forward kernel's time, measured by
-// ablation) per MFMA.  Offered where the compile-time basis specs exist and O is a multiple of 256.
-bool big_tiles(const KanBasis* b, const KanPlan& pl) {
-    const bool off = tuning_off("KAN_BIG");
-    const int f = fast_variant(b);
-    return !off && pl.Opad % 256 == 0 && (f == 1 || f == 2 || f == 4 || f == 6);
-}
-// Halo forward kernel (k_conv_fwd_halo): 3x3 / stride 1 / pad 1 layers of the default B-spline specs whose 128-pixel
-// tiles are whole row blocks of one image or whole images (the KAN-VGG shapes 32x32, 16x16, 8x8, 4x4).
-bool halo_fwd(const KanGeom* g, const KanBasis* b) {
-    const bool off = tuning_off("KAN_HALO");
-    const int f = fast_variant(b);
-    if (off || !(f == 1 || f == 2 || f == 5 || f == 6 || f == 9 || f == 10)) return false;     // B-spline defaults, ChebyKAN degree 3, recurrence families degree 3, ReLU-KAN / GRAM-KAN defaults
-    if (b->kind == KAN_BASIS_POLY && b->order == 0) return false;          // order 0 = basis on a second, pre-normalised tensor (LegendreKAN): tap-major kernel
-    if (g->kh != 3 || g->kw != 3 || g->sh != 1 || g->sw != 1 || g->dh != 1 || g->dw != 1 || g->ph != 1 || g->pw != 1) return false;
-    if ((g->C & 1) || g->O % 128 != 0) return false;
-    if (want_pix_major(g, b, PM_FWD)) return false;
-    const int W = g->W, H = g->H;
-    return (W == 32 && H % 4 == 0) || (W == 16 && H % 8 == 0) || (W == 8 && H == 8) || (W == 4 && H == 4);
-}
-// Band forward kernel (kan_direct.hip): the layers that would otherwise run the tap-major kernel on 64-output tiles -- few input channels
-// (a model's first layer: the whole GEMM depth is a few hundred rows and re-expanding the input once per tap is most of the kernel) or an
-// output count that fills no 128-wide tile (64 -> 192) -- with a compile-time basis spec.  Any kernel size, stride, dilation, padding.
-bool dw_direct(const KanGeom* g, const KanBasis* b);
-bool band_fwd(const KanGeom* g, const KanBasis* b, KanBandCfg* out = nullptr) {
-    const int f = fast_variant(b);
-    if (tuning_off("KAN_BAND") || !(f >= 1 && f <= 6)) return false;
-    if (b->kind == KAN_BASIS_POLY && b->order == 0) return false;            // (LegendreKAN: second input tensor; keep it on the tap-major kernel for now)
-    if (dw_direct(g, b) || want_pix_major(g, b, PM_FWD) || halo_fwd(g, b)) return false;
-    // ... and (round 3, measured on the 13x13 ChebyKAN-AlexNet layers) every other layer of >= 4 taps that the halo kernel's plane list does not cover:
-    // one expansion per channel group instead of one per tap
-    if (!(g->C <= 3 || round_up(g->O, 64) % 128 != 0 || (g->kh * g->kw >= 4 && g->C % 2 == 0 && !tuning_off("KAN_BAND_WIDE")))) return false;
-    KanBandCfg c;
-    kan_band_cfg(g, b, f, &c);
-    if (out) *out = c;
-    return c.ok != 0;
-}
-struct FwdCfg { int TO, TP, tiles_o, tiles_p, chunks, splits, slots; };
-FwdCfg fwd_cfg(const KanGeom* g, const KanBasis* b, const KanPlan& pl) {
-    FwdCfg c;
-    c.TO = (big_tiles(b, pl) && !want_pix_major(g, b, PM_FWD)) ? 256 : (pl.Opad % 128 == 0) ? 128 : 64;   // (2x2 planes: -17 % with 256)
-    c.slots = c.TO == 256 ? 512 : 1024;
-    c.TP = 128;
-    c.tiles_o = pl.Opad / c.TO;
-    c.tiles_p = ceil_div((long long)g->B * g->Ho * g->Wo, c.TP);
-    c.chunks = pl.Kpad / pl.KC;
-    c.splits = pick_splits((long long)c.tiles_o * c.tiles_p * ngroups(g), c.chunks, 8, 4.0 * g->B * g->O * g->Ho * g->Wo * ngroups(g), c.slots);
-    if (halo_fwd(g, b)) {                            // the halo kernel splits the depth axis between channel pairs (9 steps each)
-        const int n_pairs = g->C / 2, pps = ceil_div(n_pairs, c.splits < n_pairs ? c.splits : n_pairs);
-        c.splits = ceil_div(n_pairs, pps);
-    }
-    return c;
-}
-// Row-ordered pixel blocks on 4x4 planes (k_conv_fwd_halo ROWBLK, k_conv_bwd_data RB): 1/6 of the MFMA blocks multiply the zero border and are skipped
-bool rowblk_fwd(const KanGeom* g, const KanBasis* b, const KanPlan& pl) {
-    return halo_fwd(g, b) && g->H == 4 && g->W == 4 && fwd_cfg(g, b, pl).TO == 256;
-}
-bool rowblk_bwd_data(const KanGeom* g, const KanBasis* b) {
-    const int f = fast_variant(b);
-    return !tuning_off("KAN_BD_ROWBLK") && (f == 1 || f == 2) && !want_pix_major(g, b, PM_BWD_DATA) && g->H == 4 && g->W == 4 && g->Ho == 4 && g->Wo == 4 &&
-           g->kh == 3 && g->kw == 3 && g->sh == 1 && g->sw == 1 && g->ph == 1 && g->pw == 1 && g->dh == 1 && g->dw == 1 && g->B % 8 == 0 && g->O % 16 == 0;
-}
-// With dead-tap skipping the tiles of one launch carry 4/9 ... 9/9 of the nominal work depending on their pixel
-// position (or tap, for the weight gradient).  Each tile therefore gets its own split count ceil(live steps / target)
-// so that every workgroup runs ~`target` live steps, and the target is chosen on the host by the same round model as
-// pick_splits, evaluated on the true per-class workgroup counts (a 1088-workgroup grid would run two rounds).
-// (Oversubscribing 4x with small equal splits instead was measured 15-40 % slower.)
-struct LiveClass { long long tiles; int live_steps; };           // tiles sharing one live-step count
-
-// Workgroups are dealt to the 8 XCDs round-robin by linear block id and never migrate.  Position-major pixel tiles are
-// ordered by position, so without care XCD k would get only the tiles of positions k, k+8, ... -- all light (corner)
-// or all heavy (centre) ones (measured: half the chip idle).  The host therefore deals the pixel tiles to 8 bins in
-// snake order of decreasing live work and hands the kernel the resulting order.
-TilePerm balance_tiles(const int* weight, int n) {
-    TilePerm p; p.n = 0;
-    if (n < 2 || n > PERM_MAX) return p;
-    int order[PERM_MAX];
-    for (int i = 0; i < n; ++i) order[i] = i;
-    for (int i = 1; i < n; ++i) {                                   // insertion sort, heaviest first (stable)
-        int v = order[i], j = i;
-        while (j > 0 && weight[order[j - 1]] < weight[v]) { order[j] = order[j - 1]; --j; }
-        order[j] = v;
-    }
-    // rank r goes to slot (bin = snake(r), depth = r / 8); slot s = depth*8 + bin is dispatched s-th => XCD = bin
-    for (int r = 0; r < n; ++r) {
-        const int depth = r / 8, k = r % 8, bin = (depth & 1) ? 7 - k : k;
-        int slot = depth * 8 + bin;
-        if (slot >= n) slot = r;                                    // ragged last row: keep it simple
-        p.idx[slot] = (unsigned short)order[r];
-    }
-    // the ragged fallback can collide; verify it is a permutation, else identity
-    bool seen[PERM_MAX] = {false};
-    for (int i = 0; i < n; ++i) { if (p.idx[i] >= n || seen[p.idx[i]]) return p; seen[p.idx[i]] = true; }
-    p.n = n;
-    return p;
-}
-int pick_target_steps(const LiveClass* cls, int ncls, int min_steps, double slab_bytes, int* max_splits, long long SLOTS = 1024) {
-    int hi = 1;
-    for (int i = 0; i < ncls; ++i) if (cls[i].live_steps > hi) hi = cls[i].live_steps;
-    int best = hi; double best_cost = -1; int best_ms = 1;
-    for (int t = min_steps < hi ? min_steps : hi; t <= hi; ++t) {
-        long long wgs = 0; int ms = 1;
-        for (int i = 0; i < ncls; ++i) {
-            const int sp = cls[i].live_steps > 0 ? ceil_div(cls[i].live_steps, t) : 1;
-            wgs += cls[i].tiles * sp;
-            if (sp > ms) ms = sp;
-        }
-        const long long rounds = (wgs + SLOTS - 1) / SLOTS;
-        const double cost = (double)(rounds * (t + 6)) + ms * slab_cost_steps(slab_bytes);
-        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = t; best_ms = ms; }
-    }
-    *max_splits = best_ms;
-    return best;
-}
-int live_taps_out(const KanGeom* g, int hw) {
-    int n = 0;
-    for (int tap = 0; tap < g->kh * g->kw; ++tap) {
-        const int r = tap / g->kw, t = tap % g->kw, ho = hw / g->Wo, wo = hw % g->Wo;
-        const int hi = ho * g->sh - g->ph + r * g->dh, wi = wo * g->sw - g->pw + t * g->dw;
-        n += (hi >= 0 && hi < g->H && wi >= 0 && wi < g->W);
-    }
-    return n;
-}
-int live_taps_in(const KanGeom* g, int hw) {
-    int n = 0;
-    for (int tap = 0; tap < g->kh * g->kw; ++tap) {
-        const int r = tap / g->kw, t = tap % g->kw, h = hw / g->W, w = hw % g->W;
-        const int hn = h + g->ph - r * g->dh, wn = w + g->pw - t * g->dw;
-        n += (hn >= 0 && wn >= 0 && hn % g->sh == 0 && wn % g->sw == 0 && hn / g->sh < g->Ho && wn / g->sw < g->Wo);
-    }
-    return n;
-}
-int live_positions_for_tap(const KanGeom* g, int tap) {
-    int n = 0;
-    for (int hw = 0; hw < g->Ho * g->Wo; ++hw) {
-        const int r = tap / g->kw, t = tap % g->kw, ho = hw / g->Wo, wo = hw % g->Wo;
-        const int hi = ho * g->sh - g->ph + r * g->dh, wi = wo * g->sw - g->pw + t * g->dw;
-        n += (hi >= 0 && hi < g->H && wi >= 0 && wi < g->W);
-    }
-    return n;
-}
-struct BdCfg { int CH, tiles_c, tiles_p, n_ob, Opad32, chunks, splits; };   // Opad32: rows per tap of wd (multiple of 32)
-BdCfg bd_cfg(const KanGeom* g, const KanPlan& pl) {
-    BdCfg c;
-    c.CH = 64 / pl.P;
-    c.tiles_c = ceil_div(g->C, 2 * c.CH);
-    c.tiles_p = ceil_div((long long)g->B * g->H * g->W, 128);
-    c.n_ob = ceil_div(g->O, 16);
-    c.Opad32 = round_up(g->O, 32);
-    c.chunks = g->kh * g->kw * c.n_ob;
-    c.splits = pick_splits((long long)c.tiles_c * c.tiles_p * ngroups(g), c.chunks, 8, 4.0 * g->B * g->C * g->H * g->W * ngroups(g));
-    return c;
-}
-// Halo weight-gradient kernel (k_conv_bwd_weight_halo): 3x3 / stride 1 / pad 1 layers of the default B-spline specs on square
-// 16x16 and 8x8 planes (KAN-VGG layers 1-3), whole 128-output tiles, single input tensor.  Its packed gradient is
-// CHANNEL-major: row = (c*T + tap)*P + p (kan_unpack_wgrad follows).
-// DMA-only position-major weight gradient on the expanded operand (k_conv_bwd_weight_pmdma): default B-spline specs, whole
-// 128-row tiles inside one tap, 16-image steps, 128-output tiles.
-bool pmdma_bwd_weight(const KanGeom* g, const KanBasis* b) {
-    const int f = fast_variant(b);
-    if (tuning_off("KAN_PMDMA") || !(f == 1 || f == 2 || f == 9 || f == 10)) return false;      // B-spline, ReLU-KAN, GRAM-KAN default specs
-    if (!want_pix_major(g, b, PM_BWD_WEIGHT)) return false;
-    const int P = b->n_basis + (b->act != KAN_ACT_NONE);
-    return (g->C * P) % 128 == 0 && g->B % 16 == 0 && round_up(g->O, 64) % 128 == 0 &&
-           (long long)g->C * g->H * g->W * P * g->B * 4 < (1ll << 31);
-}
-bool pmdma_fwd(const KanGeom* g, const KanBasis* b) { return pmdma_fwd_shape(g, b) && want_pix_major(g, b, PM_FWD); }
-bool halo_bwd_weight(const KanGeom* g, const KanBasis* b) {
-    const int f = fast_variant(b);
-    if (tuning_off("KAN_HALO_BW") || !(f == 1 || f == 2 || f == 9 || f == 10)) return false;
-    if (g->kh != 3 || g->kw != 3 || g->sh != 1 || g->sw != 1 || g->dh != 1 || g->dw != 1 || g->ph != 1 || g->pw != 1) return false;
-    if (round_up(g->O, 64) % 128 != 0 || g->C > 65535 / 81) return false;      // (row index = (c*9 + tap)*P + p stays far below 2^31)
-    if (g->H != g->W) return false;
-    // 4x4 planes: two images per band, dense (31 % of the products multiply padding).  The position-major tap-skipping launch
-    // wins where it has enough row tiles to balance its unequal taps (measured: 512 -> 512 142 TFLOP/s dense-equivalent against
-    // 134 here; 256 -> 512 118 against 134), so it keeps the wide layers.
-    if (g->W == 4) return !pmdma_bwd_weight(g, b) && g->B % 2 == 0 && g->C <= 256;
-    return g->W == 16 || g->W == 8;
-}
-bool pm_bwd_weight(const KanGeom* g, const KanBasis* b) { return want_pix_major(g, b, PM_BWD_WEIGHT) && !halo_bwd_weight(g, b); }
-struct BwHaloCfg { int R, nimg, spb, n_bands, tiles_r, tiles_o, splits, bands_per_split; };
-BwHaloCfg bw_halo_cfg(const KanGeom* g, const KanPlan& pl) {
-    BwHaloCfg c;
-    c.R = g->W == 16 ? 4 : g->W;
-    c.nimg = g->W == 4 ? 2 : 1;
-    c.spb = c.nimg * c.R * g->W / 16;
-    c.n_bands = g->B * (g->H / c.R) / c.nimg;
-    c.tiles_r = ceil_div(pl.K, 128);
-    c.tiles_o = pl.Opad / 128;
-    const long long tiles = (long long)c.tiles_r * c.tiles_o * ngroups(g);
-    const double slab_bytes = 4.0 * pl.K * pl.Opad * ngroups(g);
-    int best = 1; double best_cost = -1;
-    for (int sp = 1; sp <= c.n_bands && sp <= 1024; ++sp) {            // the round model of pick_splits, in bands of spb steps
-        const int bps = ceil_div(c.n_bands, sp);
-        if (ceil_div(c.n_bands, bps) != sp) continue;
-        const long long rounds = (tiles * sp + 1023) / 1024;
-        const double cost = (double)(rounds * (bps * c.spb + 6)) + sp * slab_cost_steps(slab_bytes);
-        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = sp; }
-    }
-    c.splits = best;
-    c.bands_per_split = ceil_div(c.n_bands, best);
-    return c;
-}
-struct BwCfg { int TR, TO, tiles_r, tiles_o, chunks, splits, slots; };
-BwCfg bw_cfg(const KanGeom* g, const KanBasis* b, const KanPlan& pl) {
-    BwCfg c;
-    c.TO = (big_tiles(b, pl) && !pm_bwd_weight(g, b)) ? 256 : (pl.Opad % 128 == 0) ? 128 : 64;
-    c.slots = c.TO == 256 ? 512 : 1024;
-    c.TR = c.TO == 64 ? 256 : 128;
-    c.tiles_r = ceil_div(pl.K, c.TR);
-    c.tiles_o = pl.Opad / c.TO;
-    c.chunks = ceil_div((long long)g->B * g->Ho * g->Wo, 16);
-    c.splits = pick_splits((long long)c.tiles_r * c.tiles_o * ngroups(g), c.chunks, 16, 4.0 * pl.K * pl.Opad * ngroups(g), c.slots);
-    return c;
-}
-
-// Depthwise groups (one input channel, <= 2 outputs per group, <= 9 taps): direct kernels instead of GEMM tiles.
-bool dw_direct(const KanGeom* g, const KanBasis* b) {
-    const bool off = tuning_off("KAN_DW");
-    const int T = g->kh * g->kw, P = b->n_basis + (b->act != KAN_ACT_NONE);
-    return !off && g->C == 1 && g->O <= 2 && T <= DW_T && T * P <= DW_MAX_TP;
-}
-int dw_weight_chunks(const KanGeom* g) {           // slabs of the depthwise weight gradient: ~2048 blocks over all groups
-    const long long total = (long long)g->B * g->Ho * g->Wo;
-    int s = ceil_div(2048, ngroups(g));
-    const int most = ceil_div(total, 256);
-    if (s > most) s = most;
-    if (s > 64) s = 64;
-    return s < 1 ? 1 : s;
-}
-
-int make_plan(const KanGeom* g, const KanBasis* b, KanPlan* pl) {
-    if (int rc = check(g, b)) return rc;
-    const int T = g->kh * g->kw;
-    pl->P = b->n_basis + (b->act != KAN_ACT_NONE);
-    pl->K = g->C * T * pl->P;
-    {   // LDS step of the forward kernel: KC in {16, 18} rows holding IPC <= 4 whole items; take the one wasting fewer rows
-        int i18 = 18 / pl->P, i16 = 16 / pl->P;
-        if (i18 > 4) i18 = 4;
-        if (i16 > 4) i16 = 4;
-        const bool use18 = (long long)i18 * pl->P * 16 > (long long)i16 * pl->P * 18;   // i18*P/18 > i16*P/16
-        pl->KC = use18 ? 18 : 16;
-        pl->IPC = use18 ? i18 : i16;
-        // 10 - 12 planes (FourierKAN grid 5: P = 11) hold ONE item in either step and leave 31 - 44 % of the rows -- of the MFMA work -- as zero padding:
-        // a 12-row step wastes 0 - 17 % (round 3; the generic forward is the only kernel that pays for pad rows)
-        if (pl->P >= 10 && pl->P <= 12) { pl->KC = 12; pl->IPC = 1; }
-        if (halo_fwd(g, b)) { pl->KC = 2 * pl->P; pl->IPC = 2; }      // pair order: one step = one tap of a channel pair, no pad rows
-    }
-    pl->Kpad = ceil_div(g->C * T, pl->IPC) * pl->KC;
-    KanBandCfg band;
-    const bool use_band = band_fwd(g, b, &band);
-    if (use_band) { pl->KC = band.NPLE; pl->IPC = band.NG; pl->Kpad = band.n_steps * band.NPLE; }      // band order: steps of even(NG * P) rows
-    pl->Opad = round_up(g->O, 64);
-    const int G = ngroups(g);
-    pl->packed_weight_bytes = (long long)G * pl->Kpad * pl->Opad * 4;
-    BdCfg bd = bd_cfg(g, *pl);
-    pl->bwd_data_weight_bytes = (long long)G * T * bd.Opad32 * bd.tiles_c * 128 * 4;
-    pl->fwd_slab_elems = (long long)g->B * g->y_bstride;
-    pl->bwd_data_slab_elems = (long long)g->B * g->x_bstride;
-    pl->bwd_weight_slab_elems = (long long)G * pl->K * pl->Opad;
-    pl->fwd_splits = use_band ? band.fwd_splits : fwd_cfg(g, b, *pl).splits;
-    pl->fwd_band = use_band ? 1 : 0;
-    // same layers, except the small padded planes whose weight gradient takes the position-major tap-skipping launch (its plan below sets the
-    // split count and the copies it wants); the packed gradient of a band launch is in the forward's band order
-    pl->bwd_weight_band = (use_band && band.bw_ok && !want_pix_major(g, b, PM_BWD_WEIGHT) && !tuning_off("KAN_BAND_BW")) ? 1 : 0;
-    pl->bwd_data_splits = bd.splits;
-    pl->bwd_weight_splits = halo_bwd_weight(g, b) ? bw_halo_cfg(g, *pl).splits : bw_cfg(g, b, *pl).splits;
-    if (pl->bwd_weight_band) {
-        pl->bwd_weight_splits = band.bw_splits;
-        pl->bwd_weight_slab_elems = (long long)G * pl->Kpad * pl->Opad;      // rows as the packed forward weights (pad rows included)
-    }
-    pl->x_pm_wanted = ((want_pix_major(g, b, PM_FWD) && !pmdma_fwd(g, b)) || (pm_bwd_weight(g, b) && !pmdma_bwd_weight(g, b))) ? 1 : 0;
-    pl->dz_pm_wanted = (want_pix_major(g, b, PM_BWD_DATA) || pm_bwd_weight(g, b)) ? 1 : 0;
-    pl->fwd_target = pl->bwd_data_target = pl->bwd_weight_target = 0;
-    pl->fwd_halo = halo_fwd(g, b) ? 1 : 0;
-    pl->bwd_weight_halo = (halo_bwd_weight(g, b) && !pl->bwd_weight_band) ? 1 : 0;
-    pl->e_pm_wanted = 0; pl->fwd_expanded = 0; pl->bwd_weight_expanded = 0; pl->e_pm_elems = 0;
-    pl->row_blocks = (rowblk_fwd(g, b, *pl) ? 1 : 0) | (rowblk_bwd_data(g, b) ? 2 : 0);
-    if (dw_direct(g, b)) {
-        pl->fwd_halo = pl->bwd_weight_halo = pl->fwd_band = pl->bwd_weight_band = 0;   // direct depthwise kernels: no split-K on the data path, no position-major copies
-        pl->fwd_splits = pl->bwd_data_splits = 1;
-        pl->bwd_weight_splits = dw_weight_chunks(g);
-        pl->x_pm_wanted = pl->dz_pm_wanted = 0;
-        pl->bwd_data_weight_bytes = pl->packed_weight_bytes;      // the direct bwd-data kernel reads the forward layout: wd = copy of wp
-        return 0;
-    }
-    if (want_pix_major(g, b, PM_FWD)) {          // forward: one class per output position; a tap holds C/IPC steps
-        LiveClass cls[16]; const int plane = g->Ho * g->Wo; FwdCfg fc = fwd_cfg(g, b, *pl);
-        const long long tiles_per_pos = (long long)ceil_div(g->B, fc.TP) * fc.tiles_o * G;
-        for (int hw = 0; hw < plane; ++hw) cls[hw] = LiveClass{tiles_per_pos, live_taps_out(g, hw) * ceil_div(g->C, pl->IPC)};
-        pl->fwd_target = pick_target_steps(cls, plane, 8, 4.0 * g->B * g->O * g->Ho * g->Wo * G, &pl->fwd_splits, fc.slots);
-    }
-    pl->fwd_expanded = pmdma_fwd(g, b) ? 1 : 0;
-    pl->bwd_weight_expanded = pmdma_bwd_weight(g, b) ? 1 : 0;
-    if (pl->bwd_weight_expanded || pl->fwd_expanded) {    // the expanded position-major copy (kan_position_major_expanded) feeds the forward / the weight gradient
-        pl->e_pm_wanted = 1;
-        pl->e_pm_elems = (long long)G * g->C * g->H * g->W * pl->P * g->B + 256;       // + a pad the expansion kernel may scribble on
-    }
-    if (pm_bwd_weight(g, b)) {   // bwd-weight: one class per tap; a live position holds B/16 steps
-        LiveClass cw[32]; BwCfg wc = bw_cfg(g, b, *pl);
-        const long long tiles_per_tap = (long long)ceil_div((long long)g->C * pl->P, wc.TR) * wc.tiles_o * G;
-        for (int tap = 0; tap < T; ++tap) cw[tap] = LiveClass{tiles_per_tap, live_positions_for_tap(g, tap) * ceil_div(g->B, 16)};
-        pl->bwd_weight_target = pick_target_steps(cw, T, 16, 4.0 * pl->K * pl->Opad * G, &pl->bwd_weight_splits, wc.slots);
-    }
-    if (want_pix_major(g, b, PM_BWD_DATA)) {     // bwd-data: one class per input position; a tap holds n_ob steps
-        LiveClass cls[16]; const int plane = g->H * g->W;
-        const long long tiles_per_pos = (long long)ceil_div(g->B, 128) * bd.tiles_c * G;
-        for (int hw = 0; hw < plane; ++hw) cls[hw] = LiveClass{tiles_per_pos, live_taps_in(g, hw) * bd.n_ob};
-        pl->bwd_data_target = pick_target_steps(cls, plane, 8, 4.0 * g->B * g->C * g->H * g->W * G, &pl->bwd_data_splits);
-    }
-    return 0;
-}
-
-// Compile-time specialisation available?  (numbers as documented at stage_unit; 0 = generic)
-int fast_variant(const KanBasis* b) {
-    if (b->kind == KAN_BASIS_BSPLINE && b->n_basis == 8 && b->order == 3) return b->act == KAN_ACT_SILU ? 1 : b->act == KAN_ACT_GELU ? 2 : 0;
-    if (b->kind == KAN_BASIS_RBF && b->act == KAN_ACT_SILU && (b->n_basis == 8 || b->n_basis == 5)) return b->n_basis == 8 ? 3 : 8;
-    if (b->kind == KAN_BASIS_CHEBY && b->act == KAN_ACT_NONE) return b->n_basis == 5 ? 4 : b->n_basis == 4 ? 5 : 0;
-    if (b->kind == KAN_BASIS_POLY && b->act != KAN_ACT_NONE) return b->n_basis == 4 ? 6 : b->n_basis == 3 ? 7 : b->n_basis == 1 ? 11 : 0;
-    if (b->kind == KAN_BASIS_RELU && b->act == KAN_ACT_SILU && b->n_basis == 8) return 9;      // halo kernels only
-    if (b->kind == KAN_BASIS_GRAM && b->act == KAN_ACT_SILU && b->n_basis == 4) return 10;     // halo kernels only
-    return 0;
-}
-
-PackGeo pack_geo(const KanGeom* g, const KanBasis* b, const KanPlan& pl, bool flat) {
+// Layout of the packed weights (wp, flat == false) or of the packed weight gradient (flat == true) the plan's routes read / write.
+PackGeo pack_geo(const KanGeom* g, const KanBasis* b, const ConvPlan& cp, bool flat) {
+    const KanPlan& pl = cp.pub;
     PackGeo q;
     q.O = g->O; q.C = g->C; q.T = g->kh * g->kw; q.P = pl.P; q.hb = b->act != KAN_ACT_NONE; q.nb = b->n_basis;
     q.IPC = flat ? 1 : pl.IPC; q.KC = flat ? pl.P : pl.KC; q.Opad = pl.Opad;
-    q.pair = (!flat && halo_fwd(g, b)) ? 1 : 0;
-    q.cmajor = (flat && halo_bwd_weight(g, b)) ? 1 : 0;
-    q.band = 0;
-    KanBandCfg band;
-    if (((!flat && pl.fwd_band) || (flat && pl.bwd_weight_band)) && band_fwd(g, b, &band)) {
-        q.band = 1; q.cmajor = 0;
-        q.IPC = pl.IPC; q.KC = pl.KC; q.divIPC = make_fastdiv(q.IPC);       // (the flat gradient of a band layer has the forward's rows, pad rows included)
-        for (int i = 0; i < q.T; ++i) { q.tap_step[i] = band.tap_step[i]; q.tap_nt[i] = band.tap_nt[i]; }
+    q.pair = (!flat && cp.fwd == Route::HALO) ? 1 : 0;
+    q.cmajor = (flat && cp.bwd_weight == Route::HALO) ? 1 : 0;
+    q.band = (flat ? cp.bwd_weight : cp.fwd) == Route::BAND ? 1 : 0;
+    if (q.band) {                                     // (the flat gradient of a band layer has the forward's rows, pad rows included)
+        q.IPC = pl.IPC; q.KC = pl.KC;
+        for (int i = 0; i < q.T; ++i) { q.tap_step[i] = cp.band.tap_step[i]; q.tap_nt[i] = cp.band.tap_nt[i]; }
     }
     q.divT = make_fastdiv(q.T); q.divNb = make_fastdiv(q.nb); q.divIPC = make_fastdiv(q.IPC); q.divP = make_fastdiv(q.P);
     return q;
+}
+
+// XCD-balanced order of the position-major pixel tiles, weighted by their live work
+template <class Weight>
+TilePerm tile_perm(int tiles_p, Weight weight) {
+    TilePerm perm; perm.n = 0;
+    if (tiles_p > PERM_MAX) return perm;
+    int w[PERM_MAX];
+    for (int t = 0; t < tiles_p; ++t) w[t] = weight(t);
+    perm.n = balance_tiles(w, tiles_p, perm.idx);
+    return perm;
 }
 
 template <int G>
@@ -3153,7 +2743,10 @@ const char* kan_last_error(void) { return g_err; }
 
 int kan_plan(const KanGeom* geom, const KanBasis* basis, KanPlan* plan) {
     if (!plan) return fail("null plan");
-    return make_plan(geom, basis, plan);
+    ConvPlan cp;
+    if (int rc = plan_conv(geom, basis, &cp)) return rc;
+    *plan = cp.pub;
+    return 0;
 }
 
 // Does packing this geometry need wp cleared first (pad rows)?  Cached packing cannot skip a clear conditionally.
@@ -3164,15 +2757,16 @@ static bool pack_needs_clear(const KanGeom* g, const KanPlan& pl) {
 
 static int pack_weights_impl(const float* w_base, const float* w_basis, float* wp, float* wd, const KanGeom* g, const KanBasis* b,
                              const unsigned long long* fp, int fp_cur, void* stream) {
-    KanPlan pl;
-    if (int rc = make_plan(g, b, &pl)) return rc;
+    ConvPlan cp;
+    if (int rc = plan_conv(g, b, &cp)) return rc;
+    const KanPlan& pl = cp.pub;
     const int hb = b->act != KAN_ACT_NONE;
     if ((hb && !w_base) || !w_basis || !wp) return fail("null weight pointer");
     hipStream_t st = (hipStream_t)stream;
     const int T = g->kh * g->kw, NI = g->C * T, G = ngroups(g);
     const long long wp_gs = (long long)pl.Kpad * pl.Opad;          // floats per group in wp
-    PackGeo q = pack_geo(g, b, pl, false);
-    if (fp && (pack_needs_clear(g, pl) || dw_direct(g, b))) return fail("cached packing is not offered for this geometry (kan_pack_cacheable)");
+    PackGeo q = pack_geo(g, b, cp, false);
+    if (fp && (pack_needs_clear(g, pl) || cp.fwd == Route::DW)) return fail("cached packing is not offered for this geometry (kan_pack_cacheable)");
     // rows no source element maps to must be zero: pad rows of every chunk, and the missing items of the last chunk
     if (pl.KC != pl.IPC * pl.P || (pl.fwd_band && pack_needs_clear(g, pl))) {     // (whole-buffer clear only for P that do not divide the step)
         if (hipMemsetAsync(wp, 0, (size_t)pl.packed_weight_bytes, st) != hipSuccess) return fail("memset failed");
@@ -3190,10 +2784,10 @@ static int pack_weights_impl(const float* w_base, const float* w_basis, float* w
     const long long cap = fp ? 1024 : 4096;             // cached mode: the usual outcome is an early exit, keep the grid small
     dim3 grid((unsigned)(n_tiles < cap ? n_tiles : cap), 1, G);
     hipLaunchKernelGGL(k_pack, grid, dim3(256), 0, st, w_base, w_basis, wp, q, nb_base, wp_gs, tiles_x, tiles_y, fp, fp_cur);
-    if (wd && dw_direct(g, b)) {
+    if (wd && cp.bwd_data == Route::DW) {
         if (hipMemcpyAsync(wd, wp, (size_t)pl.packed_weight_bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail("memcpy failed");
     } else if (wd) {
-        BdCfg c = bd_cfg(g, pl);
+        const BdCfg& c = cp.bd;
         const int bx = c.tiles_c * 4, by = c.Opad32 / 32 * G;
         const long long nt = (long long)bx * by;
         const long long capd = fp ? 128 : 1024;
@@ -3208,10 +2802,10 @@ int kan_pack_weights(const float* w_base, const float* w_basis, float* wp, float
 }
 
 int kan_pack_cacheable(const KanGeom* g, const KanBasis* b) {
-    KanPlan pl;
-    if (make_plan(g, b, &pl)) return 0;
+    ConvPlan cp;
+    if (plan_conv(g, b, &cp)) return 0;
     if ((long long)g->O * g->C * (b->n_basis + 1) * g->kh * g->kw >= (1ll << 31)) return 0;      // 32-bit element positions in the fingerprint
-    return (!pack_needs_clear(g, pl) && !dw_direct(g, b) && ngroups(g) == 1) ? 1 : 0;
+    return (!pack_needs_clear(g, cp.pub) && cp.fwd != Route::DW && ngroups(g) == 1) ? 1 : 0;
 }
 
 int kan_pack_weights_cached(const float* w_base, const float* w_basis, float* wp, float* wd, const KanGeom* g, const KanBasis* b,
@@ -3233,14 +2827,15 @@ int kan_pack_weights_cached(const float* w_base, const float* w_basis, float* wp
 }
 
 int kan_unpack_wgrad(const float* dwp, float* dw_base, float* dw_basis, const KanGeom* g, const KanBasis* b, void* stream) {
-    KanPlan pl;
-    if (int rc = make_plan(g, b, &pl)) return rc;
+    ConvPlan cp;
+    if (int rc = plan_conv(g, b, &cp)) return rc;
+    const KanPlan& pl = cp.pub;
     const int hb = b->act != KAN_ACT_NONE;
     if ((hb && !dw_base) || !dw_basis || !dwp) return fail("null weight-gradient pointer");
     hipStream_t st = (hipStream_t)stream;
     const int T = g->kh * g->kw, G = ngroups(g);
     const long long dwp_gs = (long long)(pl.bwd_weight_band ? pl.Kpad : pl.K) * pl.Opad;
-    PackGeo q = pack_geo(g, b, pl, true);
+    PackGeo q = pack_geo(g, b, cp, true);
     int n_slabs = pl.bwd_weight_splits;
     if (n_slabs >= 32) {                                      // (dwp is the caller's scratch: slab 0 becomes the sum)
         hipLaunchKernelGGL(k_fold_slabs, dim3(ceil_div(pl.bwd_weight_slab_elems, 64)), dim3(256), 0, st, const_cast<float*>(dwp), n_slabs,
@@ -3262,120 +2857,84 @@ int kan_position_major(const float* src, float* dst, int B, int Cn, int HW, long
 
 int kan_conv_fwd(const float* x, const float* xn, const float* wp, float* z, const KanGeom* g, const KanBasis* b, const float* x_pm,
                  void* stream) {
-    KanPlan pl;
-    if (int rc = make_plan(g, b, &pl)) return rc;
+    ConvPlan cp;
+    if (int rc = plan_conv(g, b, &cp)) return rc;
+    const KanPlan& pl = cp.pub;
     if (!x || !xn || !wp || !z) return fail("null tensor pointer");
     if ((b->kind == KAN_BASIS_RELU || b->kind == KAN_BASIS_GRAM) && !b->chan_table) return fail("ReLU / Gram bases need their device parameter table (chan_table)");
-    if (dw_direct(g, b)) {
+    hipStream_t st = (hipStream_t)stream;
+    if (cp.fwd == Route::DW) {
         DevGeom dgd = dev_geom(g); DevBasis dbd = dev_basis(b);
         dim3 grid(ceil_div((long long)g->B * g->Ho * g->Wo, 256), ngroups(g));
-#define KAN_DWF(KIND) hipLaunchKernelGGL((k_dw_fwd<KIND>), grid, dim3(256), 0, (hipStream_t)stream, x, xn, wp, z, dgd, dbd, pl.Opad, pl.IPC, pl.KC, pl.Kpad)
-        switch (b->kind) {
-            case KAN_BASIS_BSPLINE: KAN_DWF(KAN_BASIS_BSPLINE); break;
-            case KAN_BASIS_RBF: KAN_DWF(KAN_BASIS_RBF); break;
-            case KAN_BASIS_POLY: KAN_DWF(KAN_BASIS_POLY); break;
-            case KAN_BASIS_FOURIER: KAN_DWF(KAN_BASIS_FOURIER); break;
-            case KAN_BASIS_RELU: KAN_DWF(KAN_BASIS_RELU); break;
-            case KAN_BASIS_GRAM: KAN_DWF(KAN_BASIS_GRAM); break;
-            default: KAN_DWF(KAN_BASIS_CHEBY); break;
-        }
-#undef KAN_DWF
+        dispatch_kind(b->kind, [&](auto kind) {
+            hipLaunchKernelGGL((k_dw_fwd<decltype(kind)::value>), grid, dim3(256), 0, st, x, xn, wp, z, dgd, dbd, pl.Opad, pl.IPC, pl.KC, pl.Kpad);
+        });
         return launch_ok("dw_fwd");
     }
-    if (pl.fwd_band) {
-        KanBandCfg band;
-        if (!band_fwd(g, b, &band)) return fail("internal: plan and band configuration disagree");
+    if (cp.fwd == Route::BAND) {
         if (x != xn && b->kind != KAN_BASIS_RBF && b->kind != KAN_BASIS_POLY) return fail("this basis / activation pair runs on single-input kernels: pass xn == x");
-        return kan_band_fwd_launch(x, xn, wp, z, g, b, &band, pl.fwd_splits, pl.fwd_slab_elems, stream);
+        return kan_band_fwd_launch(x, xn, wp, z, g, b, &cp.band, pl.fwd_splits, pl.fwd_slab_elems, stream);
     }
-    FwdCfg c = fwd_cfg(g, b, pl);
-    if (halo_fwd(g, b)) {
+    const FwdCfg& c = cp.fc;
+    if ((long long)c.tiles_o * ngroups(g) > 65535) return fail("groups * output tiles exceed the grid limit");
+    const unsigned x_bytes = (unsigned)((long long)g->B * g->x_bstride * 4);
+    if (cp.fwd == Route::HALO) {
         if (x != xn) return fail("internal: halo forward kernel needs a single input tensor");
         DevGeom dgh = dev_geom(g); DevBasis dbh = dev_basis(b);
-        const int n_pairs = g->C / 2, pps = ceil_div(n_pairs, pl.fwd_splits), fv = fast_variant(b);
-        if ((long long)c.tiles_o * ngroups(g) > 65535) return fail("groups * output tiles exceed the grid limit");
+        const int n_pairs = g->C / 2, pps = ceil_div(n_pairs, pl.fwd_splits);
         dim3 gridh(c.tiles_p, c.tiles_o * ngroups(g), pl.fwd_splits);
-#define KAN_HALO(F, WOV, WV, RV, NV) \
-    hipLaunchKernelGGL((k_conv_fwd_halo<F, WOV, WV, RV, NV>), gridh, dim3(WOV * 128), 0, (hipStream_t)stream, x, wp, z, dgh, dbh, pl.Opad, n_pairs, pps, pl.fwd_slab_elems, (unsigned)((long long)g->B * g->x_bstride * 4), c.tiles_o)
-#define KAN_HALO_SHAPE(F, WOV)                                              \
-    do {                                                                    \
-        if (g->W == 32) KAN_HALO(F, WOV, 32, 4, 1);                          \
-        else if (g->W == 16) KAN_HALO(F, WOV, 16, 8, 1);                     \
-        else if (g->W == 8) KAN_HALO(F, WOV, 8, 8, 2);                       \
-        else KAN_HALO(F, WOV, 4, 4, 8);                                      \
-    } while (0)
-        if (c.TO == 256 && fv == 1) KAN_HALO_SHAPE(1, 4);
-        else if (c.TO == 256 && fv == 2) KAN_HALO_SHAPE(2, 4);
-        else if (c.TO == 256 && fv == 6) KAN_HALO_SHAPE(6, 4);
-        else if (c.TO == 128 && fv == 1) KAN_HALO_SHAPE(1, 2);
-        else if (c.TO == 128 && fv == 2) KAN_HALO_SHAPE(2, 2);
-        else if (c.TO == 128 && fv == 5) KAN_HALO_SHAPE(5, 2);
-        else if (c.TO == 128 && fv == 6) KAN_HALO_SHAPE(6, 2);
-        else if (c.TO == 128 && fv == 9) KAN_HALO_SHAPE(9, 2);
-        else if (c.TO == 128 && fv == 10) KAN_HALO_SHAPE(10, 2);
-        else return fail("internal: no halo forward kernel for this basis / tile");
-#undef KAN_HALO_SHAPE
-#undef KAN_HALO
+        dispatch_fast<ON_HALO_FWD>(cp.fast, [&](auto fv) {
+            constexpr int F = decltype(fv)::value;
+            auto launch = [&](auto wo, auto w, auto r, auto nimg) {       // (output waves, plane width, rows per tile, images per tile)
+                constexpr int WOV = decltype(wo)::value;
+                hipLaunchKernelGGL((k_conv_fwd_halo<F, WOV, decltype(w)::value, decltype(r)::value, decltype(nimg)::value>), gridh, dim3(WOV * 128), 0,
+                                   st, x, wp, z, dgh, dbh, pl.Opad, n_pairs, pps, pl.fwd_slab_elems, x_bytes, c.tiles_o);
+            };
+            auto planes = [&](auto wo) {
+                if (g->W == 32) launch(wo, IC<32>{}, IC<4>{}, IC<1>{});
+                else if (g->W == 16) launch(wo, IC<16>{}, IC<8>{}, IC<1>{});
+                else if (g->W == 8) launch(wo, IC<8>{}, IC<8>{}, IC<2>{});
+                else launch(wo, IC<4>{}, IC<4>{}, IC<8>{});
+            };
+            if constexpr (fast_has(F, ON_BIG_TILES)) {
+                if (c.TO == 256) return planes(IC<4>{});
+            }
+            planes(IC<2>{});
+        });
         return launch_ok("conv_fwd_halo");
     }
     DevGeom dg = dev_geom(g);
-    dg.pix_major = (x_pm && x == xn && want_pix_major(g, b, PM_FWD)) ? 1 : 0;      // (one copy serves both inputs only when they are the same)
+    dg.pix_major = (x_pm && x == xn && cp.pm_fwd) ? 1 : 0;      // (one copy serves both inputs only when they are the same)
     if (dg.pix_major) { x = x_pm; xn = x_pm; }
     DevBasis db = dev_basis(b);
-    hipStream_t st = (hipStream_t)stream;
-    if ((long long)c.tiles_o * ngroups(g) > 65535) return fail("groups * output tiles exceed the grid limit");
     dim3 grid(c.tiles_p, c.tiles_o * ngroups(g), pl.fwd_splits);   // always the plan's slab count: the consumer sums exactly that many
-    int cps = dg.pix_major ? pl.fwd_target : ceil_div(c.chunks, pl.fwd_splits);
+    const int cps = dg.pix_major ? pl.fwd_target : ceil_div(c.chunks, pl.fwd_splits);
     TilePerm perm; perm.n = 0;
-    if (dg.pix_major && c.tiles_p <= PERM_MAX) {             // weight of a pixel tile = its own split count (live work)
-        int w[PERM_MAX];
-        for (int t = 0; t < c.tiles_p; ++t) {
-            const int hw = (int)(((long long)t * c.TP) / g->B);
-            w[t] = ceil_div(live_taps_out(g, hw < g->Ho * g->Wo ? hw : 0) * ceil_div(g->C, pl.IPC), cps > 0 ? cps : 1);
-        }
-        perm = balance_tiles(w, c.tiles_p);
-    }
-#define KAN_FWD(KIND, WO, WP, KCV) KAN_FWD2(KIND, 0, WO, WP, KCV)
-#define KAN_FWD2(KIND, FAST, WO, WP, KCV) \
-    hipLaunchKernelGGL((k_conv_fwd<KIND, FAST, WO, WP, KCV>), grid, dim3(WO * WP * 64), 0, st, x, xn, wp, z, dg, db, pl.Opad, pl.IPC, c.chunks, cps, pl.fwd_slab_elems, (unsigned)((long long)g->B * g->x_bstride * 4), perm, c.tiles_o)
-#define KAN_FWD_KIND(KIND)                                                     \
-    do {                                                                       \
-        if (c.TO == 128 && pl.KC == 18) KAN_FWD(KIND, 2, 2, 18);               \
-        else if (c.TO == 128 && pl.KC == 12) KAN_FWD(KIND, 2, 2, 12);          \
-        else if (c.TO == 128) KAN_FWD(KIND, 2, 2, 16);                         \
-        else if (pl.KC == 18) KAN_FWD(KIND, 1, 2, 18);                         \
-        else if (pl.KC == 12) KAN_FWD(KIND, 1, 2, 12);                         \
-        else KAN_FWD(KIND, 1, 2, 16);                                          \
-    } while (0)
-    const int fast = fast_variant(b);
-    if (x != xn && fast != 0 && b->kind != KAN_BASIS_RBF && b->kind != KAN_BASIS_POLY)
+    if (dg.pix_major) perm = tile_perm(c.tiles_p, [&](int t) {     // weight of a pixel tile = its own split count (live work)
+        const int hw = (int)(((long long)t * c.TP) / g->B);
+        return ceil_div(live_taps_out(g, hw < g->Ho * g->Wo ? hw : 0) * ceil_div(g->C, pl.IPC), cps > 0 ? cps : 1);
+    });
+    if (x != xn && cp.fast != FAST_GENERIC && b->kind != KAN_BASIS_RBF && b->kind != KAN_BASIS_POLY)
         return fail("this basis / activation pair runs on single-input kernels: pass xn == x");
-#define KAN_FWD_FAST(KIND, F, KCV) do { if (c.TO == 128) KAN_FWD2(KIND, F, 2, 2, KCV); else KAN_FWD2(KIND, F, 1, 2, KCV); } while (0)
-    if (c.TO == 256 && fast == 1) KAN_FWD2(KAN_BASIS_BSPLINE, 1, 4, 2, 18);
-    else if (c.TO == 256 && fast == 2) KAN_FWD2(KAN_BASIS_BSPLINE, 2, 4, 2, 18);
-    else if (c.TO == 256 && fast == 4) KAN_FWD2(KAN_BASIS_CHEBY, 4, 4, 2, 16);
-    else if (c.TO == 256 && fast == 6) KAN_FWD2(KAN_BASIS_POLY, 6, 4, 2, 16);
-    else if (c.TO == 256) return fail("internal: no 256-output forward kernel for this basis");
-    else if (fast == 1) KAN_FWD_FAST(KAN_BASIS_BSPLINE, 1, 18);
-    else if (fast == 2) KAN_FWD_FAST(KAN_BASIS_BSPLINE, 2, 18);
-    else if (fast == 3) KAN_FWD_FAST(KAN_BASIS_RBF, 3, 18);
-    else if (fast == 8) KAN_FWD_FAST(KAN_BASIS_RBF, 8, 18);
-    else if (fast == 4) KAN_FWD_FAST(KAN_BASIS_CHEBY, 4, 16);
-    else if (fast == 5) KAN_FWD_FAST(KAN_BASIS_CHEBY, 5, 16);
-    else if (fast == 6) KAN_FWD_FAST(KAN_BASIS_POLY, 6, 16);
-    else if (fast == 7) KAN_FWD_FAST(KAN_BASIS_POLY, 7, 16);
-    else if (fast == 11) KAN_FWD_FAST(KAN_BASIS_POLY, 11, 16);
-    else if (b->kind == KAN_BASIS_BSPLINE) KAN_FWD_KIND(KAN_BASIS_BSPLINE);
-    else if (b->kind == KAN_BASIS_RBF) KAN_FWD_KIND(KAN_BASIS_RBF);
-    else if (b->kind == KAN_BASIS_POLY) KAN_FWD_KIND(KAN_BASIS_POLY);
-    else if (b->kind == KAN_BASIS_FOURIER) KAN_FWD_KIND(KAN_BASIS_FOURIER);
-    else if (b->kind == KAN_BASIS_RELU) KAN_FWD_KIND(KAN_BASIS_RELU);
-    else if (b->kind == KAN_BASIS_GRAM) KAN_FWD_KIND(KAN_BASIS_GRAM);
-    else KAN_FWD_KIND(KAN_BASIS_CHEBY);
-#undef KAN_FWD_FAST
-#undef KAN_FWD_KIND
-#undef KAN_FWD2
-#undef KAN_FWD
+    auto launch = [&](auto kind, auto fast, auto wo, auto kc) {
+        constexpr int WO = decltype(wo)::value;
+        hipLaunchKernelGGL((k_conv_fwd<decltype(kind)::value, decltype(fast)::value, WO, 2, decltype(kc)::value>), grid, dim3(WO * 2 * 64), 0, st,
+                           x, xn, wp, z, dg, db, pl.Opad, pl.IPC, c.chunks, cps, pl.fwd_slab_elems, x_bytes, perm, c.tiles_o);
+    };
+    const bool fast = dispatch_fast<ON_TAP_MAJOR>(cp.fast, [&](auto fv) {
+        constexpr int F = decltype(fv)::value;
+        if constexpr (fast_has(F, ON_BIG_TILES)) {
+            if (c.TO == 256) return launch(IC<fast_kind(F)>{}, fv, IC<4>{}, IC<fast_kc(F)>{});
+        }
+        if (c.TO == 128) launch(IC<fast_kind(F)>{}, fv, IC<2>{}, IC<fast_kc(F)>{});
+        else launch(IC<fast_kind(F)>{}, fv, IC<1>{}, IC<fast_kc(F)>{});
+    });
+    if (!fast) dispatch_kind(b->kind, [&](auto kind) {
+        pick<18, 12, 16>(pl.KC, [&](auto kc) {
+            if (c.TO == 128) launch(kind, IC<FAST_GENERIC>{}, IC<2>{}, kc);
+            else launch(kind, IC<FAST_GENERIC>{}, IC<1>{}, kc);
+        });
+    });
     return launch_ok("conv_fwd");
 }
 
@@ -3391,185 +2950,134 @@ int kan_conv_bwd_data_params(const float* dz, const float* x, const float* xn, c
                              const KanGeom* g, const KanBasis* b, const float* dz_pm, void* stream) {
     if (!dparams) return fail("null dparams");
     if (b && b->kind != KAN_BASIS_RELU && b->kind != KAN_BASIS_GRAM) return fail("kan_conv_bwd_data_params: only the ReLU-KAN and GRAM bases accumulate parameter gradients in this launch");
-    if (g && b && dw_direct(g, b)) return fail("kan_conv_bwd_data_params: depthwise layers take the weight-gradient route");
     return conv_bwd_data_impl(dz, x, xn, wd, dx, dxn, dparams, g, b, dz_pm, stream);
 }
 
 static int conv_bwd_data_impl(const float* dz, const float* x, const float* xn, const float* wd, float* dx, float* dxn, float* dpar,
                               const KanGeom* g, const KanBasis* b, const float* dz_pm, void* stream) {
-    KanPlan pl;
-    if (int rc = make_plan(g, b, &pl)) return rc;
+    ConvPlan cp;
+    if (int rc = plan_conv(g, b, &cp)) return rc;
+    const KanPlan& pl = cp.pub;
+    if (dpar && cp.bwd_data == Route::DW) return fail("kan_conv_bwd_data_params: depthwise layers take the weight-gradient route");
     if (!dz || !x || !xn || !wd || !dx) return fail("null tensor pointer");
     if ((b->kind == KAN_BASIS_RELU || b->kind == KAN_BASIS_GRAM) && !b->chan_table) return fail("ReLU / Gram bases need their device parameter table (chan_table)");
     if (!dxn && x != xn) return fail("dxn is required when xn != x");
-    if (dw_direct(g, b)) {
+    hipStream_t st = (hipStream_t)stream;
+    if (cp.bwd_data == Route::DW) {
         DevGeom dgd = dev_geom(g); DevBasis dbd = dev_basis(b);
         dim3 grid(ceil_div((long long)g->B * g->H * g->W, 256), ngroups(g));
-#define KAN_DWD(KIND) hipLaunchKernelGGL((k_dw_bwd_data<KIND>), grid, dim3(256), 0, (hipStream_t)stream, dz, x, xn, wd, dx, dxn, dgd, dbd, pl.Opad, pl.IPC, pl.KC, pl.Kpad)
-        switch (b->kind) {
-            case KAN_BASIS_BSPLINE: KAN_DWD(KAN_BASIS_BSPLINE); break;
-            case KAN_BASIS_RBF: KAN_DWD(KAN_BASIS_RBF); break;
-            case KAN_BASIS_POLY: KAN_DWD(KAN_BASIS_POLY); break;
-            case KAN_BASIS_FOURIER: KAN_DWD(KAN_BASIS_FOURIER); break;
-            case KAN_BASIS_RELU: KAN_DWD(KAN_BASIS_RELU); break;
-            case KAN_BASIS_GRAM: KAN_DWD(KAN_BASIS_GRAM); break;
-            default: KAN_DWD(KAN_BASIS_CHEBY); break;
-        }
-#undef KAN_DWD
+        dispatch_kind(b->kind, [&](auto kind) {
+            hipLaunchKernelGGL((k_dw_bwd_data<decltype(kind)::value>), grid, dim3(256), 0, st, dz, x, xn, wd, dx, dxn, dgd, dbd, pl.Opad, pl.IPC, pl.KC, pl.Kpad);
+        });
         return launch_ok("dw_bwd_data");
     }
-    BdCfg c = bd_cfg(g, pl);
+    const BdCfg& c = cp.bd;
     DevGeom dg = dev_geom(g);
-    dg.pix_major = (dz_pm && want_pix_major(g, b, PM_BWD_DATA)) ? 1 : 0;
+    dg.pix_major = (dz_pm && cp.pm_bwd_data) ? 1 : 0;
     if (dg.pix_major) dz = dz_pm;
     DevBasis db = dev_basis(b);
-    hipStream_t st = (hipStream_t)stream;
     if ((long long)c.tiles_c * ngroups(g) > 65535) return fail("groups * channel tiles exceed the grid limit");
     dim3 grid(c.tiles_p, c.tiles_c * ngroups(g), pl.bwd_data_splits);
-    int cps = dg.pix_major ? pl.bwd_data_target : ceil_div(c.chunks, pl.bwd_data_splits);
+    const int cps = dg.pix_major ? pl.bwd_data_target : ceil_div(c.chunks, pl.bwd_data_splits);
     TilePerm perm; perm.n = 0;
-    if (dg.pix_major && c.tiles_p <= PERM_MAX) {
-        int w[PERM_MAX];
-        for (int t = 0; t < c.tiles_p; ++t) {
-            const int hw = (int)(((long long)t * 128) / g->B);
-            w[t] = ceil_div(live_taps_in(g, hw < g->H * g->W ? hw : 0) * c.n_ob, cps > 0 ? cps : 1);
-        }
-        perm = balance_tiles(w, c.tiles_p);
-    }
-#define KAN_BD(KIND) KAN_BD2(KIND, 0)
-#define KAN_BD2(KIND, FAST) \
-    hipLaunchKernelGGL((k_conv_bwd_data<KIND, FAST>), grid, dim3(256), 0, st, dz, x, xn, wd, dx, dxn, dg, db, c.CH, c.tiles_c, c.n_ob, c.Opad32, c.chunks, cps, pl.bwd_data_slab_elems, (unsigned)((long long)g->B * g->y_bstride * 4), perm, dpar)
+    if (dg.pix_major) perm = tile_perm(c.tiles_p, [&](int t) {
+        const int hw = (int)(((long long)t * 128) / g->B);
+        return ceil_div(live_taps_in(g, hw < g->H * g->W ? hw : 0) * c.n_ob, cps > 0 ? cps : 1);
+    });
     // compile-time epilogues: single-input specs need x == xn and one output; the FastKAN specs need both tensors
-    const int fv = fast_variant(b);
-    const int fast = (fv == 3 || fv == 8) ? ((x != xn && dxn) ? fv : 0) : ((x == xn && !dxn) ? fv : 0);
+    const int fv = cp.fast;
+    const int fast = (fv == FAST_RBF8 || fv == FAST_RBF5) ? ((x != xn && dxn) ? fv : 0) : ((x == xn && !dxn) ? fv : 0);
     // 4x4 planes in tiles of 8 whole images: row-ordered pixel blocks, dead (row, tap row) blocks skipped (see the kernel)
-    const bool rb = !dg.pix_major && rowblk_bwd_data(g, b);
-#define KAN_BD3(KIND, FAST) \
-    hipLaunchKernelGGL((k_conv_bwd_data<KIND, FAST, 1>), grid, dim3(256), 0, st, dz, x, xn, wd, dx, dxn, dg, db, c.CH, c.tiles_c, c.n_ob, c.Opad32, c.chunks, cps, pl.bwd_data_slab_elems, (unsigned)((long long)g->B * g->y_bstride * 4), perm, dpar)
-    if (fast == 1 && rb) KAN_BD3(KAN_BASIS_BSPLINE, 1);
-    else if (fast == 2 && rb) KAN_BD3(KAN_BASIS_BSPLINE, 2);
-    else if (fast == 1) KAN_BD2(KAN_BASIS_BSPLINE, 1);
-    else if (fast == 2) KAN_BD2(KAN_BASIS_BSPLINE, 2);
-    else if (fast == 3) KAN_BD2(KAN_BASIS_RBF, 3);
-    else if (fast == 8) KAN_BD2(KAN_BASIS_RBF, 8);
-    else if (fast == 4) KAN_BD2(KAN_BASIS_CHEBY, 4);
-    else if (fast == 5) KAN_BD2(KAN_BASIS_CHEBY, 5);
-    else if (fast == 6) KAN_BD2(KAN_BASIS_POLY, 6);
-    else if (fast == 7) KAN_BD2(KAN_BASIS_POLY, 7);
-    else if (fast == 11) KAN_BD2(KAN_BASIS_POLY, 11);
-    else if (b->kind == KAN_BASIS_BSPLINE) KAN_BD(KAN_BASIS_BSPLINE);
-    else if (b->kind == KAN_BASIS_RBF) KAN_BD(KAN_BASIS_RBF);
-    else if (b->kind == KAN_BASIS_POLY) KAN_BD(KAN_BASIS_POLY);
-    else if (b->kind == KAN_BASIS_FOURIER) KAN_BD(KAN_BASIS_FOURIER);
-    else if (b->kind == KAN_BASIS_RELU) KAN_BD(KAN_BASIS_RELU);
-    else if (b->kind == KAN_BASIS_GRAM) KAN_BD(KAN_BASIS_GRAM);
-    else KAN_BD(KAN_BASIS_CHEBY);
-#undef KAN_BD3
-#undef KAN_BD2
-#undef KAN_BD
+    const bool rb = !dg.pix_major && cp.rowblk_bwd_data;
+    const unsigned dz_bytes = (unsigned)((long long)g->B * g->y_bstride * 4);
+    auto launch = [&](auto kind, auto fast, auto rbv) {
+        hipLaunchKernelGGL((k_conv_bwd_data<decltype(kind)::value, decltype(fast)::value, decltype(rbv)::value>), grid, dim3(256), 0, st, dz, x, xn, wd,
+                           dx, dxn, dg, db, c.CH, c.tiles_c, c.n_ob, c.Opad32, c.chunks, cps, pl.bwd_data_slab_elems, dz_bytes, perm, dpar);
+    };
+    const bool launched = dispatch_fast<ON_TAP_MAJOR>(fast, [&](auto fv) {
+        constexpr int F = decltype(fv)::value;
+        if constexpr (fast_has(F, ON_ROWBLK_BWD_DATA)) {
+            if (rb) return launch(IC<fast_kind(F)>{}, fv, IC<1>{});
+        }
+        launch(IC<fast_kind(F)>{}, fv, IC<0>{});
+    });
+    if (!launched) dispatch_kind(b->kind, [&](auto kind) { launch(kind, IC<FAST_GENERIC>{}, IC<0>{}); });
     return launch_ok("conv_bwd_data");
 }
 
 int kan_conv_bwd_weight(const float* dz, const float* x, const float* xn, float* dwp, const KanGeom* g, const KanBasis* b,
                         const float* x_pm, const float* dz_pm, void* stream) {
-    KanPlan pl;
-    if (int rc = make_plan(g, b, &pl)) return rc;
+    ConvPlan cp;
+    if (int rc = plan_conv(g, b, &cp)) return rc;
+    const KanPlan& pl = cp.pub;
     if (!dz || !x || !xn || !dwp) return fail("null tensor pointer");
     if ((b->kind == KAN_BASIS_RELU || b->kind == KAN_BASIS_GRAM) && !b->chan_table) return fail("ReLU / Gram bases need their device parameter table (chan_table)");
-    if (dw_direct(g, b)) {
+    hipStream_t st = (hipStream_t)stream;
+    if (cp.bwd_weight == Route::DW) {
         DevGeom dgd = dev_geom(g); DevBasis dbd = dev_basis(b);
         dim3 grid(pl.bwd_weight_splits, ngroups(g));
-#define KAN_DWW(KIND) hipLaunchKernelGGL((k_dw_bwd_weight<KIND>), grid, dim3(256), 0, (hipStream_t)stream, dz, x, xn, dwp, dgd, dbd, pl.K, pl.Opad, pl.bwd_weight_slab_elems)
-        switch (b->kind) {
-            case KAN_BASIS_BSPLINE: KAN_DWW(KAN_BASIS_BSPLINE); break;
-            case KAN_BASIS_RBF: KAN_DWW(KAN_BASIS_RBF); break;
-            case KAN_BASIS_POLY: KAN_DWW(KAN_BASIS_POLY); break;
-            case KAN_BASIS_FOURIER: KAN_DWW(KAN_BASIS_FOURIER); break;
-            case KAN_BASIS_RELU: KAN_DWW(KAN_BASIS_RELU); break;
-            case KAN_BASIS_GRAM: KAN_DWW(KAN_BASIS_GRAM); break;
-            default: KAN_DWW(KAN_BASIS_CHEBY); break;
-        }
-#undef KAN_DWW
+        dispatch_kind(b->kind, [&](auto kind) {
+            hipLaunchKernelGGL((k_dw_bwd_weight<decltype(kind)::value>), grid, dim3(256), 0, st, dz, x, xn, dwp, dgd, dbd, pl.K, pl.Opad, pl.bwd_weight_slab_elems);
+        });
         return launch_ok("dw_bwd_weight");
     }
-    if (pl.bwd_weight_band) {
-        KanBandCfg band;
-        if (!band_fwd(g, b, &band) || !band.bw_ok) return fail("internal: plan and band configuration disagree");
+    if (cp.bwd_weight == Route::BAND) {
         if (x != xn && b->kind != KAN_BASIS_RBF && b->kind != KAN_BASIS_POLY) return fail("this basis / activation pair runs on single-input kernels: pass xn == x");
-        return kan_band_bwd_weight_launch(dz, x, xn, dwp, g, b, &band, pl.bwd_weight_splits, pl.bwd_weight_slab_elems, stream);
+        return kan_band_bwd_weight_launch(dz, x, xn, dwp, g, b, &cp.band, pl.bwd_weight_splits, pl.bwd_weight_slab_elems, stream);
     }
-    if (halo_bwd_weight(g, b) && x == xn) {
-        const BwHaloCfg hc = bw_halo_cfg(g, pl);
+    const unsigned x_bytes = (unsigned)((long long)g->B * g->x_bstride * 4), dz_bytes = (unsigned)((long long)g->B * g->y_bstride * 4);
+    if (cp.bwd_weight == Route::HALO) {
+        if (x != xn) return fail("internal: the channel-major weight-gradient layout needs x == xn");
+        const BwHaloCfg& hc = cp.bwh;
         const DevGeom dgh = dev_geom(g); const DevBasis dbh = dev_basis(b);
         if ((long long)hc.tiles_o * ngroups(g) > 65535) return fail("groups * output tiles exceed the grid limit");
         dim3 grid(hc.tiles_r, hc.tiles_o * ngroups(g), hc.splits);
-        const int fv = fast_variant(b);
-#define KAN_BWH(F, WV, RV, NV) hipLaunchKernelGGL((k_conv_bwd_weight_halo<F, WV, RV, NV>), grid, dim3(256), 0, (hipStream_t)stream, dz, x, dwp, dgh, dbh, pl.K, \
-        pl.Opad, hc.n_bands, hc.bands_per_split, pl.bwd_weight_slab_elems, (unsigned)((long long)g->B * g->x_bstride * 4), (unsigned)((long long)g->B * g->y_bstride * 4), hc.tiles_o)
-        if (fv == 1 && g->W == 16) KAN_BWH(1, 16, 4, 1);
-        else if (fv == 1 && g->W == 8) KAN_BWH(1, 8, 8, 1);
-        else if (fv == 1) KAN_BWH(1, 4, 4, 2);
-        else if (fv == 9 && g->W == 16) KAN_BWH(9, 16, 4, 1);
-        else if (fv == 9 && g->W == 8) KAN_BWH(9, 8, 8, 1);
-        else if (fv == 9) KAN_BWH(9, 4, 4, 2);
-        else if (fv == 10 && g->W == 16) KAN_BWH(10, 16, 4, 1);
-        else if (fv == 10 && g->W == 8) KAN_BWH(10, 8, 8, 1);
-        else if (fv == 10) KAN_BWH(10, 4, 4, 2);
-        else if (g->W == 16) KAN_BWH(2, 16, 4, 1);
-        else if (g->W == 8) KAN_BWH(2, 8, 8, 1);
-        else KAN_BWH(2, 4, 4, 2);
-#undef KAN_BWH
+        dispatch_fast<ON_HALO_BWD_WEIGHT>(cp.fast, [&](auto fv) {
+            auto launch = [&](auto w, auto r, auto nimg) {          // (plane width, rows per band, images per band)
+                hipLaunchKernelGGL((k_conv_bwd_weight_halo<decltype(fv)::value, decltype(w)::value, decltype(r)::value, decltype(nimg)::value>), grid,
+                                   dim3(256), 0, st, dz, x, dwp, dgh, dbh, pl.K, pl.Opad, hc.n_bands, hc.bands_per_split, pl.bwd_weight_slab_elems,
+                                   x_bytes, dz_bytes, hc.tiles_o);
+            };
+            if (g->W == 16) launch(IC<16>{}, IC<4>{}, IC<1>{});
+            else if (g->W == 8) launch(IC<8>{}, IC<8>{}, IC<1>{});
+            else launch(IC<4>{}, IC<4>{}, IC<2>{});
+        });
         return launch_ok("conv_bwd_weight_halo");
     }
-    if (halo_bwd_weight(g, b)) return fail("internal: the channel-major weight-gradient layout needs x == xn");
-    BwCfg c = bw_cfg(g, b, pl);
+    const BwCfg& c = cp.bw;
     DevGeom dg = dev_geom(g);
-    dg.pix_major = (x_pm && dz_pm && x == xn && pm_bwd_weight(g, b)) ? 1 : 0;
+    dg.pix_major = (x_pm && dz_pm && x == xn && cp.pm_bwd_weight) ? 1 : 0;
     if (dg.pix_major) { x = x_pm; xn = x_pm; dz = dz_pm; }
     DevBasis db = dev_basis(b);
-    hipStream_t st = (hipStream_t)stream;
     if ((long long)c.tiles_o * ngroups(g) > 65535) return fail("groups * output tiles exceed the grid limit");
     dim3 grid(c.tiles_r, c.tiles_o * ngroups(g), pl.bwd_weight_splits);
-    int cps = dg.pix_major ? pl.bwd_weight_target : ceil_div(c.chunks, pl.bwd_weight_splits);
-#define KAN_BW(KIND, WR, WC) KAN_BW2(KIND, 0, WR, WC)
-#define KAN_BW2(KIND, FAST, WR, WC) \
-    hipLaunchKernelGGL((k_conv_bwd_weight<KIND, FAST, WR, WC>), grid, dim3(WR * WC * 64), 0, st, dz, x, xn, dwp, dg, db, pl.K, pl.Opad, c.chunks, cps, pl.bwd_weight_slab_elems, (unsigned)((long long)g->B * g->x_bstride * 4), (unsigned)((long long)g->B * g->y_bstride * 4), c.tiles_o)
-#define KAN_BW_KIND(KIND) do { if (c.TO == 128) KAN_BW(KIND, 2, 2); else KAN_BW(KIND, 4, 1); } while (0)
-    const int fast = fast_variant(b);
-    if (x != xn && fast != 0 && b->kind != KAN_BASIS_RBF && b->kind != KAN_BASIS_POLY)
+    const int cps = dg.pix_major ? pl.bwd_weight_target : ceil_div(c.chunks, pl.bwd_weight_splits);
+    if (x != xn && cp.fast != FAST_GENERIC && b->kind != KAN_BASIS_RBF && b->kind != KAN_BASIS_POLY)
         return fail("this basis / activation pair runs on single-input kernels: pass xn == x");
-#define KAN_BW_FAST(KIND, F) do { if (c.TO == 128) KAN_BW2(KIND, F, 2, 2); else KAN_BW2(KIND, F, 4, 1); } while (0)
-    if (c.TO == 256 && fast == 1) KAN_BW2(KAN_BASIS_BSPLINE, 1, 2, 4);
-    else if (c.TO == 256 && fast == 2) KAN_BW2(KAN_BASIS_BSPLINE, 2, 2, 4);
-    else if (c.TO == 256 && fast == 4) KAN_BW2(KAN_BASIS_CHEBY, 4, 2, 4);
-    else if (c.TO == 256 && fast == 6) KAN_BW2(KAN_BASIS_POLY, 6, 2, 4);
-    else if (c.TO == 256) return fail("internal: no 256-output weight-gradient kernel for this basis");
-    else if (fast == 1) KAN_BW_FAST(KAN_BASIS_BSPLINE, 1);
-    else if (fast == 2) KAN_BW_FAST(KAN_BASIS_BSPLINE, 2);
-    else if (fast == 3) KAN_BW_FAST(KAN_BASIS_RBF, 3);
-    else if (fast == 8) KAN_BW_FAST(KAN_BASIS_RBF, 8);
-    else if (fast == 4) KAN_BW_FAST(KAN_BASIS_CHEBY, 4);
-    else if (fast == 5) KAN_BW_FAST(KAN_BASIS_CHEBY, 5);
-    else if (fast == 6) KAN_BW_FAST(KAN_BASIS_POLY, 6);
-    else if (fast == 7) KAN_BW_FAST(KAN_BASIS_POLY, 7);
-    else if (fast == 11) KAN_BW_FAST(KAN_BASIS_POLY, 11);
-    else if (b->kind == KAN_BASIS_BSPLINE) KAN_BW_KIND(KAN_BASIS_BSPLINE);
-    else if (b->kind == KAN_BASIS_RBF) KAN_BW_KIND(KAN_BASIS_RBF);
-    else if (b->kind == KAN_BASIS_POLY) KAN_BW_KIND(KAN_BASIS_POLY);
-    else if (b->kind == KAN_BASIS_FOURIER) KAN_BW_KIND(KAN_BASIS_FOURIER);
-    else if (b->kind == KAN_BASIS_RELU) KAN_BW_KIND(KAN_BASIS_RELU);
-    else if (b->kind == KAN_BASIS_GRAM) KAN_BW_KIND(KAN_BASIS_GRAM);
-    else KAN_BW_KIND(KAN_BASIS_CHEBY);
-#undef KAN_BW_FAST
-#undef KAN_BW_KIND
-#undef KAN_BW2
-#undef KAN_BW
+    auto launch = [&](auto kind, auto fast, auto wr, auto wc) {
+        constexpr int WR = decltype(wr)::value, WC = decltype(wc)::value;
+        hipLaunchKernelGGL((k_conv_bwd_weight<decltype(kind)::value, decltype(fast)::value, WR, WC>), grid, dim3(WR * WC * 64), 0, st, dz, x, xn, dwp,
+                           dg, db, pl.K, pl.Opad, c.chunks, cps, pl.bwd_weight_slab_elems, x_bytes, dz_bytes, c.tiles_o);
+    };
+    auto tiles = [&](auto kind, auto fast) {                        // 128 outputs: 2 x 2 waves; 64 outputs: 4 x 1
+        if (c.TO == 128) launch(kind, fast, IC<2>{}, IC<2>{});
+        else launch(kind, fast, IC<4>{}, IC<1>{});
+    };
+    const bool fast = dispatch_fast<ON_TAP_MAJOR>(cp.fast, [&](auto fv) {
+        constexpr int F = decltype(fv)::value;
+        if constexpr (fast_has(F, ON_BIG_TILES)) {
+            if (c.TO == 256) return launch(IC<fast_kind(F)>{}, fv, IC<2>{}, IC<4>{});
+        }
+        tiles(IC<fast_kind(F)>{}, fv);
+    });
+    if (!fast) dispatch_kind(b->kind, [&](auto kind) { tiles(kind, IC<FAST_GENERIC>{}); });
     return launch_ok("conv_bwd_weight");
 }
 
 int kan_position_major_expanded(const float* x, float* e_pm, const KanGeom* g, const KanBasis* b, void* stream) {
-    KanPlan pl;
-    if (int rc = make_plan(g, b, &pl)) return rc;
+    ConvPlan cp;
+    if (int rc = plan_conv(g, b, &cp)) return rc;
+    const KanPlan& pl = cp.pub;
     if (!x || !e_pm) return fail("null tensor pointer");
     if (!pl.e_pm_wanted) return fail("this geometry / basis does not use the expanded position-major copy (plan.e_pm_wanted)");
     const int G = ngroups(g), CHW = G * g->C * g->H * g->W;
@@ -3577,50 +3085,42 @@ int kan_position_major_expanded(const float* x, float* e_pm, const KanGeom* g, c
     dim3 grid(ceil_div(CHW, 32), ceil_div(g->B, 32));
     float* dump = e_pm + (pl.e_pm_elems - 256);
     if ((b->kind == KAN_BASIS_RELU || b->kind == KAN_BASIS_GRAM) && !b->chan_table) return fail("ReLU / Gram bases need their device parameter table (chan_table)");
-#define KAN_EXP(KIND, F) hipLaunchKernelGGL((k_expand_pm<KIND, F>), grid, dim3(256), 0, (hipStream_t)stream, x, e_pm, db, g->B, CHW, g->H * g->W, g->C, g->x_bstride, dump)
-    switch (fast_variant(b)) {
-        case 1: KAN_EXP(KAN_BASIS_BSPLINE, 1); break;
-        case 2: KAN_EXP(KAN_BASIS_BSPLINE, 2); break;
-        case 9: KAN_EXP(KAN_BASIS_RELU, 9); break;           // (basis->order selects value / phase-derivative planes)
-        case 10: KAN_EXP(KAN_BASIS_GRAM, 10); break;
-        default: return fail("internal: no expansion kernel for this basis");
-    }
-#undef KAN_EXP
+    dispatch_fast<ON_EXPANDED>(cp.fast, [&](auto fv) {             // (ReLU-KAN: basis->order selects value / phase-derivative planes)
+        constexpr int F = decltype(fv)::value;
+        hipLaunchKernelGGL((k_expand_pm<fast_kind(F), F>), grid, dim3(256), 0, (hipStream_t)stream, x, e_pm, db, g->B, CHW, g->H * g->W, g->C, g->x_bstride, dump);
+    });
     return launch_ok("position_major_expanded");
 }
 
 int kan_conv_fwd_expanded(const float* e_pm, const float* wp, float* z, const KanGeom* g, const KanBasis* b, void* stream) {
-    KanPlan pl;
-    if (int rc = make_plan(g, b, &pl)) return rc;
+    ConvPlan cp;
+    if (int rc = plan_conv(g, b, &cp)) return rc;
+    const KanPlan& pl = cp.pub;
     if (!e_pm || !wp || !z) return fail("null tensor pointer");
-    if (!pl.fwd_expanded) return fail("the forward of this geometry / basis does not read the expanded position-major copy (plan.fwd_expanded)");
-    const FwdCfg c = fwd_cfg(g, b, pl);
-    if (c.TO != 128 || c.TP != 128 || pl.KC != 18 || pl.IPC != 2) return fail("internal: the expanded forward kernel is built for 128 x 128 tiles and 18-row steps");
+    if (cp.fwd != Route::EXPANDED) return fail("the forward of this geometry / basis does not read the expanded position-major copy (plan.fwd_expanded)");
+    const FwdCfg& c = cp.fc;                                // (128 x 128 tiles, 18-row steps of channel pairs: the planner's pmdma shape)
     DevGeom dg = dev_geom(g);
     dg.pix_major = 1;
     TilePerm perm; perm.n = 0;
-    const int xcd = tuning_on("KAN_PMDMA_XCD") ? 1 : 0;
-    if (c.tiles_p <= PERM_MAX && !xcd) {                     // weight of a pixel tile = its live work (as kan_conv_fwd)
-        int wts[PERM_MAX];
+    if (!cp.pmdma_xcd) {                                    // weight of a pixel tile = its live work (as kan_conv_fwd)
         const int tpp = ceil_div(g->B, c.TP), cpt = ceil_div(g->C, pl.IPC);
-        for (int t = 0; t < c.tiles_p; ++t) wts[t] = live_taps_out(g, t / tpp) * cpt;
-        perm = balance_tiles(wts, c.tiles_p);
+        perm = tile_perm(c.tiles_p, [&](int t) { return live_taps_out(g, t / tpp) * cpt; });
     }
     if ((long long)c.tiles_o * ngroups(g) > 65535) return fail("groups * output tiles exceed the grid limit");
     dim3 grid(c.tiles_p, c.tiles_o * ngroups(g), pl.fwd_splits);
     hipLaunchKernelGGL((k_conv_fwd_pmdma<18>), grid, dim3(256), 0, (hipStream_t)stream, e_pm, wp, z, dg, pl.P, make_fastdiv(pl.P), pl.Opad, c.chunks,
                        pl.fwd_target, pl.fwd_slab_elems, (unsigned)(((long long)pl.e_pm_elems - 256) * 4),
-                       (unsigned)((long long)pl.Kpad * pl.Opad * 4), perm, c.tiles_o, xcd);
+                       (unsigned)((long long)pl.Kpad * pl.Opad * 4), perm, c.tiles_o, cp.pmdma_xcd ? 1 : 0);
     return launch_ok("conv_fwd_expanded");
 }
 
 int kan_conv_bwd_weight_expanded(const float* dz_pm, const float* e_pm, float* dwp, const KanGeom* g, const KanBasis* b, void* stream) {
-    KanPlan pl;
-    if (int rc = make_plan(g, b, &pl)) return rc;
+    ConvPlan cp;
+    if (int rc = plan_conv(g, b, &cp)) return rc;
+    const KanPlan& pl = cp.pub;
     if (!dz_pm || !e_pm || !dwp) return fail("null tensor pointer");
-    if (!pl.bwd_weight_expanded) return fail("the weight gradient of this geometry / basis does not read the expanded position-major copy (plan.bwd_weight_expanded)");
-    const BwCfg c = bw_cfg(g, b, pl);
-    if (c.TR != 128 || c.TO != 128) return fail("internal: the expanded weight-gradient kernel is built for 128 x 128 tiles");
+    if (cp.bwd_weight != Route::EXPANDED) return fail("the weight gradient of this geometry / basis does not read the expanded position-major copy (plan.bwd_weight_expanded)");
+    const BwCfg& c = cp.bw;                                 // (128 x 128 tiles: the planner's pmdma shape)
     DevGeom dg = dev_geom(g);
     dg.pix_major = 1;
     if ((long long)c.tiles_o * ngroups(g) > 65535) return fail("groups * output tiles exceed the grid limit");
@@ -3629,7 +3129,7 @@ int kan_conv_bwd_weight_expanded(const float* dz_pm, const float* e_pm, float* d
     // min(splits, ceil(live / target)) ranges exactly as the kernel cuts them
     PmOrder ord; ord.n = 0; ord.xcd = 0;
     const int T = g->kh * g->kw, S = pl.bwd_weight_splits, trpt = (g->C * pl.P) / 128;
-    if (!tuning_off("KAN_PM_LPT") && T * S <= PM_ORDER_MAX && T <= 255 && S <= 255 && trpt * T == c.tiles_r) {
+    if (cp.pm_lpt && T * S <= PM_ORDER_MAX && T <= 255 && S <= 255 && trpt * T == c.tiles_r) {
         int steps[PM_ORDER_MAX], idx[PM_ORDER_MAX], n = 0;
         unsigned char tp[PM_ORDER_MAX], zz[PM_ORDER_MAX];
         const int per_pos = ceil_div(g->B, 16), tgt = pl.bwd_weight_target > 0 ? pl.bwd_weight_target : 1;
@@ -3647,7 +3147,7 @@ int kan_conv_bwd_weight_expanded(const float* dz_pm, const float* e_pm, float* d
             idx[j] = v;
         }
         const int per_entry = trpt * c.tiles_o * ngroups(g);
-        ord.n = n; ord.tiles_r_per_tap = trpt; ord.xcd = tuning_off("KAN_PM_XCD") ? 0 : 1;
+        ord.n = n; ord.tiles_r_per_tap = trpt; ord.xcd = cp.pm_xcd ? 1 : 0;
         for (int i = 0; i < n; ++i) { ord.tap[i] = tp[idx[i]]; ord.z[i] = zz[idx[i]]; ord.first[i] = i * per_entry; }
         ord.first[n] = n * per_entry;
         grid = dim3((unsigned)(n * per_entry), 1, 1);

@@ -13,7 +13,8 @@
  *     frees or synchronises the device; all work is enqueued on `stream`
  *     (a hipStream_t passed as void*);
  *   - return value: 0 on success, <0 on error; message via kan_last_error() (thread-local);
- *   - no C++ exception crosses the boundary; no mutable global state.
+ *   - no C++ exception crosses the boundary; no mutable global state, except one: a mutex-guarded
+ *     record of the (kernel, device) pairs whose dynamic-LDS limit the library has raised (once each).
  *
  * Tensor layouts: activations NCHW.  KanGeom describes ONE group of the reference layer
  * (kan_layers.py:249-258 loops over groups in Python); `groups` = G > 1 runs G such groups in
