@@ -1,7 +1,8 @@
 """Seeded random geometries through the HIP path vs the CPU oracle (forward, input gradient, every parameter gradient).
 
-Shapes are drawn so that every kernel family gets hit: 64/128/256-output tiles, halo and tap-major forward, position-major
-small planes, grouped and depthwise launches, strides / dilations / paddings / rectangular kernels, 1..300 images."""
+Shapes are drawn over 64/128/256-output tiles, grouped and depthwise launches, strides / dilations / paddings / rectangular kernels
+and 1..300 images.  The draws do not reach every kernel route: the geometry fuzz never takes a halo or expanded launch, and a
+position-major one only for a few generic kinds; tests/test_gpu_route_matrix.py checks one layer per (spec, route) cell the planner can pick."""
 import random
 
 import pytest
