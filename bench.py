@@ -9,6 +9,11 @@ A "step" = zero grads, forward, CrossEntropy loss, backward (+ bucketed RCCL all
 no optimizer step.  Rank 0 prints ONE JSON line; `ms_per_step` in it is the time of one of the K timed steps.
 `--dump-outputs DIR` also writes what the last timed step computed as DIR/<name>.npy (inputs and weights are seeded, so two builds
 run with the same arguments can be compared array by array).
+
+A plain run does only what the headline needs: set-up, W warm-up and K timed steps, the dump if asked for, and the line (its `roofline`
+comes from the HIP events of the timed steps themselves).  `--full` then also runs, after the timed steps, what else the benchmark
+measures: for N = 1 the step with the optimizer, the other workloads, the opt-in precisions and the CPU baseline; for N > 1 one traced
+step of the gradient all-reduce.
 """
 import argparse
 import json
@@ -522,8 +527,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=0, help="images per GPU (default: the workload's)")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="kan_vgg11")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-aux", action="store_true", help="skip the auxiliary legs (with-optimizer timing, other workloads): clean kernel profiles")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run the auxiliary legs (with-optimizer timing, other workloads "
+                                                        "and precisions) and the CPU baseline for N = 1, the traced all-reduce step for N > 1")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-aux", action="store_true", help="with --full: skip the auxiliary legs (with-optimizer timing, other workloads)")
     ap.add_argument("--cpu-batch", type=int, default=256)
     ap.add_argument("--cpu-iters", type=int, default=10)
     ap.add_argument("--cpu-warmup", type=int, default=3)
@@ -603,15 +610,16 @@ def main():
         dist.all_gather(every, tt)                       # each rank's own clock over the same K steps (spread = load imbalance / stragglers)
         per_rank = [float(v.item()) for v in every]
         elapsed = max(per_rank)                          # the contract's MAX over ranks
-        # one more, UNTIMED step with HIP events around every bucket's collective: where the all-reduce sits relative to backward
-        trace = traced_step(model, x, t, reducer)
-        barrier()
+        if args.full:
+            # one more, UNTIMED step with HIP events around every bucket's collective: where the all-reduce sits relative to backward
+            trace = traced_step(model, x, t, reducer)
+            barrier()
 
     if rank == 0:
         ips, roof = summarise(prof, elapsed, args.steps, args.batch, world, wl["gflop_per_image"])
         out = {
             "metric": wl["metric"],
-            "value": round(ips, 1), "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "value": round(ips, 1), "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic (randn images, randint labels; seeded random-init weights)",
             "config": {"workload": wl["desc"], "per_gpu_batch": args.batch,
@@ -634,7 +642,7 @@ def main():
             out["allreduce"].update({("bucket_trace" if k == "buckets" else k): v for k, v in trace.items()})
             out["ms_per_step_ranks"] = {"min": round(min(per_rank) / args.steps * 1e3, 3), "max": round(max(per_rank) / args.steps * 1e3, 3),
                                         "all": [round(v / args.steps * 1e3, 3) for v in per_rank]}
-        aux = world == 1 and not use_dist and args.workload == "kan_vgg11" and not args.no_aux
+        aux = args.full and world == 1 and not use_dist and args.workload == "kan_vgg11" and not args.no_aux
         if aux:
             out["with_optimizer"] = train_step_timing(model, x, t, args.steps, max(3, args.warmup // 2))
             del model, x, t
@@ -643,7 +651,7 @@ def main():
                                       "cheby_alexnet": other_workload("cheby_alexnet", device, 10, 3),
                                       "split_precision_forward": split_precision_forward(device),
                                       "kan_vgg11_inference": inference_modes(device)}
-        if world == 1 and not args.no_cpu_baseline and args.workload == "kan_vgg11":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload == "kan_vgg11":
             out["cpu_baseline"] = cpu_baseline(args.cpu_batch, args.cpu_iters, args.cpu_warmup)
             out["cpu_baseline"]["gpu_over_cpu"] = round(ips / out["cpu_baseline"]["value"], 1)
         sys.stdout.flush()

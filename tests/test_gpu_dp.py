@@ -144,9 +144,10 @@ def test_shared_layer_does_not_alias_its_sink(gpu_lib):
 
 @pytest.mark.timeout(600)
 def test_bench_launches_its_own_ranks(gpu_lib):
-    """`bench.py --spawn --force-dp`: parent without GPU state -> torch.distributed.run child -> one rank on RCCL; one JSON line."""
+    """`bench.py --spawn --force-dp --full`: parent without GPU state -> torch.distributed.run child -> one rank on RCCL; one JSON line
+    with the traced all-reduce step that --full adds."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--spawn", "--force-dp", "--steps", "3", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--spawn", "--force-dp", "--full", "--steps", "3", "--warmup", "2",
                         "--no-cpu-baseline", "--no-aux"], capture_output=True, text=True, timeout=560, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
