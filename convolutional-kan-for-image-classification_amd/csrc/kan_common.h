@@ -7,6 +7,7 @@
 #include <type_traits>
 #include "kanconv.h"
 #include "kan_device.h"
+#include "kan_internal.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define MFMA32(a, b, c) __builtin_amdgcn_mfma_f32_32x32x2f32((a), (b), (c), 0, 0, 0)
@@ -164,47 +165,49 @@ __device__ __forceinline__ int mfma_row(int reg, int lane) { return (reg & 3) + 
 // FAST != 0 fixes one of the configurations BASELINE.json names at compile time: straight-line code, no runtime loop
 // bounds, fewer live scalars.  That matters twice on gfx950: VALU instructions steal fp32-MFMA issue time, and SGPR
 // spills are VALU (v_readlane).
-//   1 / 2 : B-spline grid 5, order 3 (8 bases) + base branch SiLU / GELU          P = 9   (KANConv2DLayer defaults)
-//   3     : RBF, 8 centres + base branch SiLU                                     P = 9   (FastKANConv2DLayer defaults)
-//   4 / 5 : Chebyshev degree 4 / 3, no base branch                                P = 5 / 4
-//   9     : ReLU-KAN g = 5, k = 3 (8 planes) + base branch SiLU, phases in device memory  P = 9   (halo kernels only)
-//   10    : GRAM-KAN degree 3 (4 planes) + base branch, SiLU, coefficients in device memory  P = 5   (halo kernels only)
-//   11    : a base branch + ONE constant polynomial plane (degree-0 recurrence)  P = 2   -- with zero weights on the constant plane this is a plain
-//           convolution of act(x): Wav-KAN's base conv and 1x1 `wavelet_out` conv (layers/wav_layers.py), Bessel/Taylor/... at degree 0
-__host__ __device__ constexpr int fast_planes(int fast) { return (fast == 4 || fast == 6 || fast == 10) ? 5 : (fast == 5 || fast == 7) ? 4 : fast == 8 ? 6 : fast == 11 ? 2 : 9; }
+// The specs are the FAST_* rows of fast_spec (kan_internal.h): kind, plane count P and base plane come from there, the arithmetic of each
+// kind is below, and stage_unit_grad after it holds the derivative of the same planes.  FAST_RELU8 / FAST_GRAM4 read per-channel / layer
+// parameters from device memory (halo and expanded kernels only); FAST_POLY1 is a base branch + ONE constant polynomial plane -- with zero
+// weights on that plane a plain convolution of act(x): Wav-KAN's base conv and 1x1 `wavelet_out` conv, Bessel/Taylor/... at degree 0.
 __device__ __forceinline__ float silu_fast(float x) { return x * kan_rcp(1.0f + kan_exp2k(x, -1.44269504088896340736f)); }
+__device__ __forceinline__ float silu_grad_fast(float x) {
+    const float sg = kan_rcp(1.0f + kan_exp2k(x, -1.44269504088896340736f));
+    return sg * (1.0f + x * (1.0f - sg));
+}
 
 template <int KIND, int FAST>
 __device__ __forceinline__ void stage_unit(const DevBasis& bs, const float* sTab, bool inb, float xa, float xb,
                                            float* col, int ld, float* dump, int c = 0) {
-    if (KIND == KAN_BASIS_RBF && (FAST == 3 || FAST == 8)) {          // 8 (FastKAN default) or 5 (grid_size 5, as kan_vgg.py builds it) centres
+    constexpr FastSpec S = fast_spec(FAST);
+    static_assert(FAST == FAST_GENERIC || KIND == S.kind, "a compile-time spec runs under its own basis kind");
+    if (FAST != 0 && KIND == KAN_BASIS_RBF) {                         // 8 (FastKAN default) or 5 (grid_size 5, as kan_vgg.py builds it) centres
         // utils/utils.py:33 with hardware exp2: exp(-u^2) = exp2(-u^2 log2 e), u = (x - c_g) / d
         col[0] = inb ? silu_fast(xa) : 0.f;
         const float inv_d = 1.0f / bs.p0;
 #pragma unroll
-        for (int j = 0; j < fast_planes(FAST) - 1; ++j) {
+        for (int j = 0; j < S.planes - S.base; ++j) {
             const float u = (xb - bs.tab[j]) * inv_d;
             col[(1 + j) * ld] = inb ? kan_exp2k(u * u, -1.44269504088896340736f) : 0.f;
         }
         return;
     }
-    if (KIND == KAN_BASIS_CHEBY && (FAST == 4 || FAST == 5)) {
+    if (FAST != 0 && KIND == KAN_BASIS_CHEBY) {
         // cheby_kan_layers.py:93-96 by recurrence; tanh through hardware exp2/rcp: (e-1)/(e+1), e = exp(2x), |err| ~1e-7 absolute
         const float t = fminf(fmaxf(kan_tanh_fast(xb), bs.p0), bs.p1);
         float Tm = 1.f, Tc = t;
         col[0] = inb ? 1.f : 0.f;
 #pragma unroll
-        for (int k = 1; k < fast_planes(FAST); ++k) {
+        for (int k = 1; k < S.planes; ++k) {
             col[k * ld] = inb ? Tc : 0.f;
             const float Tn = 2.f * t * Tc - Tm; Tm = Tc; Tc = Tn;
         }
         return;
     }
-    if (KIND == KAN_BASIS_POLY && (FAST == 6 || FAST == 7)) {
-        // Recurrence families with a base branch and 4 (FAST 6) or 3 (FAST 7) polynomial planes -- degree 3, the
-        // reference's default -- so P is a compile-time 5 / 4.  Activation and squash stay runtime (uniform branches),
-        // coefficients come from the kernel argument (scalar registers).  tanh through hardware exp2/rcp as above.
-        constexpr int NB = FAST == 6 ? 4 : 3;
+    if (FAST != 0 && KIND == KAN_BASIS_POLY && S.planes > 2) {
+        // Recurrence families with a base branch and a compile-time count of polynomial planes (4: degree 3, the reference's
+        // default, or 3).  Activation and squash stay runtime (uniform branches), coefficients come from the kernel
+        // argument (scalar registers).  tanh through hardware exp2/rcp as above.
+        constexpr int NB = S.planes - S.base;
         const float base = bs.act == KAN_ACT_SILU ? silu_fast(xa) : kan_act(bs.act, xa);
         float t = xb;
         if (bs.order) {
@@ -220,12 +223,12 @@ __device__ __forceinline__ void stage_unit(const DevBasis& bs, const float* sTab
         }
         return;
     }
-    if (KIND == KAN_BASIS_POLY && FAST == 11) {
+    if (FAST != 0 && KIND == KAN_BASIS_POLY) {                       // the constant plane alone (FAST_POLY1): no recurrence, no squash
         col[0] = inb ? (bs.act == KAN_ACT_SILU ? silu_fast(xa) : kan_act(bs.act, xa)) : 0.f;
         col[ld] = inb ? bs.tab[0] : 0.f;
         return;
     }
-    if (KIND == KAN_BASIS_RELU && FAST == 9) {
+    if (FAST != 0 && KIND == KAN_BASIS_RELU) {
         // ReLU-KAN defaults (relu_kan_layers.py:118-136: g = 5, k = 3 => 8 planes, SiLU base branch, P = 9): the per-channel phases come
         // from device memory (16 loads; the lanes of a wave mostly share the channel).  bs.order selects value / d phase_low / d phase_high
         // as in kan_planes<KAN_BASIS_RELU> (uniform branch).  Used by the halo kernels, where expansions are rare.
@@ -242,7 +245,7 @@ __device__ __forceinline__ void stage_unit(const DevBasis& bs, const float* sTab
         }
         return;
     }
-    if (KIND == KAN_BASIS_GRAM && FAST == 10) {
+    if (FAST != 0 && KIND == KAN_BASIS_GRAM) {
         // GRAM-KAN degree 3 with SiLU (gram_kan_layers.py:150-182): planes act(P_k(tanh x)), P_0 = 1, P_1 = t, P_k = t P_{k-1} - c_k P_{k-2},
         // c_k from device memory (layer-global); bs.order = m >= 1 selects the derivative w.r.t. c_{m+1} (act'(P_k) dP_k/dc), base plane
         // zero, as kan_planes<KAN_BASIS_GRAM>.  tanh and SiLU through hardware exp2 / rcp.  P = 5.  Halo kernels only.
@@ -268,7 +271,7 @@ __device__ __forceinline__ void stage_unit(const DevBasis& bs, const float* sTab
     if (KIND == KAN_BASIS_BSPLINE && FAST != 0) {
         float base = 0.f, N0 = 0.f, N1 = 0.f, N2 = 0.f, N3 = 0.f; int j0 = -8;
         const bool live = inb && xa >= bs.g0 && xa < bs.gN;             // NaN fails both, as the reference's indicator
-        if (inb) base = FAST == 1 ? silu_fast(xa) : kan_act(KAN_ACT_GELU, xa);
+        if (inb) base = FAST == FAST_BSPLINE_SILU ? silu_fast(xa) : kan_act(KAN_ACT_GELU, xa);
         if (live) {
             const int i = min((int)((xa - bs.g0) * bs.inv_h), 10);       // 11 knot intervals
 #ifdef KAN_EXACT_TRANSCENDENTALS
@@ -320,7 +323,79 @@ __device__ __forceinline__ void stage_unit(const DevBasis& bs, const float* sTab
     }
 }
 
-constexpr int KCM = 36;                        // (legacy constant kept for plan arithmetic)
+// The derivative twin of stage_unit for the compile-time specs of the bwd-data kernel: the input gradient of one (pixel, channel) unit,
+// sum_p plane_p'(x) G_p, from its G column in LDS (plane p at G[p * ld]).  The two-tensor specs (RBF: base branch on x, basis on xn)
+// return the two parts apart, dx for x and dxn for xn; the others read xa alone and leave dxn zero.
+struct InGrad { float dx, dxn; };
+template <int KIND, int FAST>
+__device__ __forceinline__ InGrad stage_unit_grad(const DevBasis& bs, const float* sTab, float xa, float xb, const float* G, int ld) {
+    constexpr FastSpec S = fast_spec(FAST);
+    constexpr int P = S.planes;
+    static_assert(FAST != 0 && KIND == S.kind, "a compile-time spec runs under its own basis kind");
+    if constexpr (KIND == KAN_BASIS_RBF) {
+        // d/dxn exp(-u_j^2) = (-2 u_j / d) exp(-u_j^2) (utils/utils.py:33), hardware exp2
+        const float inv_d = 1.0f / bs.p0;
+        float sb = 0.f;
+#pragma unroll
+        for (int j = 0; j < P - S.base; ++j) {
+            const float u = (xb - bs.tab[j]) * inv_d;
+            sb += u * kan_exp2k(u * u, -1.44269504088896340736f) * G[(1 + j) * ld];
+        }
+        return {silu_grad_fast(xa) * G[0], sb * (-2.0f * inv_d)};
+    } else if constexpr (KIND == KAN_BASIS_CHEBY) {
+        // dT_k/dx = k U_{k-1}(t) (1 - tanh^2 x) inside the clamp, 0 where it is active (kan_device.h), tanh as in stage_unit
+        const float t0 = kan_tanh_fast(xa);
+        const float t = fminf(fmaxf(t0, bs.p0), bs.p1);
+        const float chain = (t0 >= bs.p0 && t0 <= bs.p1) ? (1.0f - t0 * t0) : 0.f;
+        float Um = 0.f, Uc = 1.f, sb = 0.f;
+#pragma unroll
+        for (int k = 1; k < P; ++k) {
+            sb += (float)k * Uc * G[k * ld];
+            const float Un = 2.f * t * Uc - Um; Um = Uc; Uc = Un;
+        }
+        return {sb * chain, 0.f};
+    } else if constexpr (KIND == KAN_BASIS_POLY) {
+        // the differentiated recurrence (one constant plane: no polynomial derivative at all)
+        constexpr int NB = P - S.base;
+        const float dact = bs.act == KAN_ACT_SILU ? silu_grad_fast(xa) : kan_act_grad(bs.act, xa);
+        float t = xa, chain = 1.0f;
+        if (bs.order) {
+            t = kan_tanh_fast(xa);
+            chain = 1.0f - t * t;
+        }
+        float Tm = bs.tab[0], Tc = bs.tab[1] * t + bs.tab[2], Dm = 0.f, Dc = bs.tab[1];
+        float sb = 0.f;                                        // sum_k T_k'(t) G_k   (T_0' = 0)
+#pragma unroll
+        for (int k = 1; k < NB; ++k) {
+            sb += Dc * G[(1 + k) * ld];
+            if (k + 1 < NB) {
+                const float A = bs.tab[3 * k], B = bs.tab[3 * k + 1], Cc = bs.tab[3 * k + 2], sc = A * t + B;
+                const float Tn = sc * Tc + Cc * Tm, Dn = A * Tc + sc * Dc + Cc * Dm;
+                Tm = Tc; Tc = Tn; Dm = Dc; Dc = Dn;
+            }
+        }
+        return {dact * G[0] + sb * chain, 0.f};
+    } else {
+        // B-spline: the cubic's derivative from the closed form (kan_device.h, bspline_uniform<true>, S = 3); only the <= 4 live planes of G are read
+        const float hh = 0.5f * bs.inv_h;
+        float sum = (FAST == FAST_BSPLINE_SILU ? silu_grad_fast(xa) : kan_act_grad(KAN_ACT_GELU, xa)) * G[0];
+        if (xa >= bs.g0 && xa < bs.gN) {                       // NaN fails both, as the reference's indicator
+            const int i = min((int)((xa - bs.g0) * bs.inv_h), 10);
+#ifdef KAN_EXACT_TRANSCENDENTALS
+            const double ihd = 1.0 / ((double)sTab[i + 1] - (double)sTab[i]), hd = 0.5 * ihd;
+            const double ud = fmin(fmax(((double)xa - (double)sTab[i]) * ihd, 0.0), 1.0), vd = 1.0 - ud, ud2 = ud * ud;
+            const float n0 = (float)(-hd * vd * vd), n1 = (float)(hd * (3.0 * ud2 - 4.0 * ud)), n2 = (float)(hd * (-3.0 * ud2 + 2.0 * ud + 1.0)), n3 = (float)(hd * ud2);
+#else
+            const float u = fminf(fmaxf((xa - sTab[i]) * bs.inv_h, 0.f), 1.f), v = 1.f - u, u2 = u * u;
+            const float n0 = -hh * v * v, n1 = hh * (3.f * u2 - 4.f * u), n2 = hh * (-3.f * u2 + 2.f * u + 1.f), n3 = hh * u2;
+#endif
+            const int j0 = i - 3;                              // bases j0 .. j0+3, kept where 0 <= j < 8
+            sum += ((unsigned)j0 < 8u ? n0 * G[(1 + j0) * ld] : 0.f) + ((unsigned)(j0 + 1) < 8u ? n1 * G[(2 + j0) * ld] : 0.f)
+                 + ((unsigned)(j0 + 2) < 8u ? n2 * G[(3 + j0) * ld] : 0.f) + ((unsigned)(j0 + 3) < 8u ? n3 * G[(4 + j0) * ld] : 0.f);
+        }
+        return {sum, 0.f};
+    }
+}
 
 // Occupancy is the lever on this chip for an exact-fp32 MFMA GEMM (measured: 2 -> 4 workgroups per CU took the
 // bwd-data kernel from 79 to 120 TFLOP/s): every kernel below is sized for FOUR 256-thread workgroups per CU,

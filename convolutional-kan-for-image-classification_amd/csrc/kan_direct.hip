@@ -118,7 +118,7 @@ __global__ __launch_bounds__(WO * WP * 64, 2) void k_band_fwd(
         u_ok |= ((ch < NG) ? 1u : 0u) << k;                  // the unit exists: its planes are written on every expansion (zeros where there is no input)
         u_img |= ((img < g.B) ? 1u : 0u) << k;
     }
-    const bool same_in = (KIND != KAN_BASIS_RBF && KIND != KAN_BASIS_POLY) || (x == xn);
+    const bool same_in = !fast_spec(FAST).xn_fwd || (x == xn);
     const kan_rsrc x_rs = make_rsrc(x, x_bytes), xn_rs = make_rsrc(same_in ? x : xn, x_bytes);
     float xa[SLOTS], xb[SLOTS]; unsigned inb_mask = 0; int s_cbase = 0;
     auto load_group = [&](int gi) {                          // request the inputs of (phase, group) gi
@@ -353,7 +353,7 @@ __global__ __launch_bounds__(WR * 64, (NI == 6 && WR == 4) ? 3 : 2) void k_band_
         zoff[j] = (m < NZ && o_tile0 + ol < g.O) ? (unsigned)((o_tile0 + ol) * HoWo + q) * 4u : KAN_OOB;
         zq[j] = q;
     }
-    const bool same_in = (KIND != KAN_BASIS_RBF && KIND != KAN_BASIS_POLY) || (x == xn);
+    const bool same_in = !fast_spec(FAST).xn_fwd || (x == xn);
     const kan_rsrc x_rs = make_rsrc(x, x_bytes), xn_rs = make_rsrc(same_in ? x : xn, x_bytes), dz_rs = make_rsrc(dz, dz_bytes);
 
     // expansion units (fixed): unit = channel-of-group * cells + cell -> (virtual row v, halo column jj)

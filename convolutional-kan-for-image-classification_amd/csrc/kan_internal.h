@@ -15,24 +15,24 @@ int kan_fail_msg(const char* fmt, const char* a);
 int kan_raise_lds_limit(const void* kernel, int bytes);
 
 // ---------------------------------------------------------------------------------------------------------------- compile-time basis specs
-// A fast variant is a basis (kind, planes, activation) with compile-time kernels (template parameter FAST; 0 = the generic kernels).
-// The values are part of the kernel names: never renumber.
+// A fast variant is a basis (kind, planes, activation) with compile-time kernels (template parameter FAST; 0 = the generic kernels);
+// its facts are its row of fast_spec below.  The values are part of the kernel names: never renumber.
 enum : int {
     FAST_GENERIC = 0,
-    FAST_BSPLINE_SILU = 1,    // B-spline grid 5 order 3, SiLU base (P = 9)
+    FAST_BSPLINE_SILU = 1,    // B-spline grid 5 order 3, SiLU base
     FAST_BSPLINE_GELU = 2,    // B-spline grid 5 order 3, GELU base
-    FAST_RBF8 = 3,            // FastKAN, 8 centres, SiLU base (P = 9)
-    FAST_CHEBY5 = 4,          // ChebyKAN degree 4 (P = 5)
-    FAST_CHEBY4 = 5,          // ChebyKAN degree 3 (P = 4)
-    FAST_POLY4 = 6,           // recurrence families degree 3, with base (P = 5)
-    FAST_POLY3 = 7,           // recurrence families degree 2, with base (P = 4)
-    FAST_RBF5 = 8,            // FastKAN, 5 centres (kan_vgg.py's grid_size 5), SiLU base (P = 6)
-    FAST_RELU8 = 9,           // ReLU-KAN g + k = 8, SiLU base (P = 9; halo and expanded kernels only)
-    FAST_GRAM4 = 10,          // GRAM-KAN degree 3, SiLU base (P = 5; halo and expanded kernels only)
-    FAST_POLY1 = 11,          // recurrence families degree 0, with base (P = 2)
+    FAST_RBF8 = 3,            // FastKAN, 8 centres, SiLU base
+    FAST_CHEBY5 = 4,          // ChebyKAN degree 4
+    FAST_CHEBY4 = 5,          // ChebyKAN degree 3
+    FAST_POLY4 = 6,           // recurrence families degree 3, with base
+    FAST_POLY3 = 7,           // recurrence families degree 2, with base
+    FAST_RBF5 = 8,            // FastKAN, 5 centres (kan_vgg.py's grid_size 5), SiLU base
+    FAST_RELU8 = 9,           // ReLU-KAN g + k = 8, SiLU base (halo and expanded kernels only)
+    FAST_GRAM4 = 10,          // GRAM-KAN degree 3, SiLU base (halo and expanded kernels only)
+    FAST_POLY1 = 11,          // recurrence families degree 0, with base
     FAST_LAST = 11
 };
-// The kernel families instantiated for each fast variant (the one table: the planner asks it which routes a basis may take, the
+// The kernel families instantiated for a fast variant (FastSpec::routes: the planner asks it which routes a basis may take, the
 // launchers instantiate exactly these kernels).
 enum : unsigned {
     ON_TAP_MAJOR = 1u << 0,          // k_conv_fwd / k_conv_bwd_data / k_conv_bwd_weight with FAST = F
@@ -45,28 +45,34 @@ enum : unsigned {
     ON_EXPANDED = 1u << 7,           // k_expand_pm + k_conv_bwd_weight_pmdma
     ON_ROWBLK_BWD_DATA = 1u << 8,    // k_conv_bwd_data with row-ordered pixel blocks (RB = 1)
 };
-constexpr unsigned fast_routes(int f) {
+// THE definition of a fast variant: kernels, launchers and the planner read these facts and restate none of them.
+struct FastSpec {
+    int kind, planes;        // KAN_BASIS_*, planes per channel P (base plane included)
+    bool base;               // plane 0 is the base branch act(x)
+    bool xn_fwd, xn_bwd;     // the basis reads a second tensor xn != x in the forward / weight gradient; also in bwd-data (which then writes dx and dxn)
+    int kc;                  // tap-major LDS step (rows)
+    unsigned routes;         // kernel families instantiated (ON_*)
+};
+constexpr FastSpec fast_spec(int f) {
     constexpr unsigned bspline = ON_TAP_MAJOR | ON_BIG_TILES | ON_HALO_FWD | ON_HALO_BWD_WEIGHT | ON_BAND_FWD | ON_BAND_BWD_WEIGHT |
                                  ON_EXPANDED_FWD | ON_EXPANDED | ON_ROWBLK_BWD_DATA;
     switch (f) {
-        case FAST_BSPLINE_SILU: case FAST_BSPLINE_GELU: return bspline;
-        case FAST_RBF8: return ON_TAP_MAJOR | ON_BAND_FWD | ON_BAND_BWD_WEIGHT;
-        case FAST_CHEBY5: return ON_TAP_MAJOR | ON_BIG_TILES | ON_BAND_FWD | ON_BAND_BWD_WEIGHT;
-        case FAST_CHEBY4: return ON_TAP_MAJOR | ON_HALO_FWD | ON_BAND_FWD;
-        case FAST_POLY4: return ON_TAP_MAJOR | ON_BIG_TILES | ON_HALO_FWD | ON_BAND_FWD;
-        case FAST_POLY3: case FAST_RBF5: case FAST_POLY1: return ON_TAP_MAJOR;
-        case FAST_RELU8: return ON_HALO_FWD | ON_HALO_BWD_WEIGHT | ON_EXPANDED_FWD | ON_EXPANDED;
-        case FAST_GRAM4: return ON_HALO_FWD | ON_HALO_BWD_WEIGHT | ON_EXPANDED;
-        default: return 0;
+        case FAST_BSPLINE_SILU: case FAST_BSPLINE_GELU: return {KAN_BASIS_BSPLINE, 9, true, false, false, 18, bspline};
+        case FAST_RBF8: return {KAN_BASIS_RBF, 9, true, true, true, 18, ON_TAP_MAJOR | ON_BAND_FWD | ON_BAND_BWD_WEIGHT};
+        case FAST_RBF5: return {KAN_BASIS_RBF, 6, true, true, true, 18, ON_TAP_MAJOR};
+        case FAST_CHEBY5: return {KAN_BASIS_CHEBY, 5, false, false, false, 16, ON_TAP_MAJOR | ON_BIG_TILES | ON_BAND_FWD | ON_BAND_BWD_WEIGHT};
+        case FAST_CHEBY4: return {KAN_BASIS_CHEBY, 4, false, false, false, 16, ON_TAP_MAJOR | ON_HALO_FWD | ON_BAND_FWD};
+        case FAST_POLY4: return {KAN_BASIS_POLY, 5, true, true, false, 16, ON_TAP_MAJOR | ON_BIG_TILES | ON_HALO_FWD | ON_BAND_FWD};
+        case FAST_POLY3: return {KAN_BASIS_POLY, 4, true, true, false, 16, ON_TAP_MAJOR};
+        case FAST_POLY1: return {KAN_BASIS_POLY, 2, true, true, false, 16, ON_TAP_MAJOR};
+        case FAST_RELU8: return {KAN_BASIS_RELU, 9, true, false, false, 16, ON_HALO_FWD | ON_HALO_BWD_WEIGHT | ON_EXPANDED_FWD | ON_EXPANDED};
+        case FAST_GRAM4: return {KAN_BASIS_GRAM, 5, true, false, false, 16, ON_HALO_FWD | ON_HALO_BWD_WEIGHT | ON_EXPANDED};
+        default: return {-1, 0, false, true, true, 0, 0};          // FAST_GENERIC: the generic kernels read both tensors, the rest is DevBasis at run time
     }
 }
-constexpr bool fast_has(int f, unsigned routes) { return (fast_routes(f) & routes) == routes && f != FAST_GENERIC; }
-constexpr int fast_kind(int f) {
-    return (f == FAST_RBF8 || f == FAST_RBF5) ? KAN_BASIS_RBF : (f == FAST_CHEBY5 || f == FAST_CHEBY4) ? KAN_BASIS_CHEBY
-         : (f == FAST_POLY4 || f == FAST_POLY3 || f == FAST_POLY1) ? KAN_BASIS_POLY : f == FAST_RELU8 ? KAN_BASIS_RELU
-         : f == FAST_GRAM4 ? KAN_BASIS_GRAM : KAN_BASIS_BSPLINE;
-}
-constexpr int fast_kc(int f) { return fast_kind(f) == KAN_BASIS_BSPLINE || fast_kind(f) == KAN_BASIS_RBF ? 18 : 16; }   // tap-major LDS step
+constexpr int fast_kind(int f) { return fast_spec(f).kind; }
+constexpr int fast_planes(int f) { return fast_spec(f).planes; }
+constexpr bool fast_has(int f, unsigned routes) { return (fast_spec(f).routes & routes) == routes && f != FAST_GENERIC; }
 
 // ---------------------------------------------------------------------------------------------------------------- dispatch helpers
 template <int V> using IC = std::integral_constant<int, V>;

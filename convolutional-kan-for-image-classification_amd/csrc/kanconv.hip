@@ -372,7 +372,7 @@ __global__ __launch_bounds__(WO * WP * 64, (WO * WP > 4 ? 2 : 4)) void k_conv_fw
     const int estride = g.pix_major ? g.B : 1;               // element stride of the (c,hi,wi) index
     // FastKAN / LegendreKAN evaluate their basis on a second tensor, and so does any layer whose base activation the host applied
     // (x = act(input), xn = input, act = identity); the compile-time specs of the other kinds are single-input by construction
-    const bool same_in = (FAST != 0 && KIND != KAN_BASIS_RBF && KIND != KAN_BASIS_POLY) || (x == xn);
+    const bool same_in = !fast_spec(FAST).xn_fwd || (x == xn);
     const kan_rsrc x_rs = make_rsrc(x, x_bytes), xn_rs = make_rsrc(same_in ? x : xn, x_bytes);
     const int wv = wave;
     const unsigned wlane = (unsigned)((lane / (TO / 4)) * Opad + (lane % (TO / 4)) * 4) * 4u;   // this lane inside a 1-KiB weight block
@@ -526,7 +526,7 @@ __global__ __launch_bounds__(WO * 2 * 64, ((WO > 2 && !(R * W == 16 && NIMG * W 
     const float* __restrict__ x, const float* __restrict__ wp, float* __restrict__ z, DevGeom g, DevBasis bs, int Opad,
     int n_pairs, int pairs_per_split, long long slab_elems, unsigned x_bytes, int tiles_o) {
     constexpr int TO = WO * 64, TP = 128, NT = WO * 2 * 64, NW = WO * 2, P = fast_planes(FAST), KC = 2 * P, T = 9;
-    constexpr int KIND = (FAST == 4 || FAST == 5) ? KAN_BASIS_CHEBY : (FAST == 6 || FAST == 7) ? KAN_BASIS_POLY : FAST == 9 ? KAN_BASIS_RELU : FAST == 10 ? KAN_BASIS_GRAM : KAN_BASIS_BSPLINE;
+    constexpr int KIND = fast_kind(FAST);
     constexpr int HW_ = W + 2, HIMG = (R + 2) * HW_, HALO = NIMG * HIMG;          // cells per plane
     constexpr int RPI = 256 / TO, NQ = (KC + RPI - 1) / RPI;
     static_assert(NIMG * R * W == TP && HALO % 2 == 0, "tile shape");
@@ -923,238 +923,61 @@ __global__ __launch_bounds__(256, 4) void k_conv_bwd_data(
     const bool split_out = (dxn != nullptr);
     float* dxs = dx + (size_t)blk.z * slab_elems;
     float* dxns = split_out ? dxn + (size_t)blk.z * slab_elems : nullptr;
-    if (FAST == 3 || FAST == 8) {
-        // FastKAN (8 or 5 centres + SiLU base, P = 9 / 6), two inputs and two outputs: dx = SiLU'(x) G_0 on the raw
-        // tensor, dxn = sum_j (-2 u_j / d) exp(-u_j^2) G_{1+j} on the normalised one (utils/utils.py:33); both inputs
-        // prefetched, hardware exp2.
-        constexpr int FP = FAST == 3 ? 9 : 6, FCH = 64 / FP, NIT = (FCH + 1) / 2;
-        const float inv_d = 1.0f / bs.p0;
+    // the G rows of one half: the accumulators of its two waves -> smem[64][TP], between two barriers (the first: previous readers of smem are
+    // done).  A macro: through a function the compiler no longer pairs the 64 stores into ds_write2_b32.
+#define KAN_G_TO_LDS(half)                                                                                                 \
+    __syncthreads();                                                                                                       \
+    if (w_r == (half)) {                                                                                                   \
+        _Pragma("unroll") for (int mi = 0; mi < 2; ++mi)                                                                   \
+            _Pragma("unroll") for (int ni = 0; ni < 2; ++ni)                                                               \
+                _Pragma("unroll") for (int r = 0; r < 16; ++r)                                                             \
+                    smem[(mi * 32 + mfma_row(r, lane)) * TP + w_p * 64 + ni * 32 + (lane & 31)] = acc[mi][ni][r];          \
+    }                                                                                                                      \
+    __syncthreads();
+    if constexpr (FAST != 0) {
+        // Compile-time specs (fast_spec: FP planes, FCH = 64 / FP whole channels per half; the derivative is stage_unit_grad).  The x values
+        // of this thread's (channel, pixel) pairs are requested before the LDS round trip (the generic loop below pays one dependent
+        // global-load latency per channel): for both halves up front, or -- the two-tensor specs (FastKAN: x and xn in, dx and dxn out) --
+        // the two inputs of one half at a time.
+        constexpr FastSpec S = fast_spec(FAST);
+        constexpr int FP = S.planes, FCH = 64 / FP, NIT = (FCH + 1) / 2, NPF = S.xn_bwd ? 1 : 2;      // NPF: halves prefetched at once
+        float xv[NPF][NIT], nv[NIT]; unsigned ok = 0;
+        // (a macro: as a by-reference lambda the same loop cost every spec ~30 instructions and, in some formulations, spills)
+#define KAN_FETCH(half, slot)                                                                                              \
+        _Pragma("unroll") for (int it = 0; it < NIT; ++it) {                                                                   \
+            const int cl = ol0 + 2 * it, c = (ct * 2 + (half)) * FCH + cl;                                                     \
+            const bool v = cl < FCH && c < g.C && pv;                                                                          \
+            const size_t idx = (size_t)pb * g.xbs + (size_t)c * HW + (size_t)(ph_ * g.W + pw_);                                \
+            xv[slot][it] = v ? x[idx] : 0.f;                                                                                   \
+            if constexpr (S.xn_bwd) nv[it] = v ? xn[idx] : 0.f;                                                                \
+            ok |= (v ? 1u : 0u) << ((slot) * NIT + it);                                                                        \
+        }
+        if constexpr (!S.xn_bwd) {
+#pragma unroll
+            for (int half = 0; half < 2; ++half) KAN_FETCH(half, half)
+        }
 #pragma unroll 1
         for (int half = 0; half < 2; ++half) {
-            float xv[NIT], nv[NIT]; unsigned ok = 0;       // this half's inputs, requested before the LDS round trip
+            if constexpr (S.xn_bwd) { ok = 0; KAN_FETCH(half, 0) }
+            KAN_G_TO_LDS(half)
 #pragma unroll
             for (int it = 0; it < NIT; ++it) {
+                if (!((ok >> ((S.xn_bwd ? 0 : half) * NIT + it)) & 1u)) continue;
                 const int cl = ol0 + 2 * it, c = (ct * 2 + half) * FCH + cl;
-                const bool v = cl < FCH && c < g.C && pv;
+                const float xa = (S.xn_bwd || half == 0) ? xv[0][it] : xv[NPF - 1][it];
+                const InGrad d = stage_unit_grad<KIND, FAST>(bs, sTab, xa, S.xn_bwd ? nv[it] : xa, smem + (cl * FP) * TP + pxl, TP);
                 const size_t idx = (size_t)pb * g.xbs + (size_t)c * HW + (size_t)(ph_ * g.W + pw_);
-                xv[it] = v ? x[idx] : 0.f;
-                nv[it] = v ? xn[idx] : 0.f;
-                ok |= (v ? 1u : 0u) << it;
-            }
-            __syncthreads();
-            if (w_r == half) {
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            smem[(mi * 32 + mfma_row(r, lane)) * TP + w_p * 64 + ni * 32 + (lane & 31)] = acc[mi][ni][r];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                if (!((ok >> it) & 1u)) continue;
-                const int cl = ol0 + 2 * it, c = (ct * 2 + half) * FCH + cl;
-                const float xa = xv[it], xb = nv[it];
-                const float sg = kan_rcp(1.0f + kan_exp2k(xa, -1.44269504088896340736f));
-                const float* G = smem + (cl * FP) * TP + pxl;
-                float sb = 0.f;
-#pragma unroll
-                for (int j = 0; j < FP - 1; ++j) {
-                    const float u = (xb - bs.tab[j]) * inv_d;
-                    sb += u * kan_exp2k(u * u, -1.44269504088896340736f) * G[(1 + j) * TP];
-                }
-                const size_t idx = (size_t)pb * g.xbs + (size_t)c * HW + (size_t)(ph_ * g.W + pw_);
-                dxs[idx] = sg * (1.0f + xa * (1.0f - sg)) * G[0];
-                dxns[idx] = sb * (-2.0f * inv_d);
+                dxs[idx] = d.dx;
+                if constexpr (S.xn_bwd) dxns[idx] = d.dxn;
             }
         }
-        return;
-    }
-    if (FAST == 4 || FAST == 5) {
-        // ChebyKAN degree 4 / 3 (P = 5 / 4 planes, no base branch): x prefetched, dT_k/dx = k U_{k-1}(t) (1 - tanh^2 x)
-        // inside the clamp, 0 where it is active (kan_device.h), tanh through hardware exp2/rcp as in the forward spec.
-        constexpr int FP = FAST == 4 ? 5 : 4, FCH = 64 / FP, NIT = (FCH + 1) / 2;
-        float xv[2][NIT]; unsigned ok = 0;
-#pragma unroll
-        for (int half = 0; half < 2; ++half)
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int cl = ol0 + 2 * it, c = (ct * 2 + half) * FCH + cl;
-                const bool v = cl < FCH && c < g.C && pv;
-                xv[half][it] = v ? x[(size_t)pb * g.xbs + (size_t)c * HW + (size_t)(ph_ * g.W + pw_)] : 0.f;
-                ok |= (v ? 1u : 0u) << (half * NIT + it);
-            }
-#pragma unroll 1
-        for (int half = 0; half < 2; ++half) {
-            __syncthreads();
-            if (w_r == half) {
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            smem[(mi * 32 + mfma_row(r, lane)) * TP + w_p * 64 + ni * 32 + (lane & 31)] = acc[mi][ni][r];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                if (!((ok >> (half * NIT + it)) & 1u)) continue;
-                const int cl = ol0 + 2 * it, c = (ct * 2 + half) * FCH + cl;
-                const float xa = half == 0 ? xv[0][it] : xv[1][it];
-                const float t0 = kan_tanh_fast(xa);
-                const float t = fminf(fmaxf(t0, bs.p0), bs.p1);
-                const float chain = (t0 >= bs.p0 && t0 <= bs.p1) ? (1.0f - t0 * t0) : 0.f;
-                const float* G = smem + (cl * FP) * TP + pxl;
-                float Um = 0.f, Uc = 1.f, sb = 0.f;
-#pragma unroll
-                for (int k = 1; k < FP; ++k) {
-                    sb += (float)k * Uc * G[k * TP];
-                    const float Un = 2.f * t * Uc - Um; Um = Uc; Uc = Un;
-                }
-                dxs[(size_t)pb * g.xbs + (size_t)c * HW + (size_t)(ph_ * g.W + pw_)] = sb * chain;
-            }
-        }
-        return;
-    }
-    if (FAST == 6 || FAST == 7 || FAST == 11) {
-        // Recurrence families, degree 3 (or 0: FAST 11, one constant plane, no polynomial derivative) with a base branch (P = 5 / 4 / 2, CH = 12 / 16 / 32 channels per half), single input
-        // tensor: x prefetched, derivative by the differentiated recurrence with compile-time plane count.
-        constexpr int FP = FAST == 6 ? 5 : FAST == 7 ? 4 : 2, NB = FP - 1, FCH = 64 / FP, NIT = (FCH + 1) / 2;
-        float xv[2][NIT]; unsigned ok = 0;
-#pragma unroll
-        for (int half = 0; half < 2; ++half)
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int cl = ol0 + 2 * it, c = (ct * 2 + half) * FCH + cl;
-                const bool v = cl < FCH && c < g.C && pv;
-                xv[half][it] = v ? x[(size_t)pb * g.xbs + (size_t)c * HW + (size_t)(ph_ * g.W + pw_)] : 0.f;
-                ok |= (v ? 1u : 0u) << (half * NIT + it);
-            }
-#pragma unroll 1
-        for (int half = 0; half < 2; ++half) {
-            __syncthreads();
-            if (w_r == half) {
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            smem[(mi * 32 + mfma_row(r, lane)) * TP + w_p * 64 + ni * 32 + (lane & 31)] = acc[mi][ni][r];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                if (!((ok >> (half * NIT + it)) & 1u)) continue;
-                const int cl = ol0 + 2 * it, c = (ct * 2 + half) * FCH + cl;
-                const float xa = half == 0 ? xv[0][it] : xv[1][it];
-                float dact;
-                if (bs.act == KAN_ACT_SILU) {
-                    const float sg = kan_rcp(1.0f + kan_exp2k(xa, -1.44269504088896340736f));
-                    dact = sg * (1.0f + xa * (1.0f - sg));
-                } else dact = kan_act_grad(bs.act, xa);
-                float t = xa, chain = 1.0f;
-                if (bs.order) {
-                    t = kan_tanh_fast(xa);
-                    chain = 1.0f - t * t;
-                }
-                const float* G = smem + (cl * FP) * TP + pxl;
-                float Tm = bs.tab[0], Tc = bs.tab[1] * t + bs.tab[2], Dm = 0.f, Dc = bs.tab[1];
-                float sb = 0.f;                                        // sum_k T_k'(t) G_k   (T_0' = 0)
-#pragma unroll
-                for (int k = 1; k < NB; ++k) {
-                    sb += Dc * G[(1 + k) * TP];
-                    if (k + 1 < NB) {
-                        const float A = bs.tab[3 * k], B = bs.tab[3 * k + 1], Cc = bs.tab[3 * k + 2], sc = A * t + B;
-                        const float Tn = sc * Tc + Cc * Tm, Dn = A * Tc + sc * Dc + Cc * Dm;
-                        Tm = Tc; Tc = Tn; Dm = Dc; Dc = Dn;
-                    }
-                }
-                dxs[(size_t)pb * g.xbs + (size_t)c * HW + (size_t)(ph_ * g.W + pw_)] = dact * G[0] + sb * chain;
-            }
-        }
-        return;
-    }
-    if (FAST != 0) {
-        // Compile-time spec (B-spline grid 5 / order 3, P = 9, CH = 7; FAST 1: SiLU, 2: GELU), single input tensor.
-        // All x values of this thread's (channel, pixel) pairs are fetched up front (the generic loop below pays one
-        // dependent global-load latency per channel), the cubic's derivative comes from the closed form (kan_device.h,
-        // bspline_uniform<true>, S = 3) and only the <= 4 live planes of G are read back from LDS.
-        constexpr int FP = 9, FCH = 7, NIT = (FCH + 1) / 2;
-        float xv[2][NIT]; unsigned ok = 0;
-#pragma unroll
-        for (int half = 0; half < 2; ++half)
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                const int cl = ol0 + 2 * it, c = (ct * 2 + half) * FCH + cl;
-                const bool v = cl < FCH && c < g.C && pv;
-                xv[half][it] = v ? x[(size_t)pb * g.xbs + (size_t)c * HW + (size_t)(ph_ * g.W + pw_)] : 0.f;
-                ok |= (v ? 1u : 0u) << (half * NIT + it);
-            }
-        const float hh = 0.5f * bs.inv_h;
-#pragma unroll 1
-        for (int half = 0; half < 2; ++half) {
-            __syncthreads();
-            if (w_r == half) {
-#pragma unroll
-                for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r)
-                            smem[(mi * 32 + mfma_row(r, lane)) * TP + w_p * 64 + ni * 32 + (lane & 31)] = acc[mi][ni][r];
-            }
-            __syncthreads();
-#pragma unroll
-            for (int it = 0; it < NIT; ++it) {
-                if (!((ok >> (half * NIT + it)) & 1u)) continue;
-                const int cl = ol0 + 2 * it, c = (ct * 2 + half) * FCH + cl;
-                const float xa = half == 0 ? xv[0][it] : xv[1][it];
-                float dact;
-                if (FAST == 1) {
-                    const float sg = kan_rcp(1.0f + kan_exp2k(xa, -1.44269504088896340736f));
-                    dact = sg * (1.0f + xa * (1.0f - sg));
-                } else dact = kan_act_grad(KAN_ACT_GELU, xa);
-                const float* G = smem + (cl * FP) * TP + pxl;
-                float sum = dact * G[0];
-                if (xa >= bs.g0 && xa < bs.gN) {                       // NaN fails both, as the reference's indicator
-                    const int i = min((int)((xa - bs.g0) * bs.inv_h), 10);
-#ifdef KAN_EXACT_TRANSCENDENTALS
-                    const double ihd = 1.0 / ((double)sTab[i + 1] - (double)sTab[i]), hd = 0.5 * ihd;
-                    const double ud = fmin(fmax(((double)xa - (double)sTab[i]) * ihd, 0.0), 1.0), vd = 1.0 - ud, ud2 = ud * ud;
-                    const float n0 = (float)(-hd * vd * vd), n1 = (float)(hd * (3.0 * ud2 - 4.0 * ud)), n2 = (float)(hd * (-3.0 * ud2 + 2.0 * ud + 1.0)), n3 = (float)(hd * ud2);
-#else
-                    const float u = fminf(fmaxf((xa - sTab[i]) * bs.inv_h, 0.f), 1.f), v = 1.f - u, u2 = u * u;
-                    const float n0 = -hh * v * v, n1 = hh * (3.f * u2 - 4.f * u), n2 = hh * (-3.f * u2 + 2.f * u + 1.f), n3 = hh * u2;
-#endif
-                    const int j0 = i - 3;                              // bases j0 .. j0+3, kept where 0 <= j < 8
-                    sum += ((unsigned)j0 < 8u ? n0 * G[(1 + j0) * TP] : 0.f) + ((unsigned)(j0 + 1) < 8u ? n1 * G[(2 + j0) * TP] : 0.f)
-                         + ((unsigned)(j0 + 2) < 8u ? n2 * G[(3 + j0) * TP] : 0.f) + ((unsigned)(j0 + 3) < 8u ? n3 * G[(4 + j0) * TP] : 0.f);
-                }
-                dxs[(size_t)pb * g.xbs + (size_t)c * HW + (size_t)(ph_ * g.W + pw_)] = sum;
-            }
-        }
+#undef KAN_FETCH
         return;
     }
 #pragma unroll 1
     for (int half = 0; half < 2; ++half) {
-        __syncthreads();                                   // previous readers of smem are done
-        if (w_r == half) {
-#pragma unroll
-            for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-                for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        int row = mi * 32 + mfma_row(r, lane);
-                        int col = w_p * 64 + ni * 32 + (lane & 31);
-                        smem[row * TP + col] = acc[mi][ni][r];
-                    }
-        }
-        __syncthreads();
+        KAN_G_TO_LDS(half)
+#undef KAN_G_TO_LDS
         for (int cl = ol0; cl < CH; cl += 2) {
             const int c = (ct * 2 + half) * CH + cl;
             if (c >= g.C || !pv) continue;
@@ -1290,7 +1113,7 @@ __global__ __launch_bounds__(WR * WC * 64, (WR * WC > 4 ? 2 : 4)) void k_conv_bw
         }
         sItem[i] = v;
     }
-    const bool same_in = (FAST != 0 && KIND != KAN_BASIS_RBF && KIND != KAN_BASIS_POLY) || (x == xn);
+    const bool same_in = !fast_spec(FAST).xn_fwd || (x == xn);
     __syncthreads();
 
     float xa[UPF], xb[UPF], zr[ZL]; unsigned inb_mask = 0;
@@ -1472,7 +1295,7 @@ template <int FAST, int W, int R, int NIMG>
 __global__ __launch_bounds__(256, 4) void k_conv_bwd_weight_halo(
     const float* __restrict__ dz, const float* __restrict__ x, float* __restrict__ dwp, DevGeom g, DevBasis bs, int Krows, int Opad,
     int n_bands, int bands_per_split, long long slab_elems, unsigned x_bytes, unsigned dz_bytes, int tiles_o) {
-    constexpr int KIND = (FAST == 4 || FAST == 5) ? KAN_BASIS_CHEBY : (FAST == 6 || FAST == 7) ? KAN_BASIS_POLY : FAST == 9 ? KAN_BASIS_RELU : FAST == 10 ? KAN_BASIS_GRAM : KAN_BASIS_BSPLINE;
+    constexpr int KIND = fast_kind(FAST);
     constexpr int P = fast_planes(FAST), T = 9, PT = P * T;
     constexpr int TR = 128, TO = 128, NT = 256, KPX = 16;
     constexpr int HWc = W + 2, HIMG = (R + 2) * HWc, CELLS = NIMG * HIMG;        // a band is NIMG images x R rows (NIMG > 1: whole images)
@@ -2872,7 +2695,7 @@ int kan_conv_fwd(const float* x, const float* xn, const float* wp, float* z, con
         return launch_ok("dw_fwd");
     }
     if (cp.fwd == Route::BAND) {
-        if (x != xn && b->kind != KAN_BASIS_RBF && b->kind != KAN_BASIS_POLY) return fail("this basis / activation pair runs on single-input kernels: pass xn == x");
+        if (x != xn && !fast_spec(cp.fast).xn_fwd) return fail("this basis / activation pair runs on single-input kernels: pass xn == x");
         return kan_band_fwd_launch(x, xn, wp, z, g, b, &cp.band, pl.fwd_splits, pl.fwd_slab_elems, stream);
     }
     const FwdCfg& c = cp.fc;
@@ -2914,7 +2737,7 @@ int kan_conv_fwd(const float* x, const float* xn, const float* wp, float* z, con
         const int hw = (int)(((long long)t * c.TP) / g->B);
         return ceil_div(live_taps_out(g, hw < g->Ho * g->Wo ? hw : 0) * ceil_div(g->C, pl.IPC), cps > 0 ? cps : 1);
     });
-    if (x != xn && cp.fast != FAST_GENERIC && b->kind != KAN_BASIS_RBF && b->kind != KAN_BASIS_POLY)
+    if (x != xn && !fast_spec(cp.fast).xn_fwd)
         return fail("this basis / activation pair runs on single-input kernels: pass xn == x");
     auto launch = [&](auto kind, auto fast, auto wo, auto kc) {
         constexpr int WO = decltype(wo)::value;
@@ -2924,10 +2747,10 @@ int kan_conv_fwd(const float* x, const float* xn, const float* wp, float* z, con
     const bool fast = dispatch_fast<ON_TAP_MAJOR>(cp.fast, [&](auto fv) {
         constexpr int F = decltype(fv)::value;
         if constexpr (fast_has(F, ON_BIG_TILES)) {
-            if (c.TO == 256) return launch(IC<fast_kind(F)>{}, fv, IC<4>{}, IC<fast_kc(F)>{});
+            if (c.TO == 256) return launch(IC<fast_kind(F)>{}, fv, IC<4>{}, IC<fast_spec(F).kc>{});
         }
-        if (c.TO == 128) launch(IC<fast_kind(F)>{}, fv, IC<2>{}, IC<fast_kc(F)>{});
-        else launch(IC<fast_kind(F)>{}, fv, IC<1>{}, IC<fast_kc(F)>{});
+        if (c.TO == 128) launch(IC<fast_kind(F)>{}, fv, IC<2>{}, IC<fast_spec(F).kc>{});
+        else launch(IC<fast_kind(F)>{}, fv, IC<1>{}, IC<fast_spec(F).kc>{});
     });
     if (!fast) dispatch_kind(b->kind, [&](auto kind) {
         pick<18, 12, 16>(pl.KC, [&](auto kc) {
@@ -2984,9 +2807,8 @@ static int conv_bwd_data_impl(const float* dz, const float* x, const float* xn, 
         const int hw = (int)(((long long)t * 128) / g->B);
         return ceil_div(live_taps_in(g, hw < g->H * g->W ? hw : 0) * c.n_ob, cps > 0 ? cps : 1);
     });
-    // compile-time epilogues: single-input specs need x == xn and one output; the FastKAN specs need both tensors
-    const int fv = cp.fast;
-    const int fast = (fv == FAST_RBF8 || fv == FAST_RBF5) ? ((x != xn && dxn) ? fv : 0) : ((x == xn && !dxn) ? fv : 0);
+    // compile-time epilogues: single-input specs need x == xn and one output; the two-tensor (FastKAN) specs need both tensors
+    const int fast = (fast_spec(cp.fast).xn_bwd ? (x != xn && dxn) : (x == xn && !dxn)) ? cp.fast : FAST_GENERIC;
     // 4x4 planes in tiles of 8 whole images: row-ordered pixel blocks, dead (row, tap row) blocks skipped (see the kernel)
     const bool rb = !dg.pix_major && cp.rowblk_bwd_data;
     const unsigned dz_bytes = (unsigned)((long long)g->B * g->y_bstride * 4);
@@ -3022,7 +2844,7 @@ int kan_conv_bwd_weight(const float* dz, const float* x, const float* xn, float*
         return launch_ok("dw_bwd_weight");
     }
     if (cp.bwd_weight == Route::BAND) {
-        if (x != xn && b->kind != KAN_BASIS_RBF && b->kind != KAN_BASIS_POLY) return fail("this basis / activation pair runs on single-input kernels: pass xn == x");
+        if (x != xn && !fast_spec(cp.fast).xn_fwd) return fail("this basis / activation pair runs on single-input kernels: pass xn == x");
         return kan_band_bwd_weight_launch(dz, x, xn, dwp, g, b, &cp.band, pl.bwd_weight_splits, pl.bwd_weight_slab_elems, stream);
     }
     const unsigned x_bytes = (unsigned)((long long)g->B * g->x_bstride * 4), dz_bytes = (unsigned)((long long)g->B * g->y_bstride * 4);
@@ -3052,7 +2874,7 @@ int kan_conv_bwd_weight(const float* dz, const float* x, const float* xn, float*
     if ((long long)c.tiles_o * ngroups(g) > 65535) return fail("groups * output tiles exceed the grid limit");
     dim3 grid(c.tiles_r, c.tiles_o * ngroups(g), pl.bwd_weight_splits);
     const int cps = dg.pix_major ? pl.bwd_weight_target : ceil_div(c.chunks, pl.bwd_weight_splits);
-    if (x != xn && cp.fast != FAST_GENERIC && b->kind != KAN_BASIS_RBF && b->kind != KAN_BASIS_POLY)
+    if (x != xn && !fast_spec(cp.fast).xn_fwd)
         return fail("this basis / activation pair runs on single-input kernels: pass xn == x");
     auto launch = [&](auto kind, auto fast, auto wr, auto wc) {
         constexpr int WR = decltype(wr)::value, WC = decltype(wc)::value;
