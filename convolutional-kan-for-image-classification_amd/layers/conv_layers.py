@@ -145,14 +145,32 @@ def conv3d_stage(basis_kw, kernel_size, stride, padding, dilation, groups, x, xn
     return z
 
 
+def _norm_affine(mods):
+    """Per-group lists (gammas, betas) of the norm modules, or (None, None): the form `ops.kan_conv_in_prelu` takes."""
+    if mods[0].affine:
+        return [m.weight for m in mods], [m.bias for m in mods]
+    return None, None
+
+
+def _gamma_beta(mods):
+    """(gamma, beta) of all groups concatenated, or (None, None): the form `ops.instance_norm` takes."""
+    gam, bet = _norm_affine(mods)
+    return (torch.cat(gam), torch.cat(bet)) if gam is not None else (None, None)
+
+
+def _channel_major(poly_weights, n):
+    """Per-group views of a plane-major ``poly_weights`` [G, O/G, n * C/G, k, k] (channel index j*C + c) in the kernels'
+    channel-major order (c*n + j); autograd carries the gradient back."""
+    G, og, cn, k = poly_weights.shape[:4]
+    return [poly_weights[g].view(og, n, cn // n, k, k).transpose(1, 2).reshape(og, cn, k, k) for g in range(G)]
+
+
 def _norm3d(mods, prelus, z, og):
     """Per-group norm (+ PReLU) of a [B, O, D, H, W] tensor: plain InstanceNorm3d runs on the InstanceNorm kernel with the
     volume as one plane; anything else is the caller's own module."""
     if all(type(m) is nn.InstanceNorm3d and not m.track_running_stats for m in mods):
         B, O, Dz, Hz, Wz = z.shape
-        gam = torch.cat([m.weight for m in mods]) if mods[0].affine else None
-        bet = torch.cat([m.bias for m in mods]) if mods[0].affine else None
-        y = ops.instance_norm(z.reshape(B, O, Dz * Hz, Wz), gam, bet, eps=mods[0].eps).view(B, O, Dz, Hz, Wz)
+        y = ops.instance_norm(z.reshape(B, O, Dz * Hz, Wz), *_gamma_beta(mods), eps=mods[0].eps).view(B, O, Dz, Hz, Wz)
         parts = [y[:, g * og:(g + 1) * og] for g in range(len(mods))]
     else:
         parts = [mods[g](z[:, g * og:(g + 1) * og]) for g in range(len(mods))]
@@ -193,11 +211,35 @@ class _HipLayer(nn.Module):
     def _w(self, convs):
         return [m.weight.unsqueeze(2) for m in convs] if getattr(self, "ndim", 2) == 1 else [m.weight for m in convs]
 
-    @staticmethod
-    def _norm_affine(mods):
-        if mods[0].affine:
-            return [m.weight for m in mods], [m.bias for m in mods]
-        return None, None
+    pool_types = ()     # the one statement of which layers take `forward(x, pool=)`, and in which form: see _FusedTailLayer
+
+    def takes_pool(self, pool) -> bool:
+        """Whether the models hand this layer the MaxPool2d that follows it as `forward(x, pool=pool)`: True for
+        MaxPool2d(2, 2) (models/kan_vgg.py), a (kernel, stride) tuple (models/kan_alexnet.py)."""
+        return getattr(self, "ndim", 2) == 2 and isinstance(pool, self.pool_types)
+
+    def conv_spec(self) -> ops.ConvSpec:
+        return self._spec(**self._basis_kw())
+
+    def _build(self, conv_class, norm_class, cg, og, basis=None, planes=0, prelus=False, norm_dim=None, plane_major=0):
+        """The per-group module lists, created and initialised in the order every family's reference constructor uses (a seeded
+        construction draws the same weights): ``base_conv``, the basis convs `planes * cg -> og` under the attribute name `basis`,
+        ``layer_norm`` over `norm_dim` (default `og`) channels, ``prelus``, a plane-major ``poly_weights`` of `plane_major` planes
+        (drawn here, initialised by the caller); then the Kaiming init of the base and the basis convs."""
+        def convs(cin):
+            return nn.ModuleList([conv_class(cin, og, self.kernel_size, self.stride, self.padding, self.dilation, groups=1, bias=False)
+                                  for _ in range(self.groups)])
+        self.base_conv = convs(cg)
+        if basis is not None:
+            setattr(self, basis, convs(planes * cg))
+        self.layer_norm = nn.ModuleList([norm_class(og if norm_dim is None else norm_dim, **_filter_norm_kwargs(norm_class, self.norm_kwargs))
+                                         for _ in range(self.groups)])
+        if prelus:
+            self.prelus = nn.ModuleList([nn.PReLU() for _ in range(self.groups)])
+        if plane_major:
+            self.poly_weights = nn.Parameter(torch.randn(self.groups, og, cg * plane_major, *([self.kernel_size] * self.ndim)))
+        for conv in [*self.base_conv, *(getattr(self, basis) if basis is not None else ())]:
+            nn.init.kaiming_uniform_(conv.weight, nonlinearity='linear')
 
     def _base_input(self, x):
         """(base-branch tensor, basis tensor or None): `(act(x), x)` when the host applies the activation (no device functor
@@ -206,24 +248,87 @@ class _HipLayer(nn.Module):
             return self.base_activation(x), x
         return x, None
 
+    def _norm_act(self, z):
+        """Tail of the 'norm, then activation' layers (Jacobi, Legendre, Bersnstein, ReLU-KAN, GRAM) for the (lifted) pre-norm
+        tensor: the InstanceNorm kernel, or the caller's own norm modules on the layer's own rank (nn.LayerNorm over the
+        flattened group), then ``base_activation``."""
+        mods = self.layer_norm
+        if _fusable_instnorm(mods):
+            y = self._lower(ops.instance_norm(z, *_gamma_beta(mods), eps=mods[0].eps))
+        else:
+            z = self._lower(z)
+            og = z.shape[1] // self.groups
+            parts = []
+            for g, norm in enumerate(mods):
+                zg = z[:, g * og:(g + 1) * og]
+                parts.append(norm(zg.reshape(zg.shape[0], -1)).view(zg.shape) if isinstance(norm, nn.LayerNorm) else norm(zg))
+            y = torch.cat(parts, dim=1)
+        return self.base_activation(y)
+
+
+class _FusedTailLayer(_HipLayer):
+    """The one forward of the layers shaped  y = Dropout([PReLU](norm(conv stage)))  -- B-spline, the recurrence families,
+    FourierKAN, ChebyKAN.  A subclass gives `_basis_kw()`, the attribute name of its basis-conv list (`_basis`) and whether
+    it has a base branch with PReLUs (`_has_base`; ChebyKAN has neither)."""
+    _basis = "poly_conv"
+    _has_base = True
+    pool_types = (bool, tuple)
+
     def _norm_prelu(self, z):
         """Un-fused tail for the (lifted) [B, O, H, W] pre-norm tensor: the InstanceNorm kernel (or the caller's own norm
-        modules on the layer's own rank), then PReLU.  Returns the tensor in the layer's rank."""
-        og, mods = self.output_dim_group, self.layer_norm
+        modules on the layer's own rank), then PReLU where the layer has them.  Returns the tensor in the layer's rank."""
+        mods, og = self.layer_norm, z.shape[1] // self.groups
         if _fusable_instnorm(mods):
-            gam = torch.cat([m.weight for m in mods]) if mods[0].affine else None
-            bet = torch.cat([m.bias for m in mods]) if mods[0].affine else None
-            n = self._lower(ops.instance_norm(z.contiguous(), gam, bet, eps=mods[0].eps))
+            n = self._lower(ops.instance_norm(z.contiguous(), *_gamma_beta(mods), eps=mods[0].eps))
             parts = [n[:, g * og:(g + 1) * og] for g in range(self.groups)]
         else:
             z = self._lower(z)
             parts = [mods[g](z[:, g * og:(g + 1) * og]) for g in range(self.groups)]
-        parts = [self.prelus[g](t) for g, t in enumerate(parts)]
+        if self._has_base:
+            parts = [self.prelus[g](t) for g, t in enumerate(parts)]
         return parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+
+    def _forward3d(self, x):
+        """[B, C, D, H, W] layers (the ...KANConv3DLayer shims of the reference): each depth tap is one launch set of the 2-D
+        kernels, on the same basis description as conv_spec()."""
+        xa, xb = self._base_input(x) if self._has_base else (x, None)
+        z = conv3d_stage(self._basis_kw(), self.kernel_size, self.stride, self.padding, self.dilation, self.groups, xa, xb,
+                         [m.weight for m in self.base_conv] if self._has_base else [], [m.weight for m in getattr(self, self._basis)])
+        y = _norm3d(self.layer_norm, self.prelus if self._has_base else None, z, self.output_dim // self.groups)
+        return self.dropout(y) if self.dropout is not None else y
+
+    def forward(self, x, pool=False):
+        """`pool` (not part of the reference signature) returns max_pool2d(layer(x), ...): True for a layer that is followed by
+        MaxPool2d(2, 2) (models/kan_vgg.py), `(k, s)` for a general MaxPool2d(k, s) without padding (models/kan_alexnet.py:
+        (3, 2)).  Where the tail is fused and `ops.pool_fusable`, the pooling is done inside the InstanceNorm(+PReLU) kernels."""
+        if self.ndim == 3:
+            if pool:
+                raise NotImplementedError("pool is a 2-D fusion")
+            return self._forward3d(x)
+        spec = self.conv_spec()
+        x = self._lift(x)
+        wb = self._w(self.base_conv) if self._has_base else []
+        ws = self._w(getattr(self, self._basis))
+        prelus = [m.weight for m in self.prelus] if self._has_base else None
+        xa, xb = self._base_input(x) if self._has_base else (x, None)      # (act(x), x) when the host applies the activation
+        windowed = spec.n_basis + int(spec.has_base) > L.KAN_MAX_PLANES    # more planes than one launch holds: KANConvNDLayer._windowed_stage
+        if not windowed and xb is None and _fusable_instnorm(self.layer_norm) and all(p.numel() == 1 for p in prelus or ()):
+            gam, bet = _norm_affine(self.layer_norm)
+            if pool and self.ndim == 2 and self.dropout is None and ops.pool_fusable(pool, *spec.out_hw(x.shape[2], x.shape[3])):
+                return ops.kan_conv_in_prelu(spec, x, wb, ws, gam, bet, prelus, eps=self.layer_norm[0].eps, pool=pool)
+            y = self._lower(ops.kan_conv_in_prelu(spec, x, wb, ws, gam, bet, prelus, eps=self.layer_norm[0].eps))
+        else:
+            # other norm classes (e.g. BatchNorm2d), a host-applied activation or plane windows: HIP conv stage, then the un-fused tail
+            y = self._norm_prelu(self._windowed_stage(xa, xb, wb, ws) if windowed else ops.kan_conv(spec, xa, xb, wb, ws))
+        if self.dropout is not None:
+            y = self.dropout(y)
+        return _unfused_pool(y, pool) if pool else y
 
 
 # =========================================================================================== B-spline
-class KANConvNDLayer(_HipLayer):
+class KANConvNDLayer(_FusedTailLayer):
+    _basis = "spline_conv"
+
     def __init__(self, conv_class, norm_class, input_dim, output_dim, spline_order, kernel_size,
                  groups=1, padding=0, stride=1, dilation=1,
                  ndim: int = 2, grid_size=5, base_activation=nn.GELU, grid_range=[-1, 1], dropout=0.0,
@@ -240,31 +345,16 @@ class KANConvNDLayer(_HipLayer):
         self.dropout = _dropout2d(dropout, ndim)
         _check_groups(groups, input_dim, output_dim)
         self.input_dim_group, self.output_dim_group = input_dim // groups, output_dim // groups
-
-        cg, og = self.input_dim_group, self.output_dim_group
-        self.base_conv = nn.ModuleList([conv_class(cg, og, kernel_size, stride, padding, dilation, groups=1, bias=False)
-                                        for _ in range(groups)])
-        self.spline_conv = nn.ModuleList([conv_class((grid_size + spline_order) * cg, og, kernel_size, stride, padding, dilation,
-                                                     groups=1, bias=False) for _ in range(groups)])
-        self.layer_norm = nn.ModuleList([norm_class(og, **_filter_norm_kwargs(norm_class, norm_kwargs)) for _ in range(groups)])
-        self.prelus = nn.ModuleList([nn.PReLU() for _ in range(groups)])
-
+        self._build(conv_class, norm_class, self.input_dim_group, self.output_dim_group, "spline_conv", grid_size + spline_order, prelus=True)
         h = (self.grid_range[1] - self.grid_range[0]) / grid_size
         # plain attribute, not a buffer: absent from state_dict exactly as in kan_layers.py:184-190
         self.grid = torch.linspace(self.grid_range[0] - h * spline_order, self.grid_range[1] + h * spline_order,
                                    grid_size + 2 * spline_order + 1, dtype=torch.float32)
-        for conv in self.base_conv:
-            nn.init.kaiming_uniform_(conv.weight, nonlinearity='linear')
-        for conv in self.spline_conv:
-            nn.init.kaiming_uniform_(conv.weight, nonlinearity='linear')
         self._act_code = _act_code(self.base_activation, host_ok=True)
 
     def _basis_kw(self):
         return dict(kind=L.BASIS_BSPLINE, n_basis=self.grid_size + self.spline_order, order=self.spline_order,
                     act=self._act_code, p0=0.0, p1=0.0, table=tuple(float(v) for v in self.grid.tolist()))
-
-    def conv_spec(self) -> ops.ConvSpec:
-        return self._spec(**self._basis_kw())
 
     def _plane_windows(self):
         """The library holds at most KAN_MAX_PLANES = 16 planes per channel in one launch; the reference takes any grid_size
@@ -272,13 +362,14 @@ class KANConvNDLayer(_HipLayer):
         bases of a B-spline layer built on knots[j0 : j1 + order + 1] -- and the conv stage is linear in the planes.  A layer of more than
         16 planes therefore runs one launch set per window of <= 16 planes (the first carries the base branch) and sums the results:
         [(spec, j0, j1, with_base), ...]."""
-        n, S, knots = self.grid_size + self.spline_order, self.spline_order, [float(v) for v in self.grid.tolist()]
+        kw = self._basis_kw()
+        n, S, knots = kw["n_basis"], self.spline_order, kw["table"]
         out, j0, first = [], 0, True
         while j0 < n:
             has_base = first and self._act_code != L.ACT_NONE
             j1 = min(n, j0 + L.KAN_MAX_PLANES - (1 if has_base else 0))
-            out.append((self._spec(kind=L.BASIS_BSPLINE, n_basis=j1 - j0, order=S, act=self._act_code if has_base else L.ACT_NONE, p0=0.0, p1=0.0,
-                                   table=tuple(knots[j0:j1 + S + 1])), j0, j1, has_base))
+            out.append((self._spec(**dict(kw, n_basis=j1 - j0, act=self._act_code if has_base else L.ACT_NONE, table=knots[j0:j1 + S + 1])),
+                        j0, j1, has_base))
             j0, first = j1, False
         return out
 
@@ -293,45 +384,6 @@ class KANConvNDLayer(_HipLayer):
                                 wb if has_base else [], wsl)
             z = part if z is None else z + part
         return z
-
-    def _forward3d(self, x):
-        xa, xb = self._base_input(x)
-        z = conv3d_stage(self._basis_kw(), self.kernel_size, self.stride, self.padding, self.dilation, self.groups, xa, xb,
-                         [m.weight for m in self.base_conv], [m.weight for m in self.spline_conv])
-        y = _norm3d(self.layer_norm, self.prelus, z, self.output_dim_group)
-        return self.dropout(y) if self.dropout is not None else y
-
-    def forward(self, x, pool=False):
-        """`pool=True` (not part of the reference signature; used by models/kan_vgg.py for a layer that is followed by
-        MaxPool2d(2, 2)) returns max_pool2d(layer(x), 2, 2) with the pooling done inside the InstanceNorm+PReLU kernels;
-        `pool=(k, s)` likewise for a general MaxPool2d(k, s) without padding (models/kan_alexnet.py: (3, 2))."""
-        if self.ndim == 3:
-            if pool:
-                raise NotImplementedError("pool=True is a 2-D fusion")
-            return self._forward3d(x)
-        spec = self.conv_spec()
-        x = self._lift(x)
-        wb, ws = self._w(self.base_conv), self._w(self.spline_conv)
-        prelus = [m.weight for m in self.prelus]
-        xa, xb = self._base_input(x)
-        if spec.n_basis + int(spec.has_base) > L.KAN_MAX_PLANES:             # more planes than one launch holds: plane windows, un-fused tail
-            y = self._norm_prelu(self._windowed_stage(xa, xb, wb, ws))
-            if self.dropout is not None:
-                y = self.dropout(y)
-            return _unfused_pool(y, pool) if pool else y
-        if xb is None and _fusable_instnorm(self.layer_norm) and all(p.numel() == 1 for p in prelus):
-            gam, bet = self._norm_affine(self.layer_norm)
-            if pool and self.ndim == 2 and self.dropout is None:
-                ho, wo = spec.out_hw(x.shape[2], x.shape[3])
-                if pool is not True or (ho % 2 == 0 and wo % 2 == 0):
-                    return ops.kan_conv_in_prelu(spec, x, wb, ws, gam, bet, prelus, eps=self.layer_norm[0].eps, pool=pool)
-            y = self._lower(ops.kan_conv_in_prelu(spec, x, wb, ws, gam, bet, prelus, eps=self.layer_norm[0].eps))
-        else:
-            # other norm classes (e.g. BatchNorm2d) or a host-applied activation: HIP conv stage, then the un-fused tail
-            y = self._norm_prelu(ops.kan_conv(spec, xa, xb, wb, ws))
-        if self.dropout is not None:
-            y = self.dropout(y)
-        return _unfused_pool(y, pool) if pool else y
 
 
 class KANConv3DLayer(KANConvNDLayer):
@@ -387,17 +439,9 @@ class FastKANConvNDLayer(_HipLayer):
         self.norm_kwargs = norm_kwargs
         _check_groups(groups, input_dim, output_dim)
         cg, og = input_dim // groups, output_dim // groups
-        self.base_conv = nn.ModuleList([conv_class(cg, og, kernel_size, stride, padding, dilation, groups=1, bias=False)
-                                        for _ in range(groups)])
-        self.spline_conv = nn.ModuleList([conv_class(grid_size * cg, og, kernel_size, stride, padding, dilation, groups=1, bias=False)
-                                          for _ in range(groups)])
-        self.layer_norm = nn.ModuleList([norm_class(cg, **_filter_norm_kwargs(norm_class, norm_kwargs)) for _ in range(groups)])
+        self._build(conv_class, norm_class, cg, og, "spline_conv", grid_size, norm_dim=cg)       # the norm is on the INPUT of the RBFs
         self.rbf = RadialBasisFunction(grid_range[0], grid_range[1], grid_size)
         self.dropout = _dropout2d(dropout, ndim)
-        for conv in self.base_conv:
-            nn.init.kaiming_uniform_(conv.weight, nonlinearity='linear')
-        for conv in self.spline_conv:
-            nn.init.kaiming_uniform_(conv.weight, nonlinearity='linear')
         self._act_code = _act_code(self.base_activation, host_ok=True)
         self._centres = tuple(float(v) for v in self.rbf.grid.detach().tolist())
 
@@ -405,17 +449,12 @@ class FastKANConvNDLayer(_HipLayer):
         return dict(kind=L.BASIS_RBF, n_basis=self.grid_size, order=0, act=self._act_code, p0=float(self.rbf.denominator), p1=0.0,
                     table=self._centres)
 
-    def conv_spec(self) -> ops.ConvSpec:
-        return self._spec(**self._basis_kw())
-
     def _forward3d(self, x):
         xs = self.dropout(x) if self.dropout is not None else x
         cg = self.input_dim // self.groups
         if all(type(m) is nn.InstanceNorm3d and not m.track_running_stats for m in self.layer_norm):
             B, C, D, H, W = xs.shape
-            gam = torch.cat([m.weight for m in self.layer_norm]) if self.layer_norm[0].affine else None
-            bet = torch.cat([m.bias for m in self.layer_norm]) if self.layer_norm[0].affine else None
-            xn = ops.instance_norm(xs.reshape(B, C, D * H, W), gam, bet, eps=self.layer_norm[0].eps).view(B, C, D, H, W)
+            xn = ops.instance_norm(xs.reshape(B, C, D * H, W), *_gamma_beta(self.layer_norm), eps=self.layer_norm[0].eps).view(B, C, D, H, W)
         else:
             xn = torch.cat([self.layer_norm[g](xs[:, g * cg:(g + 1) * cg]) for g in range(self.groups)], dim=1)
         return conv3d_stage(self._basis_kw(), self.kernel_size, self.stride, self.padding, self.dilation, self.groups, self._base_input(x)[0], xn,
@@ -428,13 +467,8 @@ class FastKANConvNDLayer(_HipLayer):
         xs = self.dropout(x) if self.dropout is not None else x
         cg = self.input_dim // self.groups
         if _fusable_instnorm(self.layer_norm):
-            if self.layer_norm[0].affine:
-                gam = torch.cat([m.weight for m in self.layer_norm])
-                bet = torch.cat([m.bias for m in self.layer_norm])
-            else:
-                gam = bet = None
             xn = self._lift(xs) if xs.dim() == 3 else xs
-            xn = ops.instance_norm(xn.contiguous(), gam, bet, eps=self.layer_norm[0].eps)
+            xn = ops.instance_norm(xn.contiguous(), *_gamma_beta(self.layer_norm), eps=self.layer_norm[0].eps)
         else:
             xn = self._lift(torch.cat([self.layer_norm[g](xs[:, g * cg:(g + 1) * cg]) for g in range(self.groups)], dim=1))
         return self._lower(ops.kan_conv(self.conv_spec(), self._lift(self._base_input(x)[0]), xn, self._w(self.base_conv), self._w(self.spline_conv)))
@@ -471,7 +505,10 @@ class FastKANConv2DLayer(FastKANConvNDLayer):
 
 
 # =========================================================================================== ChebyKAN
-class ChebyKANConvNDLayer(_HipLayer):
+class ChebyKANConvNDLayer(_FusedTailLayer):
+    _has_base = False                                   # cheby_kan_layers.py:39-111: no base branch, no PReLU
+    pool_types = (tuple,)                               # models/kan_alexnet.py fuses its MaxPool2d(3, 2); models/kan_vgg.py leaves ChebyKAN un-fused
+
     def __init__(self, conv_class, norm_layer, input_dim, output_dim, degree, kernel_size,
                  groups=1, padding=0, stride=1, dilation=1, ndim: int = 2, dropout=0.0, **norm_kwargs):
         super().__init__()
@@ -496,36 +533,6 @@ class ChebyKANConvNDLayer(_HipLayer):
         lo = float(np.float32(-1 + self.epsilon))       # torch.clamp casts its Python-float bounds to fp32
         hi = float(np.float32(1 - self.epsilon))
         return dict(kind=L.BASIS_CHEBY, n_basis=self.degree + 1, order=0, act=L.ACT_NONE, p0=lo, p1=hi, table=())
-
-    def conv_spec(self) -> ops.ConvSpec:
-        return self._spec(**self._basis_kw())
-
-    def forward(self, x, pool=False):
-        """`pool` (not part of the reference signature; models/kan_alexnet.py passes (3, 2) for a layer followed by MaxPool2d(3, 2)): True or a
-        (kernel, stride) pair -- returns max_pool2d(layer(x), kernel, stride) with the pooling done inside the InstanceNorm kernels."""
-        if self.ndim == 3:
-            if pool:
-                raise NotImplementedError("pool is a 2-D fusion")
-            z = conv3d_stage(self._basis_kw(), self.kernel_size, self.stride, self.padding, self.dilation, self.groups, x, None, [],
-                             [m.weight for m in self.poly_conv])
-            y = _norm3d(self.layer_norm, None, z, self.output_dim // self.groups)
-            return self.dropout(y) if self.dropout is not None else y
-        spec = self.conv_spec()
-        x = self._lift(x)
-        wp = self._w(self.poly_conv)
-        if pool and self.ndim == 2 and self.dropout is None and _fusable_instnorm(self.layer_norm):
-            gam, bet = self._norm_affine(self.layer_norm)
-            return ops.kan_conv_in_prelu(spec, x, [], wp, gam, bet, None, eps=self.layer_norm[0].eps, pool=pool)
-        if _fusable_instnorm(self.layer_norm):
-            gam, bet = self._norm_affine(self.layer_norm)
-            y = self._lower(ops.kan_conv_in_prelu(spec, x, [], wp, gam, bet, None, eps=self.layer_norm[0].eps))
-        else:
-            z = self._lower(ops.kan_conv(spec, x, None, [], wp))
-            og = self.output_dim // self.groups
-            y = torch.cat([self.layer_norm[g](z[:, g * og:(g + 1) * og]) for g in range(self.groups)], dim=1)
-        if self.dropout is not None:
-            y = self.dropout(y)
-        return _unfused_pool(y, pool) if pool else y
 
 
 class ChebyKANConv1DLayer(ChebyKANConvNDLayer):

@@ -20,7 +20,7 @@ import torch.nn as nn
 
 from .. import _lib as L
 from .. import ops
-from .conv_layers import _HipLayer, _act_code, _check_groups, _filter_norm_kwargs, _fusable_instnorm, _need_conv2d
+from .conv_layers import _HipLayer, _act_code, _channel_major, _check_groups
 
 
 class GRAMKANConvNDLayer(_HipLayer):
@@ -43,46 +43,21 @@ class GRAMKANConvNDLayer(_HipLayer):
             raise NotImplementedError(f"GRAM-KAN on the HIP path needs 1 <= degree <= {L.KAN_MAX_PLANES - 2}")
         if not isinstance(kernel_size, int):
             raise TypeError("GRAM-KAN takes an int kernel_size (gram_kan_layers.py:132-133,146)")
-        cg, og = input_dim // groups, output_dim // groups
-        self.base_conv = nn.ModuleList([conv_class(cg, og, kernel_size, stride, padding, dilation, groups=1, bias=False)
-                                        for _ in range(groups)])
-        self.layer_norm = nn.ModuleList([norm_class(og, **_filter_norm_kwargs(norm_class, norm_kwargs)) for _ in range(groups)])
-        self.poly_weights = nn.Parameter(torch.randn(groups, og, cg * (degree + 1), *([kernel_size] * ndim)))
+        self._build(conv_class, norm_class, input_dim // groups, output_dim // groups, plane_major=degree + 1)
         self.beta_weights = nn.Parameter(torch.zeros(degree + 1, dtype=torch.float32))
-        for conv in self.base_conv:
-            nn.init.kaiming_uniform_(conv.weight, nonlinearity='linear')
         nn.init.kaiming_uniform_(self.poly_weights, nonlinearity='linear')
         nn.init.normal_(self.beta_weights, mean=0.0, std=1.0 / ((kernel_size ** ndim) * input_dim * (degree + 1.0)))
         # c_k = beta(k-1, k) = factor[k] * beta_weights[k-1]; the factor is the reference's Python-float expression (:150-153)
         fac = [0.0, 0.0] + [((2 * i - 1) * 1 * (i - 1) ** 2) / (i ** 2 / (4.0 * (i - 1) ** 2 - 1.0)) for i in range(2, degree + 1)]
         self.register_buffer("_beta_factor", torch.tensor(fac, dtype=torch.float32), persistent=False)
 
-    def conv_spec(self) -> ops.ConvSpec:
-        return self._spec(kind=L.BASIS_GRAM, n_basis=self.degree + 1, order=0, act=_act_code(self.base_activation), p0=0.0, p1=0.0,
-                          table=())
+    def _basis_kw(self):
+        return dict(kind=L.BASIS_GRAM, n_basis=self.degree + 1, order=0, act=_act_code(self.base_activation), p0=0.0, p1=0.0, table=())
 
     def forward(self, x):
-        G, n = self.groups, self.degree + 1
-        og, cg, k = self.output_dim // G, self.input_dim // G, self.kernel_size
         coef = self._beta_factor * torch.cat([self.beta_weights.new_zeros(1), self.beta_weights[:-1]])      # coef[k] = c_k
-        # plane-major (k*C + c) -> the kernels' channel-major (c*n + k) order; autograd carries the gradient back
-        ws = [self.poly_weights[g].view(og, n, cg, k, k).transpose(1, 2).reshape(og, cg * n, k, k) for g in range(G)]
-        z = ops.kan_conv_phased(self.conv_spec(), x, coef, [m.weight for m in self.base_conv], ws)
-        if _fusable_instnorm(self.layer_norm):
-            gam, bet = self._norm_affine(self.layer_norm)
-            y = ops.instance_norm(z, torch.cat(gam) if gam is not None else None, torch.cat(bet) if bet is not None else None,
-                                  eps=self.layer_norm[0].eps)
-        else:
-            parts = []
-            for g in range(G):
-                zg = z[:, g * og:(g + 1) * og]
-                if isinstance(self.layer_norm[g], nn.LayerNorm):
-                    zg = self.layer_norm[g](zg.reshape(zg.shape[0], -1)).view(zg.shape)
-                else:
-                    zg = self.layer_norm[g](zg)
-                parts.append(zg)
-            y = torch.cat(parts, dim=1)
-        return self.base_activation(y)
+        z = ops.kan_conv_phased(self.conv_spec(), x, coef, [m.weight for m in self.base_conv], _channel_major(self.poly_weights, self.degree + 1))
+        return self._norm_act(z)
 
 
 class GRAMKANConv2DLayer(GRAMKANConvNDLayer):

@@ -29,8 +29,7 @@ import torch.nn as nn
 
 from .. import _lib as L
 from .. import ops
-from .conv_layers import (_HipLayer, _act_code, _check_groups, _dropout2d, _filter_norm_kwargs, _fusable_instnorm, _norm3d, _unfused_pool,
-                          conv3d_stage)
+from .conv_layers import _FusedTailLayer, _HipLayer, _act_code, _channel_major, _check_groups, _dropout2d
 from .conv_layers import _need_conv2d as _need_conv1d_or_2d
 
 
@@ -49,7 +48,7 @@ def _table(c: Coeffs, n_basis: int) -> Tuple[float, ...]:
     return tuple(out)
 
 
-class _RecurrenceKANConvNDLayer(_HipLayer):
+class _RecurrenceKANConvNDLayer(_FusedTailLayer):
     """Shared body of the seven 'base conv + polynomial conv -> norm -> PReLU' layers."""
     _min_degree = 0
     _min_degree_msg = 'degree must be non-negative'
@@ -66,18 +65,8 @@ class _RecurrenceKANConvNDLayer(_HipLayer):
         self.norm_kwargs = norm_kwargs
         self.input_dim_group, self.output_dim_group = input_dim // groups, output_dim // groups
         self.poly_input_dim_group = self.input_dim_group * self._n_planes()
-        cg, og = self.input_dim_group, self.output_dim_group
-        self.base_conv = nn.ModuleList([conv_class(cg, og, kernel_size, stride, padding, dilation, groups=1, bias=False)
-                                        for _ in range(groups)])
-        self.poly_conv = nn.ModuleList([conv_class(self.poly_input_dim_group, og, kernel_size, stride, padding, dilation, groups=1,
-                                                   bias=False) for _ in range(groups)])
-        self.layer_norm = nn.ModuleList([norm_class(og, **_filter_norm_kwargs(norm_class, norm_kwargs)) for _ in range(groups)])
-        self.prelus = nn.ModuleList([nn.PReLU() for _ in range(groups)])
+        self._build(conv_class, norm_class, self.input_dim_group, self.output_dim_group, "poly_conv", self._n_planes(), prelus=True)
         self.dropout = _dropout2d(dropout, ndim)
-        for conv in self.base_conv:
-            nn.init.kaiming_uniform_(conv.weight, nonlinearity='linear')
-        for conv in self.poly_conv:
-            nn.init.kaiming_uniform_(conv.weight, nonlinearity='linear')
         self._act_code = _act_code(self.base_activation, host_ok=True)
         if self._n_planes() > 11:
             raise NotImplementedError("the HIP recurrence basis holds at most 11 planes per channel (degree <= 10)")
@@ -88,43 +77,9 @@ class _RecurrenceKANConvNDLayer(_HipLayer):
     def _coeffs(self) -> Coeffs:
         raise NotImplementedError
 
-    def conv_spec(self) -> ops.ConvSpec:
-        n = self._n_planes()
-        return self._spec(kind=L.BASIS_POLY, n_basis=n, order=1, act=self._act_code, p0=0.0, p1=0.0, table=_table(self._coeffs(), n))
-
-    def _forward3d(self, x):
-        """[B, C, D, H, W] layers (the ...KANConv3DLayer shims of the reference): each depth tap is one launch set of the 2-D kernels (conv3d_stage)."""
-        n = self._n_planes()                                     # (Taylor: degree planes, not degree + 1 -- same source as conv_spec())
-        kw = dict(kind=L.BASIS_POLY, n_basis=n, order=1, act=self._act_code, p0=0.0, p1=0.0, table=_table(self._coeffs(), n))
-        xa, xb = self._base_input(x)
-        z = conv3d_stage(kw, self.kernel_size, self.stride, self.padding, self.dilation, self.groups, xa, xb,
-                         [m.weight for m in self.base_conv], [m.weight for m in self.poly_conv])
-        y = _norm3d(self.layer_norm, self.prelus, z, self.output_dim_group)
-        return self.dropout(y) if self.dropout is not None else y
-
-    def forward(self, x, pool=False):
-        """`pool` = True or (kernel, stride): max_pool2d(layer(x), ...) with the pooling inside the InstanceNorm+PReLU kernels (see KANConvNDLayer)."""
-        if self.ndim == 3:
-            if pool:
-                raise NotImplementedError("pool=True is a 2-D fusion")
-            return self._forward3d(x)
-        spec = self.conv_spec()
-        x = self._lift(x)
-        wb, ws = self._w(self.base_conv), self._w(self.poly_conv)
-        prelus = [m.weight for m in self.prelus]
-        xa, xb = self._base_input(x)                              # (act(x), x) when the host applies the activation
-        if xb is None and _fusable_instnorm(self.layer_norm) and all(p.numel() == 1 for p in prelus):
-            gam, bet = self._norm_affine(self.layer_norm)
-            if pool and self.dropout is None and self.ndim == 2:
-                ho, wo = spec.out_hw(x.shape[2], x.shape[3])
-                if pool is not True or (ho % 2 == 0 and wo % 2 == 0):
-                    return ops.kan_conv_in_prelu(spec, x, wb, ws, gam, bet, prelus, eps=self.layer_norm[0].eps, pool=pool)
-            y = self._lower(ops.kan_conv_in_prelu(spec, x, wb, ws, gam, bet, prelus, eps=self.layer_norm[0].eps))
-        else:
-            y = self._norm_prelu(ops.kan_conv(spec, xa, xb, wb, ws))
-        if self.dropout is not None:
-            y = self.dropout(y)
-        return _unfused_pool(y, pool) if pool else y
+    def _basis_kw(self):
+        n = self._n_planes()                                     # (Taylor: degree planes, not degree + 1)
+        return dict(kind=L.BASIS_POLY, n_basis=n, order=1, act=self._act_code, p0=0.0, p1=0.0, table=_table(self._coeffs(), n))
 
 
 # ------------------------------------------------------------------------------------------- Bessel
@@ -437,9 +392,11 @@ class TaylorKANConv3DLayer(TaylorKANConvNDLayer):
 
 
 # ------------------------------------------------------------------------------------------- Fourier
-class FourierKANConvNDLayer(_HipLayer):
+class FourierKANConvNDLayer(_FusedTailLayer):
     """fourier_kan_layers.py:63-212: y = Dropout(PReLU(norm(conv(act(x), W_base) + conv([cos(kx)]_k ++ [sin(kx)]_k, W_fourier)))),
     k = 1..grid_size, channel index c*2G + (k-1) for the cosines and c*2G + G + (k-1) for the sines (:184-186)."""
+    _basis = "fourier_conv"
+    pool_types = ()                                              # forward(x), as in the reference: the models leave it un-fused
 
     def __init__(self, conv_class, norm_class, input_dim, output_dim, kernel_size, grid_size, groups=1, padding=0, stride=1, dilation=1,
                  ndim: int = 2, base_activation=nn.GELU, dropout: float = 0.0, smooth_initialization: bool = False, **norm_kwargs):
@@ -456,47 +413,15 @@ class FourierKANConvNDLayer(_HipLayer):
         self.norm_kwargs = norm_kwargs
         self.input_dim_group, self.output_dim_group = input_dim // groups, output_dim // groups
         self.fourier_input_dim_group = self.input_dim_group * (2 * grid_size)
-        cg, og = self.input_dim_group, self.output_dim_group
-        self.base_conv = nn.ModuleList([conv_class(cg, og, kernel_size, stride, padding, dilation, groups=1, bias=False)
-                                        for _ in range(groups)])
-        self.fourier_conv = nn.ModuleList([conv_class(self.fourier_input_dim_group, og, kernel_size, stride, padding, dilation, groups=1,
-                                                      bias=False) for _ in range(groups)])
-        self.layer_norm = nn.ModuleList([norm_class(og, **_filter_norm_kwargs(norm_class, norm_kwargs)) for _ in range(groups)])
-        self.prelus = nn.ModuleList([nn.PReLU() for _ in range(groups)])
+        self._build(conv_class, norm_class, self.input_dim_group, self.output_dim_group, "fourier_conv", 2 * grid_size, prelus=True)
         self.dropout = _dropout2d(dropout, ndim)
-        for conv in self.base_conv:
-            nn.init.kaiming_uniform_(conv.weight, nonlinearity='linear')
-        for conv in self.fourier_conv:
-            nn.init.kaiming_uniform_(conv.weight, nonlinearity='linear')
         self._act_code = _act_code(self.base_activation, host_ok=True)
 
-    def conv_spec(self) -> ops.ConvSpec:
-        return self._spec(kind=L.BASIS_FOURIER, n_basis=2 * self.grid_size, order=0, act=self._act_code, p0=0.0, p1=0.0, table=())
-
-    def _forward3d(self, x):
-        kw = dict(kind=L.BASIS_FOURIER, n_basis=2 * self.grid_size, order=0, act=self._act_code, p0=0.0, p1=0.0, table=())
-        xa, xb = self._base_input(x)
-        z = conv3d_stage(kw, self.kernel_size, self.stride, self.padding, self.dilation, self.groups, xa, xb,
-                         [m.weight for m in self.base_conv], [m.weight for m in self.fourier_conv])
-        y = _norm3d(self.layer_norm, self.prelus, z, self.output_dim_group)
-        return self.dropout(y) if self.dropout is not None else y
+    def _basis_kw(self):
+        return dict(kind=L.BASIS_FOURIER, n_basis=2 * self.grid_size, order=0, act=self._act_code, p0=0.0, p1=0.0, table=())
 
     def forward(self, x):
-        if self.ndim == 3:
-            return self._forward3d(x)
-        spec = self.conv_spec()
-        x = self._lift(x)
-        wb, ws = self._w(self.base_conv), self._w(self.fourier_conv)
-        prelus = [m.weight for m in self.prelus]
-        xa, xb = self._base_input(x)                              # (act(x), x) when the host applies the activation
-        if xb is None and _fusable_instnorm(self.layer_norm) and all(p.numel() == 1 for p in prelus):
-            gam, bet = self._norm_affine(self.layer_norm)
-            y = self._lower(ops.kan_conv_in_prelu(spec, x, wb, ws, gam, bet, prelus, eps=self.layer_norm[0].eps))
-        else:
-            y = self._norm_prelu(ops.kan_conv(spec, xa, xb, wb, ws))
-        if self.dropout is not None:
-            y = self.dropout(y)
-        return y
+        return super().forward(x)
 
 
 class FourierKANConv2DLayer(FourierKANConvNDLayer):
@@ -527,8 +452,32 @@ class FourierKANConv3DLayer(FourierKANConvNDLayer):
                          ndim=3, base_activation=base_activation, dropout=dropout, **norm_kwargs)
 
 
-# ------------------------------------------------------------------------------------------- Jacobi
-class JacobiKANConvNDLayer(_HipLayer):
+# ------------------------------------------------------------------------------------------- Jacobi / Legendre / Bernstein
+class _PlaneMajorPolyLayer(_HipLayer):
+    """Common body of the 'torchkan-style' conv layers (jacobi / legendre / bersnstein _kan_layers.py): identity base branch,
+    one ``poly_weights`` parameter [G, O/G, C/G*(degree+1), k, k], output = base_activation(norm(base + poly)) (`_norm_act`)."""
+
+    def _setup_pm(self, conv_class, norm_class, conv_w_fun, input_dim, output_dim, degree, kernel_size, base_activation, groups, padding,
+                  stride, dilation, dropout, ndim, norm_kwargs, name="this layer", jacobi_init=False):
+        _need_conv2d(conv_class, ndim)
+        self.degree, self.kernel_size = degree, kernel_size
+        self.padding, self.stride, self.dilation, self.groups = padding, stride, dilation, groups
+        self.base_activation = base_activation
+        self.conv_w_fun, self.ndim, self.norm_kwargs = conv_w_fun, ndim, norm_kwargs
+        self.dropout = _dropout2d(dropout)
+        _check_groups(groups, input_dim, output_dim)
+        if degree < 1 or degree > 10:
+            raise NotImplementedError(f"{name} on the HIP path needs 1 <= degree <= 10")
+        if not isinstance(kernel_size, int):
+            raise TypeError(f"{name} takes an int kernel_size (the reference builds poly_weights from `kernel_size` repeated ndim times)")
+        self._build(conv_class, norm_class, input_dim // groups, output_dim // groups, plane_major=degree + 1)
+        if jacobi_init:                                          # jacobi_kan_layers.py:116
+            nn.init.normal_(self.poly_weights, mean=0.0, std=1 / (input_dim * (degree + 1) * kernel_size ** ndim))
+        else:
+            nn.init.kaiming_uniform_(self.poly_weights, nonlinearity='linear')
+
+
+class JacobiKANConvNDLayer(_PlaneMajorPolyLayer):
     """jacobi_kan_layers.py:55-175: y = act(norm(conv(x, W_base) + conv(P(tanh x), poly_weights[g]))), the polynomial planes
     concatenated PLANE-major (channel index k*C + c, :136) and the activation applied after the norm (:165)."""
 
@@ -536,28 +485,13 @@ class JacobiKANConvNDLayer(_HipLayer):
                  a: float = 1.0, b: float = 1.0, groups=1, padding=0, stride=1, dilation=1, dropout: float = 0.0, ndim: int = 2,
                  **norm_kwargs):
         super().__init__()
-        _need_conv2d(conv_class, ndim)
-        self.input_dim, self.output_dim, self.degree, self.kernel_size = input_dim, output_dim, degree, kernel_size
-        self.padding, self.stride, self.dilation, self.groups = padding, stride, dilation, groups
-        self.base_activation = base_activation() if base_activation is not None else nn.Identity()
-        self.conv_w_fun, self.ndim, self.norm_kwargs, self.a, self.b = conv_w_fun, ndim, norm_kwargs, a, b
-        self.dropout = None
+        self.input_dim, self.output_dim, self.a, self.b = input_dim, output_dim, a, b
         if dropout > 0:
             raise NotImplementedError("JacobiKAN applies dropout to the expanded basis planes (jacobi_kan_layers.py:148-149); "
                                       "the fused conv stage never materialises them -- use dropout=0")
-        _check_groups(groups, input_dim, output_dim)
-        if degree < 1 or degree > 10:
-            raise NotImplementedError("JacobiKAN on the HIP path needs 1 <= degree <= 10")
-        if not isinstance(kernel_size, int):
-            raise TypeError("JacobiKAN takes an int kernel_size (jacobi_kan_layers.py:108-109,116)")
-        cg, og = input_dim // groups, output_dim // groups
-        self.base_conv = nn.ModuleList([conv_class(cg, og, kernel_size, stride, padding, dilation, groups=1, bias=False)
-                                        for _ in range(groups)])
-        self.layer_norm = nn.ModuleList([norm_class(og, **_filter_norm_kwargs(norm_class, norm_kwargs)) for _ in range(groups)])
-        self.poly_weights = nn.Parameter(torch.randn(groups, og, cg * (degree + 1), *([kernel_size] * ndim)))
-        for conv in self.base_conv:
-            nn.init.kaiming_uniform_(conv.weight, nonlinearity='linear')
-        nn.init.normal_(self.poly_weights, mean=0.0, std=1 / (input_dim * (degree + 1) * kernel_size ** ndim))
+        self._setup_pm(conv_class, norm_class, conv_w_fun, input_dim, output_dim, degree, kernel_size,
+                       base_activation() if base_activation is not None else nn.Identity(), groups, padding, stride, dilation, 0.0,
+                       ndim, norm_kwargs, name="JacobiKAN", jacobi_init=True)
 
     def _coeffs(self) -> Coeffs:
         a, b = float(self.a), float(self.b)
@@ -569,31 +503,13 @@ class JacobiKANConvNDLayer(_HipLayer):
             rec.append((th, th1, -th2))
         return 1.0, (a + b + 2.0) / 2.0, (a - b) / 2.0, rec
 
-    def conv_spec(self) -> ops.ConvSpec:
+    def _basis_kw(self):
         n = self.degree + 1
-        return self._spec(kind=L.BASIS_POLY, n_basis=n, order=1, act=L.ACT_IDENTITY, p0=0.0, p1=0.0, table=_table(self._coeffs(), n))
+        return dict(kind=L.BASIS_POLY, n_basis=n, order=1, act=L.ACT_IDENTITY, p0=0.0, p1=0.0, table=_table(self._coeffs(), n))
 
     def forward(self, x):
-        G, n = self.groups, self.degree + 1
-        og, cg, k = self.output_dim // G, self.input_dim // G, self.kernel_size
-        # plane-major (k*C + c) -> the kernels' channel-major (c*n + k) order; autograd carries the gradient back
-        ws = [self.poly_weights[g].view(og, n, cg, k, k).transpose(1, 2).reshape(og, cg * n, k, k) for g in range(G)]
-        z = ops.kan_conv(self.conv_spec(), x, None, [m.weight for m in self.base_conv], ws)
-        if _fusable_instnorm(self.layer_norm):
-            gam, bet = self._norm_affine(self.layer_norm)
-            y = ops.instance_norm(z, torch.cat(gam) if gam is not None else None, torch.cat(bet) if bet is not None else None,
-                                  eps=self.layer_norm[0].eps)
-        else:
-            parts = []
-            for g in range(G):
-                zg = z[:, g * og:(g + 1) * og]
-                if isinstance(self.layer_norm[g], nn.LayerNorm):
-                    zg = self.layer_norm[g](zg.reshape(zg.shape[0], -1)).view(zg.shape)
-                else:
-                    zg = self.layer_norm[g](zg)
-                parts.append(zg)
-            y = torch.cat(parts, dim=1)
-        return self.base_activation(y)
+        z = ops.kan_conv(self.conv_spec(), x, None, [m.weight for m in self.base_conv], _channel_major(self.poly_weights, self.degree + 1))
+        return self._norm_act(z)
 
 
 class JacobiKANConv2DLayer(JacobiKANConvNDLayer):
@@ -602,52 +518,6 @@ class JacobiKANConv2DLayer(JacobiKANConvNDLayer):
         super().__init__(conv_class=nn.Conv2d, norm_class=norm_layer, conv_w_fun=torch.nn.functional.conv2d, input_dim=input_dim,
                          output_dim=output_dim, degree=degree, kernel_size=kernel_size, base_activation=base_activation, a=a, b=b,
                          groups=groups, padding=padding, stride=stride, dilation=dilation, ndim=2, dropout=dropout, **norm_kwargs)
-
-
-# ------------------------------------------------------------------------------------------- Legendre / Bernstein
-class _PlaneMajorPolyLayer(_HipLayer):
-    """Common body of the 'torchkan-style' conv layers (legendre / bersnstein / jacobi _kan_layers.py): identity base branch,
-    one ``poly_weights`` parameter [G, O/G, C/G*(degree+1), k, k], output = base_activation(norm(base + poly))."""
-
-    def _setup_pm(self, conv_class, norm_class, conv_w_fun, input_dim, output_dim, degree, kernel_size, base_activation, groups, padding,
-                  stride, dilation, dropout, ndim, norm_kwargs):
-        _need_conv2d(conv_class, ndim)
-        self.degree, self.kernel_size = degree, kernel_size
-        self.padding, self.stride, self.dilation, self.groups = padding, stride, dilation, groups
-        self.base_activation = base_activation
-        self.conv_w_fun, self.ndim, self.norm_kwargs = conv_w_fun, ndim, norm_kwargs
-        self.dropout = _dropout2d(dropout)
-        _check_groups(groups, input_dim, output_dim)
-        if degree < 1 or degree > 10:
-            raise NotImplementedError("this layer on the HIP path needs 1 <= degree <= 10")
-        if not isinstance(kernel_size, int):
-            raise TypeError("an int kernel_size is required (the reference builds poly_weights from `kernel_size` repeated ndim times)")
-        cg, og = input_dim // groups, output_dim // groups
-        self.base_conv = nn.ModuleList([conv_class(cg, og, kernel_size, stride, padding, dilation, groups=1, bias=False)
-                                        for _ in range(groups)])
-        self.layer_norm = nn.ModuleList([norm_class(og, **_filter_norm_kwargs(norm_class, norm_kwargs)) for _ in range(groups)])
-        self.poly_weights = nn.Parameter(torch.randn(groups, og, cg * (degree + 1), *([kernel_size] * ndim)))
-        for conv in self.base_conv:
-            nn.init.kaiming_uniform_(conv.weight, nonlinearity='linear')
-        nn.init.kaiming_uniform_(self.poly_weights, nonlinearity='linear')
-
-    def _norm_act(self, z, og):
-        G = self.groups
-        if _fusable_instnorm(self.layer_norm):
-            gam, bet = self._norm_affine(self.layer_norm)
-            y = ops.instance_norm(z, torch.cat(gam) if gam is not None else None, torch.cat(bet) if bet is not None else None,
-                                  eps=self.layer_norm[0].eps)
-        else:
-            parts = []
-            for g in range(G):
-                zg = z[:, g * og:(g + 1) * og]
-                if isinstance(self.layer_norm[g], nn.LayerNorm):
-                    zg = self.layer_norm[g](zg.reshape(zg.shape[0], -1)).view(zg.shape)
-                else:
-                    zg = self.layer_norm[g](zg)
-                parts.append(zg)
-            y = torch.cat(parts, dim=1)
-        return self.base_activation(y)
 
 
 class LegendreKANConvNDLayer(_PlaneMajorPolyLayer):
@@ -663,23 +533,22 @@ class LegendreKANConvNDLayer(_PlaneMajorPolyLayer):
         self._setup_pm(conv_class, norm_class, conv_w_fun, input_dim, output_dim, degree, kernel_size, nn.SiLU(), groups, padding, stride,
                        dilation, dropout, ndim, norm_kwargs)
 
-    def conv_spec(self) -> ops.ConvSpec:
+    def _basis_kw(self):
         n = self.degree + 1     # P_{k} = ((2k-1) x P_{k-1} - (k-1) P_{k-2}) / k   (legendre_kan_layers.py:119-122)
         c = (1.0, 1.0, 0.0, [((2.0 * k - 1.0) / k, 0.0, -(k - 1.0) / k) for k in range(2, n)])
-        return self._spec(kind=L.BASIS_POLY, n_basis=n, order=0, act=L.ACT_IDENTITY, p0=0.0, p1=0.0, table=_table(c, n))
+        return dict(kind=L.BASIS_POLY, n_basis=n, order=0, act=L.ACT_IDENTITY, p0=0.0, p1=0.0, table=_table(c, n))
 
     def forward(self, x):
-        G, n = self.groups, self.degree + 1
-        og, cg, k = self.output_dim // G, self.input_dim // G, self.kernel_size
+        G, cg = self.groups, self.input_dim // self.groups
         B, _, H, W = x.shape
         xg = x.reshape(B, G, cg, H, W)
         lo, hi = xg.amin(dim=(0, 2, 3, 4), keepdim=True), xg.amax(dim=(0, 2, 3, 4), keepdim=True)
         xn = (2 * (xg - lo) / (hi - lo) - 1).reshape(B, G * cg, H, W)
         if self.dropout is not None:
             xn = self.dropout(xn)
-        ws = [self.poly_weights[g].view(og, n, cg, k, k).transpose(1, 2).reshape(og, cg * n, k, k) for g in range(G)]
-        z = ops.kan_conv(self.conv_spec(), x, xn.contiguous(), [m.weight for m in self.base_conv], ws)
-        return self._norm_act(z, og)
+        z = ops.kan_conv(self.conv_spec(), x, xn.contiguous(), [m.weight for m in self.base_conv],
+                         _channel_major(self.poly_weights, self.degree + 1))
+        return self._norm_act(z)
 
 
 class LegendreKANConv2DLayer(LegendreKANConvNDLayer):
@@ -704,16 +573,14 @@ class BersnsteinKANConvNDLayer(_PlaneMajorPolyLayer):
                        base_activation() if base_activation is not None else nn.Identity(), groups, padding, stride, dilation, dropout,
                        ndim, norm_kwargs)
 
-    def conv_spec(self) -> ops.ConvSpec:
+    def _basis_kw(self):
         n = self.degree + 1
         c = (1.0, 0.0, 1.0, [(0.0, 1.0, 0.0) for _ in range(2, n)])          # T_k == 1, dT_k/dx == 0
-        return self._spec(kind=L.BASIS_POLY, n_basis=n, order=1, act=L.ACT_IDENTITY, p0=0.0, p1=0.0, table=_table(c, n))
+        return dict(kind=L.BASIS_POLY, n_basis=n, order=1, act=L.ACT_IDENTITY, p0=0.0, p1=0.0, table=_table(c, n))
 
     def forward(self, x):
-        G = self.groups
-        og = self.outdim // G
-        z = ops.kan_conv(self.conv_spec(), x, None, [m.weight for m in self.base_conv], [self.poly_weights[g] for g in range(G)])
-        return self._norm_act(z, og)
+        z = ops.kan_conv(self.conv_spec(), x, None, [m.weight for m in self.base_conv], [self.poly_weights[g] for g in range(self.groups)])
+        return self._norm_act(z)
 
 
 class BersnsteinKANConv2DLayer(BersnsteinKANConvNDLayer):

@@ -20,7 +20,7 @@ import torch.nn as nn
 
 from .. import _lib as L
 from .. import ops
-from .conv_layers import _HipLayer, _act_code, _check_groups, _dropout2d, _filter_norm_kwargs, _fusable_instnorm, _need_conv2d
+from .conv_layers import _HipLayer, _act_code, _check_groups, _dropout2d, _need_conv2d
 
 
 class ReLUConvNDLayer(_HipLayer):
@@ -41,51 +41,26 @@ class ReLUConvNDLayer(_HipLayer):
         if g + k + 1 > L.KAN_MAX_PLANES:
             raise NotImplementedError(f"g + k + 1 = {g + k + 1} planes per channel exceed KAN_MAX_PLANES = {L.KAN_MAX_PLANES}")
         cg, og = input_dim // groups, output_dim // groups
-        self.base_conv = nn.ModuleList([conv_class(cg, og, kernel_size, stride, padding, dilation, groups=1, bias=False)
-                                        for _ in range(groups)])
-        self.relukan_conv = nn.ModuleList([conv_class((g + k) * cg, og, kernel_size, stride, padding, dilation, groups=1, bias=False)
-                                           for _ in range(groups)])
+        self._build(conv_class, norm_class, cg, og, "relukan_conv", g + k)
         phase_low = torch.arange(-k, g) / g                      # relu_kan_layers.py:97-98
         phase_high = phase_low + (k + 1) / g
         dims = (1, cg, k + g) + (1,) * ndim
         self.phase_low = nn.Parameter(phase_low[None, :].expand(cg, -1).reshape(*dims).clone(), requires_grad=train_ab)
         self.phase_high = nn.Parameter(phase_high[None, :].expand(cg, -1).reshape(*dims).clone(), requires_grad=train_ab)
-        self.layer_norm = nn.ModuleList([norm_class(og, **_filter_norm_kwargs(norm_class, norm_kwargs)) for _ in range(groups)])
-        for conv in self.base_conv:
-            nn.init.kaiming_uniform_(conv.weight, nonlinearity='linear')
-        for conv in self.relukan_conv:
-            nn.init.kaiming_uniform_(conv.weight, nonlinearity='linear')
 
-    def conv_spec(self) -> ops.ConvSpec:
-        return self._spec(kind=L.BASIS_RELU, n_basis=self.g + self.k, order=0, act=_act_code(self.base_activation, host_ok=True), p0=float(self.r),
-                          p1=0.0, table=())
+    def _basis_kw(self):
+        return dict(kind=L.BASIS_RELU, n_basis=self.g + self.k, order=0, act=_act_code(self.base_activation, host_ok=True), p0=float(self.r),
+                    p1=0.0, table=())
 
     def forward(self, x):
-        G, n = self.groups, self.g + self.k
-        cg, og = self.input_dim // G, self.output_dim // G
+        cg, n = self.input_dim // self.groups, self.g + self.k
         if self.dropout is not None:
             x = self.dropout(x)                                  # relu_kan_layers.py:120-121: on the input, both branches see it
         phases = torch.stack([self.phase_low.reshape(cg, n), self.phase_high.reshape(cg, n)], dim=1)
         xa, xb = self._base_input(x)                              # (act(x), x) when the host applies the activation (no device functor for the module)
         z = ops.kan_conv_phased(self.conv_spec(), self._lift(xa), phases, self._w(self.base_conv), self._w(self.relukan_conv),
                                 xn=self._lift(xb) if xb is not None else None)
-        if _fusable_instnorm(self.layer_norm):
-            gam, bet = self._norm_affine(self.layer_norm)
-            y = ops.instance_norm(z, torch.cat(gam) if gam is not None else None, torch.cat(bet) if bet is not None else None,
-                                  eps=self.layer_norm[0].eps)
-            y = self._lower(y)
-        else:
-            z = self._lower(z)
-            parts = []
-            for gi in range(G):
-                zg = z[:, gi * og:(gi + 1) * og]
-                if isinstance(self.layer_norm[gi], nn.LayerNorm):
-                    zg = self.layer_norm[gi](zg.reshape(zg.shape[0], -1)).view(zg.shape)
-                else:
-                    zg = self.layer_norm[gi](zg)
-                parts.append(zg)
-            y = torch.cat(parts, dim=1)
-        return self.base_activation(y)
+        return self._norm_act(z)
 
 
 class ReLUKANConv2DLayer(ReLUConvNDLayer):

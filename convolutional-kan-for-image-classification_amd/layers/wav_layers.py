@@ -20,7 +20,7 @@ import torch.nn.functional as F
 from .. import _lib as L
 from .. import ops
 
-from .conv_layers import _HipLayer, _check_groups, _dropout2d, _filter_norm_kwargs, _fusable_instnorm, _norm3d, conv3d_stage
+from .conv_layers import _HipLayer, _check_groups, _dropout2d, _filter_norm_kwargs, _fusable_instnorm, _gamma_beta, _norm3d, conv3d_stage
 
 WAVELET_TYPES = ('mexican_hat', 'morlet', 'dog', 'meyer', 'shannon')
 
@@ -172,10 +172,13 @@ class WavKANConvNDLayer(_HipLayer):
         self.register_buffer("_zero_base", torch.zeros(groups, og, cg, *((1,) if ndim == 1 else ()), *self.base_conv[0].weight.shape[2:]), persistent=False)
         self.register_buffer("_zero_out", torch.zeros(groups, og, og, 1, 1), persistent=False)
 
-    def _const_plane_spec(self, act: int, kernel, stride, padding, dilation) -> ops.ConvSpec:
+    @staticmethod
+    def _basis_kw(act: int = L.ACT_SILU):
         """act(x) conv W + (constant plane) conv 0: a plain convolution on the KAN conv kernels."""
-        return ops.ConvSpec(kind=L.BASIS_POLY, n_basis=1, order=0, act=act, p0=0.0, p1=0.0, table=(1.0, 0.0, 0.0),
-                            kernel=kernel, stride=stride, padding=padding, dilation=dilation, groups=self.groups)
+        return dict(kind=L.BASIS_POLY, n_basis=1, order=0, act=act, p0=0.0, p1=0.0, table=(1.0, 0.0, 0.0))
+
+    def _const_plane_spec(self, act: int, kernel, stride, padding, dilation) -> ops.ConvSpec:
+        return ops.ConvSpec(kernel=kernel, stride=stride, padding=padding, dilation=dilation, groups=self.groups, **self._basis_kw(act))
 
     def conv_spec(self) -> ops.ConvSpec:
         """Spec of the base-conv launch (geometry queries: out_hw)."""
@@ -185,8 +188,7 @@ class WavKANConvNDLayer(_HipLayer):
     def _forward3d(self, x):
         G, og = self.groups, self.output_dim_group
         cg = self.inputdim // G
-        base = conv3d_stage(dict(kind=L.BASIS_POLY, n_basis=1, order=0, act=L.ACT_SILU, p0=0.0, p1=0.0, table=(1.0, 0.0, 0.0)), self.kernel_size,
-                            self.stride, self.padding, self.dilation, G, x, None, [m.weight for m in self.base_conv], [self._zero_base[g] for g in range(G)])
+        base = conv3d_stage(self._basis_kw(), self.kernel_size, self.stride, self.padding, self.dilation, G, x, None, [m.weight for m in self.base_conv], [self._zero_base[g] for g in range(G)])
         xd = self.dropout(x) if self.dropout is not None else x
         us = [self.wavelet_conv[g].stage3d(xd[:, g * cg:(g + 1) * cg]) for g in range(G)]
         u = us[0] if G == 1 else torch.cat(us, dim=1)
@@ -211,9 +213,7 @@ class WavKANConvNDLayer(_HipLayer):
         mixed = ops.kan_conv(self._const_plane_spec(L.ACT_IDENTITY, (1, 1), (1, 1), (0, 0), (1, 1)), u, None, w_out, [self._zero_out[g] for g in range(G)])
         z = mixed + base
         if _fusable_instnorm(self.layer_norm):
-            gam = torch.cat([m.weight for m in self.layer_norm]) if self.layer_norm[0].affine else None
-            bet = torch.cat([m.bias for m in self.layer_norm]) if self.layer_norm[0].affine else None
-            return self._lower(ops.instance_norm(z, gam, bet, eps=self.layer_norm[0].eps))
+            return self._lower(ops.instance_norm(z, *_gamma_beta(self.layer_norm), eps=self.layer_norm[0].eps))
         z = self._lower(z)
         parts = [self.layer_norm[g](z[:, g * og:(g + 1) * og]) for g in range(G)]
         return parts[0] if G == 1 else torch.cat(parts, dim=1)

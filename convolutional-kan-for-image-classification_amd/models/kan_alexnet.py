@@ -8,8 +8,7 @@ from typing import Any, Callable, List, Optional
 import torch
 import torch.nn as nn
 
-from ..layers.conv_layers import ChebyKANConvNDLayer, KANConvNDLayer
-from ..layers.poly_layers import _RecurrenceKANConvNDLayer
+from ..layers.conv_layers import _HipLayer
 from ..layers.kan_conv import CONV_KAN_FACTORY
 from ..layers.mlp_layers import MLP_KAN_FACTORY
 
@@ -90,7 +89,7 @@ class AlexNetKAN(nn.Module):
             m = mods[i]
             nxt = mods[i + 1] if i + 1 < len(mods) else None
             ks = _plain_pool(nxt) if (self.fuse_pool and isinstance(nxt, nn.MaxPool2d)) else None
-            if ks is not None and isinstance(m, (KANConvNDLayer, ChebyKANConvNDLayer, _RecurrenceKANConvNDLayer)) and getattr(m, "ndim", 2) == 2:
+            if ks is not None and isinstance(m, _HipLayer) and m.takes_pool(ks):
                 x = m(x, pool=ks)
                 i += 2
             else:

@@ -15,8 +15,7 @@ from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 import torch
 import torch.nn as nn
 
-from ..layers.conv_layers import KANConvNDLayer
-from ..layers.poly_layers import _RecurrenceKANConvNDLayer
+from ..layers.conv_layers import _HipLayer
 from ..layers.kan_conv import CONV_KAN_FACTORY
 from ..layers.mlp_layers import MLP_KAN_FACTORY
 
@@ -104,7 +103,7 @@ class VGGKAN(nn.Module):
         while i < len(mods):
             m = mods[i]
             nxt = mods[i + 1] if i + 1 < len(mods) else None
-            if (self.fuse_pool and isinstance(m, (KANConvNDLayer, _RecurrenceKANConvNDLayer)) and getattr(m, "ndim", 2) == 2
+            if (self.fuse_pool and isinstance(m, _HipLayer) and m.takes_pool(True)
                     and isinstance(nxt, nn.MaxPool2d) and _is_pool_2x2(nxt)):
                 x = m(x, pool=True)
                 i += 2

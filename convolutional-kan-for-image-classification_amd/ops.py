@@ -673,9 +673,9 @@ class _KanConvInPrelu(torch.autograd.Function):
             # that the S-slab buffer can be freed (was: summed in place into slab 0, then cloned out of the buffer)
             z = zs[0] if S == 1 else torch.empty((B, Ot, Ho, Wo), device=x.device, dtype=torch.float32)
             pidx = None
-            if pool and pool is not True and tuple(pool) == (2, 2) and Ho % 2 == 0 and Wo % 2 == 0:
+            if pool == (2, 2) and pool_fusable(True, Ho, Wo):
                 pool = True                              # even planes: the register-resident 2x2 kernels
-            if pool and pool is not True:                # MaxPool2d(k, s), overlapping windows (the AlexNet pattern 3, 2): generic norm kernels
+            if isinstance(pool, tuple):                  # MaxPool2d(k, s), overlapping windows (the AlexNet pattern 3, 2): generic norm kernels
                 pk, ps = pool
                 if Ho < pk or Wo < pk:
                     raise L.KanConvError(f"fused {pk}x{pk} max-pool on a {Ho}x{Wo} plane")
@@ -686,7 +686,7 @@ class _KanConvInPrelu(torch.autograd.Function):
                                                          _ptr(y), C.c_void_p(pidx.data_ptr()), _ptr(mean), _ptr(rstd), B, Ot, Ho, Wo,
                                                          Ot * HW, eps, Og if G > 1 else 0, pk, ps, _stream(x)), "kan_instnorm_prelu_poolk_fwd")
             elif pool:                                   # MaxPool2d(2, 2) fused behind the PReLU: the full-size y is never written
-                if Ho % 2 or Wo % 2:
+                if not pool_fusable(True, Ho, Wo):
                     raise L.KanConvError(f"fused 2x2 max-pool needs an even plane, got {Ho}x{Wo}")
                 y = torch.empty((B, Ot, Ho // 2, Wo // 2), device=x.device, dtype=torch.float32)
                 pidx = torch.empty((B, Ot, Ho // 2, Wo // 2), device=x.device, dtype=torch.uint8)
@@ -729,7 +729,7 @@ class _KanConvInPrelu(torch.autograd.Function):
             dgam = torch.zeros_like(gamma) if use_affine else None
             dbet = torch.zeros_like(beta) if use_affine else None
             dpre = torch.zeros_like(slope) if use_prelu else None
-            if pool and pool is not True:
+            if isinstance(pool, tuple):
                 L.check(lib.kan_instnorm_prelu_poolk_bwd(_ptr(dy), C.c_void_p(pidx.data_ptr()), _ptr(z), _ptr(mean), _ptr(rstd), _ptr(gamma),
                                                          _ptr(beta), _ptr(slope), _ptr(dz), _ptr(dgam), _ptr(dbet), _ptr(dpre), B, Ot, Ho, Wo,
                                                          Ot * HW, Og if G > 1 else 0, pool[0], pool[1], _stream(x)), "kan_instnorm_prelu_poolk_bwd")
@@ -887,8 +887,15 @@ def kan_conv_phased(spec: ConvSpec, x: torch.Tensor, phases: torch.Tensor, w_bas
     return _KanConvPhased.apply(spec, x, xn, phases, *ws)
 
 
+def pool_fusable(pool, ho: int, wo: int) -> bool:
+    """THE rule for whether the InstanceNorm(+PReLU) kernels can apply the max-pool `pool` to a ho x wo plane: a (k, s) window always
+    (the generic kernels), True = MaxPool2d(2, 2) only on an even plane (the register-resident 2x2 kernels).  The layers ask before they
+    request a fused pool; `_KanConvInPrelu` refuses a request that breaks it."""
+    return pool is not True or (ho % 2 == 0 and wo % 2 == 0)
+
+
 def _norm_pool(pool):
-    """False | True (= the even-plane 2x2 kernels) | (k, s)."""
+    """False | True (= the even-plane 2x2 kernels) | a (k, s) tuple."""
     if pool is True or not pool:
         return bool(pool)
     k, st = int(pool[0]), int(pool[1])

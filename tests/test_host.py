@@ -335,7 +335,7 @@ def test_taylor_3d_shim_sizes_its_basis_like_the_2d_layer():
     lay = K.TaylorKANConv3DLayer(2, 4, 3, degree=3, padding=1)
     assert lay.poly_conv[0].weight.shape[1] == 2 * 3 and lay.conv_spec().n_basis == 3
     seen = {}
-    import convkan_amd.layers.poly_layers as PL
+    import convkan_amd.layers.conv_layers as PL         # the one 3-D body (_FusedTailLayer._forward3d) lives here
     orig = PL.conv3d_stage
     try:
         PL.conv3d_stage = lambda kw, *a, **k: seen.update(kw) or (_ for _ in ()).throw(RuntimeError("stop"))
