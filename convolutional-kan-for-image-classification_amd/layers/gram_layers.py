@@ -10,7 +10,7 @@ Gram polynomials P_0 = 1, P_1 = t, P_k = t P_{k-1} - beta(k-1, k) P_{k-2} with
 beta(n, m) = (m+n)(m-n) n^2 / (m^2 / (4 n^2 - 1)) * beta_weights[n]  (:150-170), planes concatenated PLANE-major (k*C + c)
 and passed through the layer's activation.  ``beta_weights`` is trainable: the coefficients are formed with torch ops on the
 device (no host read-back), handed to the fused conv stage as a device table (KAN_BASIS_GRAM), and their gradient comes from
-the weight-gradient kernel run on the coefficient-derivative planes (ops._KanConvPhased) -- autograd carries it on to
+the weight-gradient kernel run on the coefficient-derivative planes (ops._KanConv) -- autograd carries it on to
 ``beta_weights`` through the constant factors.
 """
 from __future__ import annotations

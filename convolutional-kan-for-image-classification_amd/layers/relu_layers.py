@@ -11,7 +11,7 @@ with g + k planes per channel, channel index c*(g+k)+j, r = 4 g^2 / (k+1)^2, and
 ``phase_high`` of shape (1, C/groups, g+k, 1, 1) that are trainable by default (``train_ab``) and SHARED by the groups.
 The conv stage (forward, input gradient, weight gradient) is the fused HIP kernel with the phases read from device memory
 (KAN_BASIS_RELU); the phase gradients come from two more runs of the weight-gradient kernel on the phase-derivative planes
-(ops._KanConvPhased) -- the expanded tensor the reference materialises never exists.
+(ops._KanConv) -- the expanded tensor the reference materialises never exists.
 """
 from __future__ import annotations
 

@@ -80,6 +80,12 @@ def _plan_cached(spec: ConvSpec, B: int, Cg: int, H: int, W: int, Og: int, C_tot
     return g, b, p
 
 
+def _plan_key(spec: ConvSpec, shape, Og: int) -> tuple:
+    """The `_plan_cached` arguments of a conv stage over an NCHW input of `shape` with `Og` outputs per group."""
+    B, Ct, H, W = shape
+    return (spec, B, Ct // spec.groups, H, W, Og, Ct, Og * spec.groups)
+
+
 def _with_phases(basis: L.KanBasis, phases: Optional[torch.Tensor], mode: int = 0) -> L.KanBasis:
     """Per-call copy of a cached basis struct carrying the device pointer of the ReLU-KAN phase table and the plane mode."""
     if phases is None:
@@ -130,7 +136,9 @@ class KernelSample:
     end: "torch.cuda.Event"
 
 
-def _launch(name: str, flops: float, t: torch.Tensor, fn, executed: Optional[float] = None, layer: str = "") -> None:
+def _launch(sample, t: torch.Tensor, fn) -> None:
+    """Run one conv-kernel launch; `sample` = (name, flops, executed, layer) from `_sample`."""
+    name, flops, executed, layer = sample
     if PROFILE is None:
         L.check(fn(), name)
         return
@@ -139,7 +147,7 @@ def _launch(name: str, flops: float, t: torch.Tensor, fn, executed: Optional[flo
     e0.record(stream)
     L.check(fn(), name)
     e1.record(stream)
-    PROFILE.append(KernelSample(name, flops, flops if executed is None else executed, layer, e0, e1))
+    PROFILE.append(KernelSample(name, flops, executed, layer, e0, e1))
 
 
 def _conv_flops(geom, plan) -> float:
@@ -161,13 +169,16 @@ def _live_fraction(which: str, H: int, W: int, Ho: int, Wo: int, kh: int, kw: in
     return live / float(Ho * Wo * kh * kw)
 
 
+_ROW_BLOCK_BIT = {"fwd": 1, "bwd_data": 2, "bwd_weight": 0}          # KanPlan.row_blocks: which launches run row-ordered 4x4 blocks
+
+
 def _executed_flops(geom, plan, which: str) -> float:
     """Dense count minus the dead (position, tap) products a position-major launch skips (plan.*_target > 0 marks one)."""
     target = {"fwd": plan.fwd_target, "bwd_data": plan.bwd_data_target, "bwd_weight": plan.bwd_weight_target}[which]
     dense = _conv_flops(geom, plan)
     if target <= 0:
         # row-ordered 4x4 launches skip the blocks of the first / last row under the tap row that leaves the plane: 2/3 * 1/4 of the work
-        if plan.row_blocks & {"fwd": 1, "bwd_data": 2}.get(which, 0):
+        if plan.row_blocks & _ROW_BLOCK_BIT[which]:
             return dense * (5.0 / 6.0)
         return dense
     g = geom
@@ -178,14 +189,26 @@ def _layer_tag(geom) -> str:
     return f"{geom.C * max(1, geom.groups)}->{geom.O * max(1, geom.groups)}@{geom.H}x{geom.W} k{geom.kh}x{geom.kw}"
 
 
-def _tile_tag(plan) -> str:
-    return "128" if plan.Opad % 128 == 0 else "64"
-
-
-def _fwd_name(plan) -> str:
-    if plan.fwd_band:                                 # band kernel tiles: 128 outputs where they fit, 192 for exactly 192, else 64 (kan_direct.hip)
-        return "k_band_fwd/o" + ("128" if plan.Opad % 128 == 0 else "192" if plan.Opad == 192 else "64")
-    return ("k_conv_fwd_halo/o" if plan.fwd_halo else "k_conv_fwd/o") + _tile_tag(plan)
+def _sample(which: str, geom, plan, pm: bool, two: bool = False, expanded: bool = False):
+    """THE place that names a launch: the (name, flops, executed, layer) arguments of `_launch` for the launch the caller makes.
+    `which`: "fwd" | "bwd_weight" | "bwd_data"; `pm`: the position-major copies that launch can take were passed; `two`: a second
+    input (xn) was passed (the halo weight gradient then is not run); `expanded`: it is the expanded-operand (DMA) entry point."""
+    tile = "128" if plan.Opad % 128 == 0 else "64"
+    if which == "bwd_data":
+        name = "k_conv_bwd_data"
+    elif expanded:
+        name = f"k_conv_{which}_pmdma/o{tile}"
+    elif plan.fwd_band if which == "fwd" else plan.bwd_weight_band:
+        # band kernel tiles: 128 outputs where they fit, 192 for exactly 192, else 64 (kan_direct.hip); the weight gradient takes the
+        # band route only where the forward does (kan_plan.hip: band_bw implies band), so one tag rule serves both
+        name = f"k_band_{which}/o" + ("128" if plan.Opad % 128 == 0 else "192" if plan.Opad == 192 else "64")
+    else:
+        halo = plan.fwd_halo if which == "fwd" else (plan.bwd_weight_halo and not two)
+        name = f"k_conv_{which}{'_halo' if halo else ''}/o{tile}"
+    # zero products are skipped by the expanded launches, by launches that got their position-major copies, and by the row-ordered 4x4 ones
+    skips = expanded or pm or bool(plan.row_blocks & _ROW_BLOCK_BIT[which])
+    dense = _conv_flops(geom, plan)
+    return name, dense, _executed_flops(geom, plan, which) if skips else dense, _layer_tag(geom)
 
 
 # --------------------------------------------------------------------------------------- raw stages
@@ -248,7 +271,6 @@ def always_pack():
 
 
 _SPLIT_INFERENCE = False
-_SPLIT_NOW = False
 _SPLIT_CACHE: "OrderedDict" = OrderedDict()             # (weight addresses) -> (version stamps, epoch, cut weights)
 
 
@@ -271,9 +293,8 @@ def _split_stage(spec: ConvSpec, x: torch.Tensor, w_base, w_basis):
     if spec.groups != 1 or not spec.has_base or x.dim() != 4:
         return None
     lib = L.load()
-    B, Ct, H, W = x.shape
     wb, ws = w_base[0], w_basis[0]
-    geom, basis, _ = _plan_cached(spec, B, Ct, H, W, ws.shape[0], Ct, ws.shape[0])
+    geom, basis, _ = _plan_cached(*_plan_key(spec, x.shape, ws.shape[0]))
     if not lib.kan_split_supported(C.byref(geom), C.byref(basis)):
         return None
     key = (wb.data_ptr(), ws.data_ptr(), x.device.index)
@@ -384,30 +405,25 @@ def _pack(lib, spec, geom, basis, plan, plan_key, w_base, w_basis, need_dgrad, p
 def _conv_forward(spec: ConvSpec, x, xn, w_base, w_basis, need_dgrad: bool = True, phases=None):
     """Returns (z_slabs [S,B,O,Ho,Wo], (bwd-data weight layout or None, position-major x or None), geom, basis, plan)."""
     lib = L.load()
-    B, Ct, H, W = x.shape
-    G = spec.groups
-    Cg, Og = Ct // G, w_basis[0].shape[0]
-    Ot = Og * G
-    plan_key = (spec, B, Cg, H, W, Og, Ct, Ot)
+    Ct = x.shape[1]
+    plan_key = _plan_key(spec, x.shape, w_basis[0].shape[0])
     geom, basis, plan = _plan_cached(*plan_key)
     basis = _with_phases(basis, phases)
-    Ho, Wo = geom.Ho, geom.Wo
     st = _stream(x)
-    z = torch.empty((plan.fwd_splits, B, Ot, Ho, Wo), device=x.device, dtype=torch.float32)
+    z = torch.empty((plan.fwd_splits, geom.B, geom.O * spec.groups, geom.Ho, geom.Wo), device=x.device, dtype=torch.float32)
     wp, wd = _pack(lib, spec, geom, basis, plan, plan_key, w_base, w_basis, need_dgrad, phases, x.device, st)
     if plan.fwd_expanded and xn is None:
         # small padded planes: the expanded position-major operand (kept for the weight gradient), DMA + MFMA forward
         e_pm = _expand_pm(x, geom, basis, plan, st)
-        _launch("k_conv_fwd_pmdma/o" + _tile_tag(plan), _conv_flops(geom, plan), x,
-                lambda: lib.kan_conv_fwd_expanded(_ptr(e_pm), _ptr(wp), _ptr(z), C.byref(geom), C.byref(basis), st),
-                _executed_flops(geom, plan, "fwd"), _layer_tag(geom))
+        _launch(_sample("fwd", geom, plan, True, expanded=True), x,
+                lambda: lib.kan_conv_fwd_expanded(_ptr(e_pm), _ptr(wp), _ptr(z), C.byref(geom), C.byref(basis), st))
         # what the backward keeps: the expanded copy (its weight gradient reads it), or -- when that launch still runs the
         # tap-major position-major kernel -- the plain copy it needs
         return z, (wd, _position_major(x, 0, Ct) if plan.x_pm_wanted else e_pm), geom, basis, plan
     x_pm = _position_major(x, 0, Ct) if (plan.x_pm_wanted and xn is None) else None
-    _launch(_fwd_name(plan), _conv_flops(geom, plan), x,
+    _launch(_sample("fwd", geom, plan, x_pm is not None, xn is not None), x,
             lambda: lib.kan_conv_fwd(_ptr(x), _ptr(xn if xn is not None else x), _ptr(wp), _ptr(z), C.byref(geom), C.byref(basis),
-                                     _ptr(x_pm), st), _executed_flops(geom, plan, "fwd") if (x_pm is not None or plan.row_blocks & 1) else None, _layer_tag(geom))
+                                     _ptr(x_pm), st))
     return z, (wd, x_pm), geom, basis, plan
 
 
@@ -457,7 +473,7 @@ def _conv_backward(spec: ConvSpec, x, xn, packed, dz, need_x: bool, need_xn: boo
     Cg = Ct // G
     Ot = dz.shape[1]
     Og = Ot // G
-    geom, basis, plan = _plan_cached(spec, B, Cg, H, W, Og, Ct, Ot)
+    geom, basis, plan = _plan_cached(*_plan_key(spec, x.shape, Og))
     basis = _with_phases(basis, phases, mode)
     kh, kw = spec.kernel
     st = _stream(x)
@@ -471,15 +487,12 @@ def _conv_backward(spec: ConvSpec, x, xn, packed, dz, need_x: bool, need_xn: boo
         if plan.bwd_weight_expanded and xn is None and dz_pm is not None:
             # small padded planes: expanded position-major operand, DMA + MFMA weight gradient (kanconv.h)
             e_pm = x_pm if (plan.fwd_expanded and not plan.x_pm_wanted and x_pm is not None and mode == 0) else _expand_pm(x, geom, basis, plan, st)   # the forward's copy, if it kept one (value planes only)
-            _launch("k_conv_bwd_weight_pmdma/o" + _tile_tag(plan), _conv_flops(geom, plan), x,
-                    lambda: lib.kan_conv_bwd_weight_expanded(_ptr(dz_pm), _ptr(e_pm), _ptr(dwp), C.byref(geom), C.byref(basis), st),
-                    _executed_flops(geom, plan, "bwd_weight"), _layer_tag(geom))
+            _launch(_sample("bwd_weight", geom, plan, True, expanded=True), x,
+                    lambda: lib.kan_conv_bwd_weight_expanded(_ptr(dz_pm), _ptr(e_pm), _ptr(dwp), C.byref(geom), C.byref(basis), st))
         else:
-            _launch(_fwd_name(plan).replace("fwd", "bwd_weight") if plan.bwd_weight_band else
-                    ("k_conv_bwd_weight_halo/o" if (plan.bwd_weight_halo and xn is None) else "k_conv_bwd_weight/o") + _tile_tag(plan), _conv_flops(geom, plan), x,
+            _launch(_sample("bwd_weight", geom, plan, x_pm is not None and dz_pm is not None, xn is not None), x,
                     lambda: lib.kan_conv_bwd_weight(_ptr(dz), _ptr(x), _ptr(xs), _ptr(dwp), C.byref(geom), C.byref(basis), _ptr(x_pm),
-                                                    _ptr(dz_pm), st),
-                    _executed_flops(geom, plan, "bwd_weight") if (x_pm is not None and dz_pm is not None) else None, _layer_tag(geom))
+                                                    _ptr(dz_pm), st))
         sb = _sink_for(wids[0], (Og, Cg, kh, kw), x.device) if (wids and G == 1 and spec.has_base) else None
         ss = _sink_for(wids[1], (Og, Cg * spec.n_basis, kh, kw), x.device) if (wids and G == 1) else None
         dwb = (sb.unsqueeze(0) if sb is not None else
@@ -495,12 +508,10 @@ def _conv_backward(spec: ConvSpec, x, xn, packed, dz, need_x: bool, need_xn: boo
         separate = xn is not None
         dxs = torch.empty((S, B, Ct, H, W), device=x.device, dtype=torch.float32)
         dxns = torch.empty_like(dxs) if separate else None
-        _launch("k_conv_bwd_data", _conv_flops(geom, plan), x,
-                (lambda: lib.kan_conv_bwd_data(_ptr(dz), _ptr(x), _ptr(xs), _ptr(wd), _ptr(dxs), _ptr(dxns) if separate else C.c_void_p(0),
-                                               C.byref(geom), C.byref(basis), _ptr(dz_pm), st)) if dparams is None else
-                (lambda: lib.kan_conv_bwd_data_params(_ptr(dz), _ptr(x), _ptr(xs), _ptr(wd), _ptr(dxs), _ptr(dxns) if separate else C.c_void_p(0),
-                                                      _ptr(dparams), C.byref(geom), C.byref(basis), _ptr(dz_pm), st)),
-                _executed_flops(geom, plan, "bwd_data") if (dz_pm is not None or plan.row_blocks & 2) else None, _layer_tag(geom))
+        head, tail = (_ptr(dz), _ptr(x), _ptr(xs), _ptr(wd), _ptr(dxs), _ptr(dxns)), (C.byref(geom), C.byref(basis), _ptr(dz_pm), st)
+        _launch(_sample("bwd_data", geom, plan, dz_pm is not None), x,
+                (lambda: lib.kan_conv_bwd_data(*head, *tail)) if dparams is None else
+                (lambda: lib.kan_conv_bwd_data_params(*head, _ptr(dparams), *tail)))
         dx, dxn = _sum_slabs(dxs, B, Ct, H * W), (_sum_slabs(dxns, B, Ct, H * W) if separate else None)
     return dx, dxn, dw_base, dw_basis
 
@@ -515,47 +526,21 @@ def _sum_slabs(slabs: torch.Tensor, B: int, Cn: int, HW: int) -> torch.Tensor:
     return out
 
 
-def _unflatten(layout, tensors):
-    """Inverse of the save_for_backward flattening of the (wd, x_pm) pair."""
-    it = iter(tensors)
-    has_wd, has_xp = layout
-    return (next(it) if has_wd else None, next(it) if has_xp else None)
-
-
 def _flat_grads(spec: ConvSpec, dw_base, dw_basis):
     return tuple(dw_base) + tuple(dw_basis) if spec.has_base else tuple(dw_basis)
 
 
 # --------------------------------------------------------------------------------------- autograd
-class _KanConv(torch.autograd.Function):
-    """z = conv stage.  args: spec, x, xn (or None), *[w_base_g...], *[w_basis_g...]"""
+def _save(ctx, **named) -> None:
+    """save_for_backward of the tensors that are not None, remembered by name (`_saved` returns them)."""
+    ctx.saved_names = tuple(k for k, t in named.items() if t is not None)
+    ctx.save_for_backward(*(t for t in named.values() if t is not None))
 
-    @staticmethod
-    def forward(ctx, spec: ConvSpec, x, xn, *weights):
-        x = _require(x, "x")
-        xn = _require(xn, "xn") if xn is not None else None
-        weights = [_require(w, "weight") for w in weights]
-        w_base, w_basis = _split_weights(spec, weights)
-        need_dgrad = bool(ctx.needs_input_grad[1] or (xn is not None and ctx.needs_input_grad[2]))
-        with torch.cuda.device(x.device):
-            z, packed, geom, _, plan = _conv_forward(spec, x, xn, w_base, w_basis, need_dgrad)
-            z = _sum_slabs(z, geom.B, z.shape[2], geom.Ho * geom.Wo)
-        ctx.spec, ctx.has_xn = spec, xn is not None
-        ctx.layout = (packed[0] is not None, packed[1] is not None)
-        ctx.save_for_backward(x, *([xn] if xn is not None else []), *[t for t in packed if t is not None])
-        return z
 
-    @staticmethod
-    def backward(ctx, dz):
-        saved = ctx.saved_tensors
-        x = saved[0]
-        xn = saved[1] if ctx.has_xn else None
-        packed = _unflatten(ctx.layout, list(saved[1 + int(ctx.has_xn):]))
-        need_x, need_xn = ctx.needs_input_grad[1], ctx.has_xn and ctx.needs_input_grad[2]
-        need_w = any(ctx.needs_input_grad[3:])
-        with torch.cuda.device(x.device):
-            dx, dxn, dwb, dws = _conv_backward(ctx.spec, x, xn, packed, dz.contiguous(), need_x, need_xn, need_w)
-        return (None, dx if need_x else None, dxn if need_xn else None) + _flat_grads(ctx.spec, dwb, dws)
+def _saved(ctx, *names):
+    """The tensors `_save` kept under `names` (None for one that was None), in that order."""
+    kept = dict(zip(ctx.saved_names, ctx.saved_tensors))
+    return tuple(kept.get(n) for n in names)
 
 
 def _is_depthwise(spec: ConvSpec, x, w_basis) -> bool:
@@ -563,10 +548,12 @@ def _is_depthwise(spec: ConvSpec, x, w_basis) -> bool:
     return x.shape[1] // spec.groups == 1 and w_basis[0].shape[0] <= 2 and spec.kernel[0] * spec.kernel[1] <= 9
 
 
-class _KanConvPhased(torch.autograd.Function):
-    """Conv stage of a basis with trainable per-channel parameters (ReLU-KAN: relu_kan_layers.py:118-136).
-    args: spec, x, xn (or None: the basis reads x), phases [Cg, 2, n] (phase_low, phase_high per channel), *[w_base_g], *[w_basis_g].
+class _KanConv(torch.autograd.Function):
+    """z = conv stage.  args: spec, x, xn (or None: the basis reads x), phases (or None), *[w_base_g...], *[w_basis_g...]
 
+    `xn`: a second input -- x feeds the base branch (a host-applied base activation: x = act(input)), xn the basis.
+    `phases`: the parameter table of a basis with trainable per-channel parameters, [Cg, 2, n] (phase_low, phase_high per channel) for ReLU-KAN
+    (relu_kan_layers.py:118-136), [n] recurrence coefficients for Gram.
     d phase[c][m][j] = sum_{b,pixel} G_{c,j} * d basis_j / d phase_m, where G = dgrad(dz, W_basis) is never materialised:
     the sum is regrouped as  sum_{group,o,tap} W_basis[o][c*n+j][tap] * wgrad(d basis / d phase_m, dz)[o][c*n+j][tap],
     i.e. the weight-gradient kernel run on the parameter-derivative planes, contracted with the weights."""
@@ -574,36 +561,33 @@ class _KanConvPhased(torch.autograd.Function):
     @staticmethod
     def forward(ctx, spec: ConvSpec, x, xn, phases, *weights):
         x = _require(x, "x")
-        xn = _require(xn, "xn") if xn is not None else None      # host-applied base activation: x = act(input) feeds the base branch, xn = input the basis
-        phases = _require(phases, "phases")
+        xn = _require(xn, "xn") if xn is not None else None
         weights = [_require(w, "weight") for w in weights]
         w_base, w_basis = _split_weights(spec, weights)
-        G = spec.groups
-        want = (x.shape[1] // G, 2, spec.n_basis) if spec.kind == L.BASIS_RELU else (spec.n_basis,)
-        if tuple(phases.shape) != want:
-            raise L.KanConvError(f"parameter table {tuple(phases.shape)} != {want} for basis kind {spec.kind}")
-        need_dgrad = bool(ctx.needs_input_grad[1]) or (xn is not None and bool(ctx.needs_input_grad[2]))
+        if phases is not None:
+            phases = _require(phases, "phases")
+            want = (x.shape[1] // spec.groups, 2, spec.n_basis) if spec.kind == L.BASIS_RELU else (spec.n_basis,)
+            if tuple(phases.shape) != want:
+                raise L.KanConvError(f"parameter table {tuple(phases.shape)} != {want} for basis kind {spec.kind}")
+        need_dgrad = bool(ctx.needs_input_grad[1] or (xn is not None and ctx.needs_input_grad[2]))
         with torch.cuda.device(x.device):
-            z, packed, geom, _, plan = _conv_forward(spec, x, xn, w_base, w_basis, need_dgrad, phases)
+            z, (wd, x_pm), geom, _, plan = _conv_forward(spec, x, xn, w_base, w_basis, need_dgrad, phases)
             z = _sum_slabs(z, geom.B, z.shape[2], geom.Ho * geom.Wo)
         ctx.spec = spec
-        ctx.two = xn is not None
-        ctx.layout = (packed[0] is not None, packed[1] is not None)
-        ctx.save_for_backward(x, phases, *w_basis, *[t for t in packed if t is not None], *([xn] if xn is not None else []))
+        # the basis weights are kept only for the parameter gradient (their version counters are then checked in the backward)
+        kept_w = {f"w_basis{g}": w for g, w in enumerate(w_basis)} if phases is not None else {}
+        _save(ctx, x=x, xn=xn, phases=phases, wd=wd, x_pm=x_pm, **kept_w)
         return z
 
     @staticmethod
     def backward(ctx, dz):
         spec, G = ctx.spec, ctx.spec.groups
-        saved = list(ctx.saved_tensors)
-        xn = saved.pop() if ctx.two else None
-        x, phases = saved[0], saved[1]
-        w_basis = saved[2:2 + G]
-        packed = _unflatten(ctx.layout, list(saved[2 + G:]))
-        need_x, need_xn = ctx.needs_input_grad[1], (ctx.two and ctx.needs_input_grad[2])
+        x, xn, phases, wd, x_pm, *w_basis = _saved(ctx, "x", "xn", "phases", "wd", "x_pm", *(f"w_basis{g}" for g in range(G)))
+        packed = (wd, x_pm)
+        need_x, need_xn = ctx.needs_input_grad[1], xn is not None and ctx.needs_input_grad[2]
         need_p, need_w = ctx.needs_input_grad[3], any(ctx.needs_input_grad[4:])
         dz = dz.contiguous()
-        dph = dxn = None
+        dph = None
         with torch.cuda.device(x.device):
             # ReLU-KAN / Gram: when the input gradient is computed anyway, its launch also accumulates the parameter gradients from the same G tiles
             # (kan_conv_bwd_data_params); otherwise (first layer of a model, depthwise groups) two more weight-gradient passes deliver them
@@ -637,13 +621,78 @@ def _cat(ts: Sequence[Optional[torch.Tensor]]) -> Optional[torch.Tensor]:
     return ts[0] if len(ts) == 1 else torch.cat([t.reshape(-1) for t in ts])
 
 
+# --------------------------------------------------------------------------------------- InstanceNorm [+ PReLU] [+ max-pool] launchers
+# The only callers of the six kan_instnorm_prelu* entry points.  `pool`: False | True (= MaxPool2d(2, 2), the register-resident kernels, even
+# planes only) | (k, s) (= MaxPool2d(k, s), the generic kernels); `groups` > 1: one PReLU slope per C / groups channels.
+def _pool_mode(pool, Ho: int, Wo: int):
+    """(2, 2) on an even plane runs the register-resident 2x2 kernels."""
+    return True if pool == (2, 2) and pool_fusable(True, Ho, Wo) else pool
+
+
+def _norm_fwd(zs, slab_elems: int, gamma, beta, slope, eps: float, groups: int = 1, pool=False):
+    """zs: [S, B, C, H, W] partial slabs `slab_elems` apart, or one [B, C, H, W] tensor.  Returns (y, z, mean, rstd, pidx): z the summed
+    pre-norm values (slab 0 itself when there is one slab, else a tensor of their own, so that the S-slab buffer can be freed), pidx the
+    uint8 argmax of each pool window (None without a pool)."""
+    lib = L.load()
+    S, z = (1, zs) if zs.dim() == 4 else (zs.shape[0], zs[0])
+    B, Ct, Ho, Wo = z.shape
+    HW, span, st = Ho * Wo, (Ct // groups if groups > 1 else 0), _stream(zs)
+    mean = torch.empty(B * Ct, device=zs.device, dtype=torch.float32)
+    rstd = torch.empty_like(mean)
+    if S > 1:
+        z = torch.empty_like(z)
+    pool = _pool_mode(pool, Ho, Wo)
+    if not pool:
+        y = torch.empty_like(z)
+        L.check(lib.kan_instnorm_prelu_fwd(_ptr(zs), S, slab_elems, _ptr(z), _ptr(gamma), _ptr(beta), _ptr(slope), _ptr(y), _ptr(mean), _ptr(rstd),
+                                           B, Ct, HW, Ct * HW, eps, span, st), "kan_instnorm_prelu_fwd")
+        return y, z, mean, rstd, None
+    pk, ps = pool if isinstance(pool, tuple) else (2, 2)
+    if pool is True:
+        if not pool_fusable(True, Ho, Wo):
+            raise L.KanConvError(f"fused 2x2 max-pool needs an even plane, got {Ho}x{Wo}")
+    elif Ho < pk or Wo < pk:
+        raise L.KanConvError(f"fused {pk}x{pk} max-pool on a {Ho}x{Wo} plane")
+    y = torch.empty((B, Ct, (Ho - pk) // ps + 1, (Wo - pk) // ps + 1), device=zs.device, dtype=torch.float32)
+    pidx = torch.empty(y.shape, device=zs.device, dtype=torch.uint8)
+    head = (_ptr(zs), S, slab_elems, _ptr(z), _ptr(gamma), _ptr(beta), _ptr(slope), _ptr(y), C.c_void_p(pidx.data_ptr()), _ptr(mean), _ptr(rstd),
+            B, Ct, Ho, Wo, Ct * HW, eps, span)
+    if pool is True:                                 # the full-size y is never written
+        L.check(lib.kan_instnorm_prelu_pool_fwd(*head, st), "kan_instnorm_prelu_pool_fwd")
+    else:                                            # overlapping windows allowed (the AlexNet pattern 3, 2)
+        L.check(lib.kan_instnorm_prelu_poolk_fwd(*head, pk, ps, st), "kan_instnorm_prelu_poolk_fwd")
+    return y, z, mean, rstd, pidx
+
+
+def _norm_bwd(dy, z, mean, rstd, gamma, beta, slope, pidx, groups: int = 1, pool=False):
+    """Backward of `_norm_fwd` from what it returned.  Returns (dz, dgamma, dbeta, dslope), None for a parameter that is None."""
+    lib = L.load()
+    dy = dy.contiguous()
+    B, Ct, Ho, Wo = z.shape
+    HW, span, st = Ho * Wo, (Ct // groups if groups > 1 else 0), _stream(z)
+    dz = torch.empty_like(z)
+    dgam, dbet, dslo = (torch.zeros_like(t) if t is not None else None for t in (gamma, beta, slope))
+    pool = _pool_mode(pool, Ho, Wo)
+    if not pool:
+        L.check(lib.kan_instnorm_prelu_bwd(_ptr(dy), _ptr(z), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), _ptr(slope), _ptr(dz),
+                                           _ptr(dgam), _ptr(dbet), _ptr(dslo), B, Ct, HW, Ct * HW, span, st), "kan_instnorm_prelu_bwd")
+        return dz, dgam, dbet, dslo
+    head = (_ptr(dy), C.c_void_p(pidx.data_ptr()), _ptr(z), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), _ptr(slope), _ptr(dz),
+            _ptr(dgam), _ptr(dbet), _ptr(dslo), B, Ct, Ho, Wo, Ct * HW, span)
+    if pool is True:
+        L.check(lib.kan_instnorm_prelu_pool_bwd(*head, st), "kan_instnorm_prelu_pool_bwd")
+    else:
+        L.check(lib.kan_instnorm_prelu_poolk_bwd(*head, pool[0], pool[1], st), "kan_instnorm_prelu_poolk_bwd")
+    return dz, dgam, dbet, dslo
+
+
 class _KanConvInPrelu(torch.autograd.Function):
-    """y = [MaxPool2d(2, 2)]([PReLU](InstanceNorm(conv stage))).
-    args: spec, eps, use_affine, use_prelu, pool, x, *[w_base_g], *[w_basis_g], *[gamma_g], *[beta_g], *[prelu_g]"""
+    """y = [MaxPool2d]([PReLU](InstanceNorm(conv stage))).
+    args: spec, eps, use_affine, use_prelu, pool, split, x, *[w_base_g], *[w_basis_g], *[gamma_g], *[beta_g], *[prelu_g]
+    `split`: run the conv stage in split precision where `kan_conv_fwd_split` takes it (inference only: nothing is kept for a backward)."""
 
     @staticmethod
-    def forward(ctx, spec: ConvSpec, eps: float, use_affine: bool, use_prelu: bool, pool: bool, x, *params):
-        lib = L.load()
+    def forward(ctx, spec: ConvSpec, eps: float, use_affine: bool, use_prelu: bool, pool, split: bool, x, *params):
         x = _require(x, "x")
         params = [_require(p, "parameter") for p in params]
         G = spec.groups
@@ -655,102 +704,37 @@ class _KanConvInPrelu(torch.autograd.Function):
         prelus = rest[2 * G * int(use_affine):] if use_prelu else [None] * G
         if use_prelu and any(p.numel() != 1 for p in prelus):
             raise L.KanConvError("only scalar-slope PReLU (nn.PReLU()) is supported, as in kan_layers.py:182")
-        need_dgrad = bool(ctx.needs_input_grad[5])
         with torch.cuda.device(x.device):
-            zs = _split_stage(spec, x, w_base, w_basis) if _SPLIT_NOW else None      # (set by kan_conv_in_prelu: grad mode is always off in here)
-            if zs is not None:                           # opt-in inference mode (split_precision_inference): one slab, nothing kept for a backward
-                packed = (None, None)
-                _, _, plan = _plan_cached(spec, x.shape[0], x.shape[1], x.shape[2], x.shape[3], zs.shape[2], x.shape[1], zs.shape[2])
+            zs = _split_stage(spec, x, w_base, w_basis) if split else None
+            if zs is not None:                           # opt-in inference mode (split_precision_inference): one slab
+                wd = x_pm = None
+                plan = _plan_cached(*_plan_key(spec, x.shape, zs.shape[2] // G))[2]
             else:
-                zs, packed, geom, _, plan = _conv_forward(spec, x, None, w_base, w_basis, need_dgrad)
-            S, B, Ot, Ho, Wo = zs.shape
-            Og, HW = Ot // G, Ho * Wo
-            mean = torch.empty(B * Ot, device=x.device, dtype=torch.float32)
-            rstd = torch.empty_like(mean)
+                zs, (wd, x_pm), _, _, plan = _conv_forward(spec, x, None, w_base, w_basis, bool(ctx.needs_input_grad[6]))
             # all groups in one launch: per-channel gamma/beta concatenated, one PReLU slope per Og channels
             gamma, beta, slope = _cat(gammas), _cat(betas), _cat(prelus)
-            # summed pre-norm values (saved for the backward): slab 0 itself when there is one slab, else a tensor of their own, so
-            # that the S-slab buffer can be freed (was: summed in place into slab 0, then cloned out of the buffer)
-            z = zs[0] if S == 1 else torch.empty((B, Ot, Ho, Wo), device=x.device, dtype=torch.float32)
-            pidx = None
-            if pool == (2, 2) and pool_fusable(True, Ho, Wo):
-                pool = True                              # even planes: the register-resident 2x2 kernels
-            if isinstance(pool, tuple):                  # MaxPool2d(k, s), overlapping windows (the AlexNet pattern 3, 2): generic norm kernels
-                pk, ps = pool
-                if Ho < pk or Wo < pk:
-                    raise L.KanConvError(f"fused {pk}x{pk} max-pool on a {Ho}x{Wo} plane")
-                Hp, Wp = (Ho - pk) // ps + 1, (Wo - pk) // ps + 1
-                y = torch.empty((B, Ot, Hp, Wp), device=x.device, dtype=torch.float32)
-                pidx = torch.empty((B, Ot, Hp, Wp), device=x.device, dtype=torch.uint8)
-                L.check(lib.kan_instnorm_prelu_poolk_fwd(_ptr(zs), S, plan.fwd_slab_elems, _ptr(z), _ptr(gamma), _ptr(beta), _ptr(slope),
-                                                         _ptr(y), C.c_void_p(pidx.data_ptr()), _ptr(mean), _ptr(rstd), B, Ot, Ho, Wo,
-                                                         Ot * HW, eps, Og if G > 1 else 0, pk, ps, _stream(x)), "kan_instnorm_prelu_poolk_fwd")
-            elif pool:                                   # MaxPool2d(2, 2) fused behind the PReLU: the full-size y is never written
-                if not pool_fusable(True, Ho, Wo):
-                    raise L.KanConvError(f"fused 2x2 max-pool needs an even plane, got {Ho}x{Wo}")
-                y = torch.empty((B, Ot, Ho // 2, Wo // 2), device=x.device, dtype=torch.float32)
-                pidx = torch.empty((B, Ot, Ho // 2, Wo // 2), device=x.device, dtype=torch.uint8)
-                L.check(lib.kan_instnorm_prelu_pool_fwd(_ptr(zs), S, plan.fwd_slab_elems, _ptr(z), _ptr(gamma), _ptr(beta), _ptr(slope),
-                                                        _ptr(y), C.c_void_p(pidx.data_ptr()), _ptr(mean), _ptr(rstd), B, Ot, Ho, Wo,
-                                                        Ot * HW, eps, Og if G > 1 else 0, _stream(x)), "kan_instnorm_prelu_pool_fwd")
-            else:
-                y = torch.empty((B, Ot, Ho, Wo), device=x.device, dtype=torch.float32)
-                L.check(lib.kan_instnorm_prelu_fwd(_ptr(zs), S, plan.fwd_slab_elems, _ptr(z), _ptr(gamma), _ptr(beta), _ptr(slope), _ptr(y),
-                                                   _ptr(mean), _ptr(rstd), B, Ot, HW, Ot * HW, eps, Og if G > 1 else 0, _stream(x)),
-                        "kan_instnorm_prelu_fwd")
-        ctx.spec, ctx.flags = spec, (use_affine, use_prelu, pool)
+            y, z, mean, rstd, pidx = _norm_fwd(zs, plan.fwd_slab_elems, gamma, beta, slope, eps, G, pool)
+        ctx.spec, ctx.pool = spec, pool
         ctx.wids = (id(w_base[0]) if spec.has_base else None, id(w_basis[0])) if G == 1 else None
-        ctx.layout = (packed[0] is not None, packed[1] is not None)
-        ctx.save_for_backward(x, z, mean, rstd, *[t for t in packed if t is not None], *[t for t in (gamma, beta, slope) if t is not None],
-                              *([pidx] if pool else []))
+        _save(ctx, x=x, z=z, mean=mean, rstd=rstd, wd=wd, x_pm=x_pm, gamma=gamma, beta=beta, slope=slope, pidx=pidx)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        lib = L.load()
-        spec = ctx.spec
-        use_affine, use_prelu, pool = ctx.flags
-        G = spec.groups
-        saved = ctx.saved_tensors
-        pidx = saved[-1] if pool else None
-        if pool:
-            saved = saved[:-1]
-        x, z, mean, rstd = saved[:4]
-        nwd = int(ctx.layout[0]) + int(ctx.layout[1])
-        packed = _unflatten(ctx.layout, list(saved[4:4 + nwd]))
-        rest = list(saved[4 + nwd:])
-        gamma, beta = (rest[0], rest[1]) if use_affine else (None, None)
-        slope = rest[2 * int(use_affine)] if use_prelu else None
-        dy = dy.contiguous()
-        B, Ot, Ho, Wo = z.shape
-        Og, HW = Ot // G, Ho * Wo
+        spec, G = ctx.spec, ctx.spec.groups
+        x, z, mean, rstd, wd, x_pm, gamma, beta, slope, pidx = _saved(ctx, "x", "z", "mean", "rstd", "wd", "x_pm", "gamma", "beta", "slope", "pidx")
         with torch.cuda.device(x.device):
-            dz = torch.empty_like(z)
-            dgam = torch.zeros_like(gamma) if use_affine else None
-            dbet = torch.zeros_like(beta) if use_affine else None
-            dpre = torch.zeros_like(slope) if use_prelu else None
-            if isinstance(pool, tuple):
-                L.check(lib.kan_instnorm_prelu_poolk_bwd(_ptr(dy), C.c_void_p(pidx.data_ptr()), _ptr(z), _ptr(mean), _ptr(rstd), _ptr(gamma),
-                                                         _ptr(beta), _ptr(slope), _ptr(dz), _ptr(dgam), _ptr(dbet), _ptr(dpre), B, Ot, Ho, Wo,
-                                                         Ot * HW, Og if G > 1 else 0, pool[0], pool[1], _stream(x)), "kan_instnorm_prelu_poolk_bwd")
-            elif pool:
-                L.check(lib.kan_instnorm_prelu_pool_bwd(_ptr(dy), C.c_void_p(pidx.data_ptr()), _ptr(z), _ptr(mean), _ptr(rstd), _ptr(gamma),
-                                                        _ptr(beta), _ptr(slope), _ptr(dz), _ptr(dgam), _ptr(dbet), _ptr(dpre), B, Ot, Ho, Wo,
-                                                        Ot * HW, Og if G > 1 else 0, _stream(x)), "kan_instnorm_prelu_pool_bwd")
-            else:
-                L.check(lib.kan_instnorm_prelu_bwd(_ptr(dy), _ptr(z), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), _ptr(slope), _ptr(dz),
-                                                   _ptr(dgam), _ptr(dbet), _ptr(dpre), B, Ot, HW, Ot * HW, Og if G > 1 else 0, _stream(x)),
-                        "kan_instnorm_prelu_bwd")
+            dz, dgam, dbet, dpre = _norm_bwd(dy, z, mean, rstd, gamma, beta, slope, pidx, G, ctx.pool)
             nw = G * (2 if spec.has_base else 1)
-            need_x = ctx.needs_input_grad[5]
-            need_w = any(ctx.needs_input_grad[6:6 + nw])
-            dx, _, dwb, dws = _conv_backward(spec, x, None, packed, dz, need_x, False, need_w, wids=ctx.wids)
+            need_x = ctx.needs_input_grad[6]
+            need_w = any(ctx.needs_input_grad[7:7 + nw])
+            dx, _, dwb, dws = _conv_backward(spec, x, None, (wd, x_pm), dz, need_x, False, need_w, wids=ctx.wids)
         grads = _flat_grads(spec, dwb, dws)
-        if use_affine:
-            grads += tuple(dgam.view(G, Og).unbind(0)) + tuple(dbet.view(G, Og).unbind(0))
-        if use_prelu:
+        if gamma is not None:
+            grads += tuple(dgam.view(G, -1).unbind(0)) + tuple(dbet.view(G, -1).unbind(0))
+        if slope is not None:
             grads += tuple(dpre.view(G, 1).unbind(0))
-        return (None, None, None, None, None, dx if need_x else None) + grads
+        return (None, None, None, None, None, None, dx if need_x else None) + grads
 
 
 class _InstanceNorm(torch.autograd.Function):
@@ -758,33 +742,17 @@ class _InstanceNorm(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, gamma, beta, eps: float):
-        lib = L.load()
         x = _require(x, "x")
-        B, Cn, H, W = x.shape
         with torch.cuda.device(x.device):
-            y = torch.empty_like(x)
-            mean = torch.empty(B * Cn, device=x.device, dtype=torch.float32)
-            rstd = torch.empty_like(mean)
-            L.check(lib.kan_instnorm_prelu_fwd(_ptr(x), 1, 0, _ptr(x), _ptr(gamma), _ptr(beta), C.c_void_p(0), _ptr(y), _ptr(mean), _ptr(rstd),
-                                               B, Cn, H * W, Cn * H * W, eps, 0, _stream(x)), "kan_instnorm_prelu_fwd")
-        ctx.affine = gamma is not None
-        ctx.save_for_backward(x, mean, rstd, *([gamma, beta] if gamma is not None else []))
+            y, _, mean, rstd, _ = _norm_fwd(x, 0, gamma, beta, None, eps)
+        _save(ctx, x=x, mean=mean, rstd=rstd, gamma=gamma, beta=beta)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        lib = L.load()
-        saved = ctx.saved_tensors
-        x, mean, rstd = saved[:3]
-        gamma, beta = (saved[3], saved[4]) if ctx.affine else (None, None)
-        dy = dy.contiguous()
-        B, Cn, H, W = x.shape
+        x, mean, rstd, gamma, beta = _saved(ctx, "x", "mean", "rstd", "gamma", "beta")
         with torch.cuda.device(x.device):
-            dx = torch.empty_like(x)
-            dg = torch.zeros_like(gamma) if ctx.affine else None
-            db = torch.zeros_like(beta) if ctx.affine else None
-            L.check(lib.kan_instnorm_prelu_bwd(_ptr(dy), _ptr(x), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), C.c_void_p(0), _ptr(dx),
-                                               _ptr(dg), _ptr(db), C.c_void_p(0), B, Cn, H * W, Cn * H * W, 0, _stream(x)), "kan_instnorm_prelu_bwd")
+            dx, dg, db, _ = _norm_bwd(dy, x, mean, rstd, gamma, beta, None, None)
         return dx, dg, db, None
 
 
@@ -861,36 +829,33 @@ def _image_runs(spec: ConvSpec, x: torch.Tensor, out_channels: int) -> Optional[
     return -(-B // runs)
 
 
-def _by_image_runs(fn, n: int, x: torch.Tensor, xn: Optional[torch.Tensor] = None) -> torch.Tensor:
+def _apply(stage, spec: ConvSpec, x, xn, w_base, w_basis, extra=()) -> torch.Tensor:
+    """Body of the public entry points: stage(x, xn, *flattened weight lists, *extra), once, or once per run of whole images."""
+    ws = (list(w_base) if spec.has_base else []) + list(w_basis) + list(extra)
+    n = _image_runs(spec, x, sum(w.shape[0] for w in w_basis))
+    if n is None:
+        return stage(x, xn, *ws)
     xs = x.split(n)
     xns = xn.split(n) if xn is not None else [None] * len(xs)
-    return torch.cat([fn(a.contiguous(), b.contiguous() if b is not None else None) for a, b in zip(xs, xns)])
+    return torch.cat([stage(a.contiguous(), b.contiguous() if b is not None else None, *ws) for a, b in zip(xs, xns)])
 
 
 def kan_conv(spec: ConvSpec, x: torch.Tensor, xn: Optional[torch.Tensor], w_base: Sequence[torch.Tensor],
              w_basis: Sequence[torch.Tensor]) -> torch.Tensor:
-    ws = (list(w_base) if spec.has_base else []) + list(w_basis)
-    n = _image_runs(spec, x, sum(w.shape[0] for w in w_basis))
-    if n is not None:
-        return _by_image_runs(lambda a, b: _KanConv.apply(spec, a, b, *ws), n, x, xn)
-    return _KanConv.apply(spec, x, xn, *ws)
+    return _apply(lambda a, b, *ws: _KanConv.apply(spec, a, b, None, *ws), spec, x, xn, w_base, w_basis)
 
 
 def kan_conv_phased(spec: ConvSpec, x: torch.Tensor, phases: torch.Tensor, w_base: Sequence[torch.Tensor],
                     w_basis: Sequence[torch.Tensor], xn: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Conv stage of a basis with trainable parameters held in device memory, differentiable in them: ReLU-KAN
     (`phases` = [channels per group, 2, n_basis]: low, high) or Gram (`phases` = [n_basis] recurrence coefficients c_k)."""
-    ws = (list(w_base) if spec.has_base else []) + list(w_basis)
-    n = _image_runs(spec, x, sum(w.shape[0] for w in w_basis))
-    if n is not None:
-        return _by_image_runs(lambda a, b: _KanConvPhased.apply(spec, a, b, phases, *ws), n, x, xn)
-    return _KanConvPhased.apply(spec, x, xn, phases, *ws)
+    return _apply(lambda a, b, *ws: _KanConv.apply(spec, a, b, phases, *ws), spec, x, xn, w_base, w_basis)
 
 
 def pool_fusable(pool, ho: int, wo: int) -> bool:
     """THE rule for whether the InstanceNorm(+PReLU) kernels can apply the max-pool `pool` to a ho x wo plane: a (k, s) window always
     (the generic kernels), True = MaxPool2d(2, 2) only on an even plane (the register-resident 2x2 kernels).  The layers ask before they
-    request a fused pool; `_KanConvInPrelu` refuses a request that breaks it."""
+    request a fused pool; `_norm_fwd` refuses a request that breaks it."""
     return pool is not True or (ho % 2 == 0 and wo % 2 == 0)
 
 
@@ -910,15 +875,11 @@ def kan_conv_in_prelu(spec: ConvSpec, x: torch.Tensor, w_base: Sequence[torch.Te
     """`pool=True` additionally applies MaxPool2d(kernel 2, stride 2) inside the same kernels (even output planes only); `pool=(k, s)` a general
     MaxPool2d(k, s) without padding (overlapping windows allowed: the AlexNet pattern (3, 2))."""
     pool = _norm_pool(pool)
-    global _SPLIT_NOW
-    _SPLIT_NOW = _SPLIT_INFERENCE and not torch.is_grad_enabled()        # opt-in inference mode: decided where the caller's grad mode is visible
-    ws = (list(w_base) if spec.has_base else []) + list(w_basis)
+    split = _SPLIT_INFERENCE and not torch.is_grad_enabled()            # opt-in inference mode: decided where the caller's grad mode is visible
     aff = gammas is not None
     extra = (list(gammas) + list(betas) if aff else []) + (list(prelus) if prelus is not None else [])
-    n = _image_runs(spec, x, sum(w.shape[0] for w in w_basis))
-    if n is not None:
-        return _by_image_runs(lambda a, _: _KanConvInPrelu.apply(spec, float(eps), aff, prelus is not None, pool, a, *ws, *extra), n, x)
-    return _KanConvInPrelu.apply(spec, float(eps), aff, prelus is not None, pool, x, *ws, *extra)
+    return _apply(lambda a, _, *ps: _KanConvInPrelu.apply(spec, float(eps), aff, prelus is not None, pool, split, a, *ps),
+                  spec, x, None, w_base, w_basis, extra)
 
 
 def kan_conv_fwd_split(spec: ConvSpec, x: torch.Tensor, w_base: torch.Tensor, w_basis: torch.Tensor, wc: Optional[torch.Tensor] = None):
@@ -928,9 +889,8 @@ def kan_conv_fwd_split(spec: ConvSpec, x: torch.Tensor, w_base: torch.Tensor, w_
     weights are unchanged to skip the cut (0.05 ms at 256 -> 256)."""
     lib = L.load()
     x, w_base, w_basis = _require(x, "x"), _require(w_base, "w_base"), _require(w_basis, "w_basis")
-    B, Ct, H, W = x.shape
-    Ot = w_basis.shape[0]
-    geom, basis, _ = _plan_cached(spec, B, Ct, H, W, Ot, Ct, Ot)
+    (B, _, H, W), Ot = x.shape, w_basis.shape[0]
+    geom, basis, _ = _plan_cached(*_plan_key(spec, x.shape, Ot))
     if not lib.kan_split_supported(C.byref(geom), C.byref(basis)):
         raise L.KanConvError("split-precision forward: default B-spline spec (grid 5, order 3, SiLU base branch), 8x8 or 16x16 planes, 3x3 / stride 1 / pad 1, one group, C % 8 == 0, O % 128 == 0, "
                              "even batch only")

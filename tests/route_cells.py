@@ -48,7 +48,7 @@ def dw_direct(g, b):
 
 def second_input(b):
     """LegendreKAN (recurrence basis of order 0) always hands the kernels a second, pre-normalised tensor; ops.py then makes no
-    position-major copy (ops.py:407, ops.py:468) and every launch stays image-major.  (FastKAN also passes one, but the planner
+    position-major copy (ops.py:423, ops.py:484) and every launch stays image-major.  (FastKAN also passes one, but the planner
     never offers it a position-major launch: want_pix_major, kan_plan.hip.)"""
     return b.kind == L.BASIS_POLY and b.order == 0
 
