@@ -38,6 +38,14 @@ class KanPlan(C.Structure):
                                             "bwd_weight_slab_elems", "e_pm_elems")]
 
 
+class KanNormRoute(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("kernel", "G", "EPL", "PPI", "NT", "pool", "lds", "held", "blocks", "strided")]
+
+
+NORM_GENERIC, NORM_REGS = 0, 1
+NORM_POOL_NONE, NORM_POOL_2X2, NORM_POOL_K = 0, 1, 2
+
+
 class KanWavGeom(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("B", "C", "H", "W", "O", "Ho", "Wo", "kh", "kw", "sh", "sw", "ph", "pw", "dh", "dw", "wavelet")] + \
                [("x_bstride", C.c_longlong), ("u_bstride", C.c_longlong)]
@@ -71,6 +79,7 @@ SIGNATURES = {
     "kan_instnorm_prelu_pool_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _LL, _I, _P]),
     "kan_instnorm_prelu_poolk_fwd": (_I, [_P, _I, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _LL, _F, _I, _I, _I, _P]),
     "kan_instnorm_prelu_poolk_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _LL, _I, _I, _I, _P]),
+    "kan_norm_route": (_I, [_I, _I, _I, _I, _I, _LL, _I, _LL, _I, _I, _I, _I, C.POINTER(KanNormRoute)]),
     "kan_split_supported": (_I, [C.POINTER(KanGeom), C.POINTER(KanBasis)]),
     "kan_split_weight_bytes": (_LL, [C.POINTER(KanGeom), C.POINTER(KanBasis)]),
     "kan_split_pack_weights": (_I, [_P, _P, _P, C.POINTER(KanGeom), C.POINTER(KanBasis), _P]),

@@ -2049,6 +2049,8 @@ __global__ __launch_bounds__(256) void k_in_prelu_fwd(const float* z, int n_slab
     if (sub == 0) { mean_o[plane] = mu; rstd_o[plane] = rs; }
 }
 
+constexpr int IN_BWD_HELD = 16;      // elements per lane k_in_prelu_bwd can hold in registers between its two passes (norm_route: `held`)
+
 template <int G>
 __global__ __launch_bounds__(256) void k_in_prelu_bwd(const float* __restrict__ dy, const float* __restrict__ z,
                                                       const float* __restrict__ mean_i, const float* __restrict__ rstd_i,
@@ -2057,7 +2059,7 @@ __global__ __launch_bounds__(256) void k_in_prelu_bwd(const float* __restrict__ 
                                                       float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dprelu,
                                                       int n_planes, int Cn, int HW, long long bstride, int prelu_span,
                                                       const unsigned char* __restrict__ pidx, int W, FastDiv divW, PoolGeo pool) {
-    constexpr int EPL = 16;                         // elements per lane held in registers between the two passes
+    constexpr int EPL = IN_BWD_HELD;                // elements per lane held in registers between the two passes
     __shared__ double s_da[256 / G];
     const int tid = threadIdx.x, sub = tid % G;
     const bool has_p = prelu_a != nullptr;
@@ -2432,59 +2434,111 @@ TilePerm tile_perm(int tiles_p, Weight weight) {
     return perm;
 }
 
-template <int G>
-void launch_in_fwd(hipStream_t st, int planes, const float* z, int n_slabs, long long slab_elems, float* z_out, const float* gamma,
-                   const float* beta, const float* a, float* y, float* mean, float* rstd, int Cn, int HW, long long bs, float eps, int span,
-                   unsigned char* pidx = nullptr, int W = 0, PoolGeo pg = PoolGeo{}) {
-    int ppb = 256 / G;
-    size_t lds = 0;
-    if (pg.k) { lds = (size_t)ppb * HW * 4; pg.lds = lds <= 48 * 1024; if (!pg.lds) lds = 0; }
-    hipLaunchKernelGGL((k_in_prelu_fwd<G>), dim3(ceil_div(planes, ppb)), dim3(256), lds, st, z, n_slabs, slab_elems, z_out, gamma, beta, a, y,
-                       mean, rstd, planes, Cn, HW, bs, eps, span, pidx, W, make_fastdiv(W > 1 ? W / 2 : 1), pg);
-}
-template <int G>
-void launch_in_bwd(hipStream_t st, int planes, const float* dy, const float* z, const float* mean, const float* rstd, const float* gamma,
-                   const float* beta, const float* a, float* dz, float* dgamma, float* dbeta, float* dprelu, int Cn, int HW, long long bs,
-                   int span, const unsigned char* pidx = nullptr, int W = 0, PoolGeo pg = PoolGeo{}) {
-    int ppb = 256 / G;
-    int blocks = ceil_div(planes, ppb);
-    const int cap = (long long)planes * HW < (4ll << 20) ? 512 : 2048;       // small tensors: fewer same-address atomics on dprelu
-    if (blocks > cap) blocks = cap;
-    size_t lds = 0;
-    if (pg.k) { lds = (size_t)ppb * HW * 4; pg.lds = lds <= 48 * 1024; if (!pg.lds) lds = 0; }
-    hipLaunchKernelGGL((k_in_prelu_bwd<G>), dim3(blocks), dim3(256), lds, st, dy, z, mean, rstd, gamma, beta, a, dz, dgamma,
-                       dbeta, dprelu, planes, Cn, HW, bs, span, pidx, W, make_fastdiv(W > 0 ? W : 1), pg);
-}
-template <int G, int EPL, int PPI, bool POOL>
-void launch_in_fwd_regs(hipStream_t st, int planes, const float* z, int n_slabs, long long slab_elems, float* z_out, const float* gamma,
-                        const float* beta, const float* a, float* y, float* mean, float* rstd, int Cn, int HW, long long bs, float eps, int span,
-                        unsigned char* pidx, int W) {
-    constexpr int NT = 256;
-    const int groups = ceil_div(planes, NT / G);
-    int blocks = ceil_div(groups, PPI);
-    if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL((k_in_prelu_fwd_regs<G, EPL, PPI, POOL, NT>), dim3(blocks), dim3(NT), 0, st, z, n_slabs, slab_elems, z_out, gamma, beta, a, y,
-                       mean, rstd, planes, Cn, HW, bs, eps, span, pidx, W, make_fastdiv(W > 1 ? W / 2 : 1));
-}
-template <int G, int EPL, int PPI>
-void launch_in_bwd_regs(hipStream_t st, int planes, const float* dy, const float* z, const float* mean, const float* rstd, const float* gamma,
-                        const float* beta, const float* a, float* dz, float* dgamma, float* dbeta, float* dprelu, int Cn, int HW,
-                        long long bs, int span, const unsigned char* pidx, int W) {
-    constexpr int NT = EPL * PPI <= 8 ? 1024 : 256;      // (<= 128 VGPRs needed for 1024 threads)
-    const int groups = ceil_div(planes, NT / G);
-    int blocks = ceil_div(groups, PPI);
-    if (blocks > 512 * (1024 / NT)) blocks = 512 * (1024 / NT);
-    const FastDiv dw = make_fastdiv(W > 0 ? W : 1);
-    if (pidx) hipLaunchKernelGGL((k_in_prelu_bwd_regs<G, EPL, PPI, true, NT>), dim3(blocks), dim3(NT), 0, st, dy, z, mean, rstd, gamma, beta, a, dz,
-                                 dgamma, dbeta, dprelu, planes, Cn, HW, bs, span, pidx, W, dw);
-    else hipLaunchKernelGGL((k_in_prelu_bwd_regs<G, EPL, PPI, false, NT>), dim3(blocks), dim3(NT), 0, st, dy, z, mean, rstd, gamma, beta, a, dz,
-                            dgamma, dbeta, dprelu, planes, Cn, HW, bs, span, pidx, W, dw);
-}
+// ---------------------------------------------------------------------------- InstanceNorm (+ PReLU, + max-pool): route and launchers
+// Every threshold of the norm dispatch lives in the tables and in norm_route() below; the launchers take the launch shape from the route.
+// Register-resident variants X(limit, G, EPL, PPI): the first row whose limit covers the plane (pixels; windows for the pooled forward).
+#define KAN_IN_REGS_PLAIN(X) X(4, 4, 1, 4) X(8, 8, 1, 4) X(16, 16, 1, 4) X(32, 32, 1, 4) \
+    X(64, 16, 4, 2)      /* (8x8 planes: 4 elements per lane, measured 52 -> 37 us on 256x256x8x8) */ \
+    X(128, 64, 2, 2) X(256, 64, 4, 2) X(512, 64, 8, 1) X(1024, 64, 16, 1)
+#define KAN_IN_REGS_POOL2(X) X(4, 4, 4, 2) X(8, 8, 4, 2) X(16, 16, 4, 2) X(32, 32, 4, 2) X(64, 64, 4, 2) X(128, 64, 8, 1) X(256, 64, 16, 1)
+#define KAN_IN_GENERIC(X) X(4) X(8) X(16) X(32) X(64)
+struct NormVariant { int limit, G, EPL, PPI; };
+#define KAN_IN_ROW(LIM, G, EPL, PPI) {LIM, G, EPL, PPI},
+constexpr NormVariant IN_REGS_PLAIN[] = {KAN_IN_REGS_PLAIN(KAN_IN_ROW)};
+constexpr NormVariant IN_REGS_POOL2[] = {KAN_IN_REGS_POOL2(KAN_IN_ROW)};
+#undef KAN_IN_ROW
+template <int N> constexpr int last_limit(const NormVariant (&t)[N]) { return t[N - 1].limit; }
+constexpr int IN_REGS_MAX_HW = last_limit(IN_REGS_PLAIN);      // the largest plane the register kernels take
+static_assert(4 * last_limit(IN_REGS_POOL2) == IN_REGS_MAX_HW, "the windowed table ends at the same plane (4 pixels per window)");
+
+// The compile-time side of the same tables: pick_*(route, f) calls f(NormPick<G, EPL, PPI>{}) for the row the route names (false: no such row).
+template <int G_, int EPL_ = 0, int PPI_ = 0> struct NormPick { static constexpr int G = G_, EPL = EPL_, PPI = PPI_; };
+#define KAN_IN_PICK(LIM, G_, EPL_, PPI_) if (r.G == G_ && r.EPL == EPL_ && r.PPI == PPI_) { f(NormPick<G_, EPL_, PPI_>{}); return true; }
+#define KAN_IN_PICK_G(G_) if (r.G == G_) { f(NormPick<G_>{}); return true; }
+template <class F> bool pick_regs_plain(const KanNormRoute& r, F&& f) { KAN_IN_REGS_PLAIN(KAN_IN_PICK) return false; }
+template <class F> bool pick_regs_pool2(const KanNormRoute& r, F&& f) { KAN_IN_REGS_POOL2(KAN_IN_PICK) return false; }
+template <class F> bool pick_generic(const KanNormRoute& r, F&& f) { KAN_IN_GENERIC(KAN_IN_PICK_G) return false; }
+#undef KAN_IN_PICK
+#undef KAN_IN_PICK_G
+constexpr int IN_FWD_REGS_NT = 256, IN_FWD_REGS_CAP = 8192;
+constexpr int in_bwd_regs_nt(int EPL, int PPI) { return EPL * PPI <= 8 ? 1024 : 256; }      // (<= 128 VGPRs needed for 1024 threads)
+constexpr int in_bwd_regs_cap(int NT) { return 512 * (1024 / NT); }
+constexpr int IN_POOL_LDS_BYTES = 48 * 1024;
+constexpr int IN_POOL_PER_LANE = 12;            // generic kernels under a general pool: ~12 elements per lane, more planes per workgroup
+
 // Lanes per (b, channel) plane.
 int group_lanes(int HW) {          // (more elements per lane was measured: no gain)
     int g = 4;
     while (g < 64 && g < HW) g <<= 1;
     return g;
+}
+
+// The one decision: `pool` is a KAN_NORM_POOL_* mode, `float2_ok` what the pooled register forward needs of its pointers and strides.
+KanNormRoute norm_route(bool bwd, int planes, int HW, int pool, bool float2_ok) {
+    KanNormRoute r{};
+    r.pool = pool;
+    const bool regs = HW <= IN_REGS_MAX_HW && (bwd ? pool != KAN_NORM_POOL_K : pool == KAN_NORM_POOL_NONE || (pool == KAN_NORM_POOL_2X2 && float2_ok));
+    if (regs) {
+        const bool windows = !bwd && pool == KAN_NORM_POOL_2X2;       // lanes own 2x2 windows (float2 accesses)
+        const NormVariant* v = windows ? IN_REGS_POOL2 : IN_REGS_PLAIN;
+        const int n = windows ? HW / 4 : HW;
+        while (n > v->limit) ++v;
+        r.kernel = KAN_NORM_REGS; r.G = v->G; r.EPL = v->EPL; r.PPI = v->PPI;
+        r.NT = bwd ? in_bwd_regs_nt(v->EPL, v->PPI) : IN_FWD_REGS_NT;
+        const int cap = bwd ? in_bwd_regs_cap(r.NT) : IN_FWD_REGS_CAP;
+        const int want = ceil_div(ceil_div(planes, r.NT / r.G), r.PPI);
+        r.blocks = want < cap ? want : cap;
+        r.strided = want > r.blocks;
+        return r;
+    }
+    r.kernel = KAN_NORM_GENERIC; r.NT = 256;
+    r.G = group_lanes(pool == KAN_NORM_POOL_K ? ceil_div(HW, IN_POOL_PER_LANE) : HW);
+    const int ppb = r.NT / r.G, want = ceil_div(planes, ppb);
+    r.lds = pool == KAN_NORM_POOL_K && (size_t)ppb * HW * 4 <= (size_t)IN_POOL_LDS_BYTES;
+    r.blocks = want;
+    if (bwd) {
+        r.held = HW <= r.G * IN_BWD_HELD;
+        const int cap = (long long)planes * HW < (4ll << 20) ? 512 : 2048;       // small tensors: fewer same-address atomics on dprelu
+        if (r.blocks > cap) r.blocks = cap;
+    }
+    r.strided = want > r.blocks;
+    return r;
+}
+
+template <int G>
+void launch_in_fwd(hipStream_t st, const KanNormRoute& r, int planes, const float* z, int n_slabs, long long slab_elems, float* z_out,
+                   const float* gamma, const float* beta, const float* a, float* y, float* mean, float* rstd, int Cn, int HW, long long bs,
+                   float eps, int span, unsigned char* pidx, int W, PoolGeo pg) {
+    pg.lds = r.lds;
+    hipLaunchKernelGGL((k_in_prelu_fwd<G>), dim3(r.blocks), dim3(256), r.lds ? (size_t)(256 / G) * HW * 4 : 0, st, z, n_slabs, slab_elems, z_out, gamma,
+                       beta, a, y, mean, rstd, planes, Cn, HW, bs, eps, span, pidx, W, make_fastdiv(W > 1 ? W / 2 : 1), pg);
+}
+template <int G>
+void launch_in_bwd(hipStream_t st, const KanNormRoute& r, int planes, const float* dy, const float* z, const float* mean, const float* rstd,
+                   const float* gamma, const float* beta, const float* a, float* dz, float* dgamma, float* dbeta, float* dprelu, int Cn, int HW,
+                   long long bs, int span, const unsigned char* pidx, int W, PoolGeo pg) {
+    pg.lds = r.lds;
+    hipLaunchKernelGGL((k_in_prelu_bwd<G>), dim3(r.blocks), dim3(256), r.lds ? (size_t)(256 / G) * HW * 4 : 0, st, dy, z, mean, rstd, gamma, beta, a, dz,
+                       dgamma, dbeta, dprelu, planes, Cn, HW, bs, span, pidx, W, make_fastdiv(W > 0 ? W : 1), pg);
+}
+template <int G, int EPL, int PPI, bool POOL>
+void launch_in_fwd_regs(hipStream_t st, const KanNormRoute& r, int planes, const float* z, int n_slabs, long long slab_elems, float* z_out,
+                        const float* gamma, const float* beta, const float* a, float* y, float* mean, float* rstd, int Cn, int HW, long long bs,
+                        float eps, int span, unsigned char* pidx, int W) {
+    constexpr int NT = IN_FWD_REGS_NT;
+    hipLaunchKernelGGL((k_in_prelu_fwd_regs<G, EPL, PPI, POOL, NT>), dim3(r.blocks), dim3(NT), 0, st, z, n_slabs, slab_elems, z_out, gamma, beta, a, y,
+                       mean, rstd, planes, Cn, HW, bs, eps, span, pidx, W, make_fastdiv(W > 1 ? W / 2 : 1));
+}
+template <int G, int EPL, int PPI>
+void launch_in_bwd_regs(hipStream_t st, const KanNormRoute& r, int planes, const float* dy, const float* z, const float* mean, const float* rstd,
+                        const float* gamma, const float* beta, const float* a, float* dz, float* dgamma, float* dbeta, float* dprelu, int Cn,
+                        int HW, long long bs, int span, const unsigned char* pidx, int W) {
+    constexpr int NT = in_bwd_regs_nt(EPL, PPI);
+    const FastDiv dw = make_fastdiv(W > 0 ? W : 1);
+    if (pidx) hipLaunchKernelGGL((k_in_prelu_bwd_regs<G, EPL, PPI, true, NT>), dim3(r.blocks), dim3(NT), 0, st, dy, z, mean, rstd, gamma, beta, a, dz,
+                                 dgamma, dbeta, dprelu, planes, Cn, HW, bs, span, pidx, W, dw);
+    else hipLaunchKernelGGL((k_in_prelu_bwd_regs<G, EPL, PPI, false, NT>), dim3(r.blocks), dim3(NT), 0, st, dy, z, mean, rstd, gamma, beta, a, dz,
+                            dgamma, dbeta, dprelu, planes, Cn, HW, bs, span, pidx, W, dw);
 }
 
 // ============================================================================ optimizer step
@@ -2988,44 +3042,26 @@ int kan_slab_reduce(const float* slabs, int n_slabs, long long slab_elems, float
     return launch_ok("slab_reduce");
 }
 
+static bool norm_float2_ok(const void* z, const void* z_out, long long bstride, int HW, long long slab_elems) {
+    return ((bstride | HW) & 1) == 0 && (((size_t)z | (size_t)z_out) & 7) == 0 && (slab_elems & 1) == 0;
+}
+static int norm_pool_mode(const void* pidx, const PoolGeo& pg) { return !pidx ? KAN_NORM_POOL_NONE : pg.k ? KAN_NORM_POOL_K : KAN_NORM_POOL_2X2; }
+
 static int instnorm_fwd_any(const float* z, int n_slabs, long long slab_elems, float* z_out, const float* gamma, const float* beta,
                             const float* prelu_a, float* y, float* mean, float* rstd, int B, int Cn, int HW, long long bstride, float eps,
                             int prelu_span, unsigned char* pidx, int W, void* stream, PoolGeo pg = PoolGeo{}) {
     if (!z || !z_out || !y || !mean || !rstd || n_slabs < 1 || B < 1 || Cn < 1 || HW < 1) return fail("bad instnorm_fwd arguments");
     hipStream_t st = (hipStream_t)stream;
     int planes = B * Cn;
-#define KAN_INF(G, EPL, PPI, POOL) launch_in_fwd_regs<G, EPL, PPI, POOL>(st, planes, z, n_slabs, slab_elems, z_out, gamma, beta, prelu_a, y, mean, rstd, Cn, HW, bstride, eps, prelu_span, pidx, W)
-    if (pidx && !pg.k && HW <= 1024 && ((bstride | HW) & 1) == 0 && (((size_t)z | (size_t)z_out) & 7) == 0 && (slab_elems & 1) == 0) {   // lanes own 2x2 windows (float2 accesses)
-        const int nwin = HW / 4;
-        if (nwin <= 4) KAN_INF(4, 4, 2, true);
-        else if (nwin <= 8) KAN_INF(8, 4, 2, true);
-        else if (nwin <= 16) KAN_INF(16, 4, 2, true);
-        else if (nwin <= 32) KAN_INF(32, 4, 2, true);
-        else if (nwin <= 64) KAN_INF(64, 4, 2, true);
-        else if (nwin <= 128) KAN_INF(64, 8, 1, true);
-        else KAN_INF(64, 16, 1, true);
-        return launch_ok("instnorm_fwd");
-    }
-    if (!pidx && HW <= 1024) {
-        if (HW <= 4) KAN_INF(4, 1, 4, false);
-        else if (HW <= 8) KAN_INF(8, 1, 4, false);
-        else if (HW <= 16) KAN_INF(16, 1, 4, false);
-        else if (HW <= 32) KAN_INF(32, 1, 4, false);
-        else if (HW <= 64) KAN_INF(16, 4, 2, false);
-        else if (HW <= 128) KAN_INF(64, 2, 2, false);
-        else if (HW <= 256) KAN_INF(64, 4, 2, false);
-        else if (HW <= 512) KAN_INF(64, 8, 1, false);
-        else KAN_INF(64, 16, 1, false);
-        return launch_ok("instnorm_fwd");
-    }
-#undef KAN_INF
-    switch (pg.k ? group_lanes((HW + 11) / 12) : group_lanes(HW)) {      // (pooled launches: ~12 elements per lane, more planes per workgroup)
-        case 4:  launch_in_fwd<4>(st, planes, z, n_slabs, slab_elems, z_out, gamma, beta, prelu_a, y, mean, rstd, Cn, HW, bstride, eps, prelu_span, pidx, W, pg); break;
-        case 8:  launch_in_fwd<8>(st, planes, z, n_slabs, slab_elems, z_out, gamma, beta, prelu_a, y, mean, rstd, Cn, HW, bstride, eps, prelu_span, pidx, W, pg); break;
-        case 16: launch_in_fwd<16>(st, planes, z, n_slabs, slab_elems, z_out, gamma, beta, prelu_a, y, mean, rstd, Cn, HW, bstride, eps, prelu_span, pidx, W, pg); break;
-        case 32: launch_in_fwd<32>(st, planes, z, n_slabs, slab_elems, z_out, gamma, beta, prelu_a, y, mean, rstd, Cn, HW, bstride, eps, prelu_span, pidx, W, pg); break;
-        default: launch_in_fwd<64>(st, planes, z, n_slabs, slab_elems, z_out, gamma, beta, prelu_a, y, mean, rstd, Cn, HW, bstride, eps, prelu_span, pidx, W, pg); break;
-    }
+    const KanNormRoute r = norm_route(false, planes, HW, norm_pool_mode(pidx, pg), norm_float2_ok(z, z_out, bstride, HW, slab_elems));
+    bool ok;
+    if (r.kernel == KAN_NORM_REGS && r.pool)                  // lanes own 2x2 windows (float2 accesses)
+        ok = pick_regs_pool2(r, [&](auto v) { launch_in_fwd_regs<decltype(v)::G, decltype(v)::EPL, decltype(v)::PPI, true>(st, r, planes, z, n_slabs, slab_elems, z_out, gamma, beta, prelu_a, y, mean, rstd, Cn, HW, bstride, eps, prelu_span, pidx, W); });
+    else if (r.kernel == KAN_NORM_REGS)
+        ok = pick_regs_plain(r, [&](auto v) { launch_in_fwd_regs<decltype(v)::G, decltype(v)::EPL, decltype(v)::PPI, false>(st, r, planes, z, n_slabs, slab_elems, z_out, gamma, beta, prelu_a, y, mean, rstd, Cn, HW, bstride, eps, prelu_span, pidx, W); });
+    else
+        ok = pick_generic(r, [&](auto v) { launch_in_fwd<decltype(v)::G>(st, r, planes, z, n_slabs, slab_elems, z_out, gamma, beta, prelu_a, y, mean, rstd, Cn, HW, bstride, eps, prelu_span, pidx, W, pg); });
+    if (!ok) return fail("instnorm_fwd: no kernel for the route");
     return launch_ok("instnorm_fwd");
 }
 
@@ -3050,27 +3086,13 @@ static int instnorm_bwd_any(const float* dy, const float* z, const float* mean, 
     if (!dy || !z || !mean || !rstd || !dz || B < 1 || Cn < 1 || HW < 1) return fail("bad instnorm_bwd arguments");
     hipStream_t st = (hipStream_t)stream;
     int planes = B * Cn;
-    if (HW <= 1024 && !pg.k) {                                // register-resident variants: G lanes x EPL elements cover the plane
-#define KAN_INB(G, EPL, PPI) launch_in_bwd_regs<G, EPL, PPI>(st, planes, dy, z, mean, rstd, gamma, beta, prelu_a, dz, dgamma, dbeta, dprelu, Cn, HW, bstride, prelu_span, pidx, W)
-        if (HW <= 4) KAN_INB(4, 1, 4);
-        else if (HW <= 8) KAN_INB(8, 1, 4);
-        else if (HW <= 16) KAN_INB(16, 1, 4);
-        else if (HW <= 32) KAN_INB(32, 1, 4);
-        else if (HW <= 64) KAN_INB(16, 4, 2);       // (8x8 planes: 4 elements per lane, as before)
-        else if (HW <= 128) KAN_INB(64, 2, 2);
-        else if (HW <= 256) KAN_INB(64, 4, 2);
-        else if (HW <= 512) KAN_INB(64, 8, 1);
-        else KAN_INB(64, 16, 1);
-#undef KAN_INB
-        return launch_ok("instnorm_bwd");
-    }
-    switch (pg.k ? group_lanes((HW + 11) / 12) : HW == 64 ? 16 : group_lanes(HW)) {      // 8x8 planes: 4 elements per lane (measured 52 -> 37 us on 256x256x8x8)
-        case 4:  launch_in_bwd<4>(st, planes, dy, z, mean, rstd, gamma, beta, prelu_a, dz, dgamma, dbeta, dprelu, Cn, HW, bstride, prelu_span, pidx, W, pg); break;
-        case 8:  launch_in_bwd<8>(st, planes, dy, z, mean, rstd, gamma, beta, prelu_a, dz, dgamma, dbeta, dprelu, Cn, HW, bstride, prelu_span, pidx, W, pg); break;
-        case 16: launch_in_bwd<16>(st, planes, dy, z, mean, rstd, gamma, beta, prelu_a, dz, dgamma, dbeta, dprelu, Cn, HW, bstride, prelu_span, pidx, W, pg); break;
-        case 32: launch_in_bwd<32>(st, planes, dy, z, mean, rstd, gamma, beta, prelu_a, dz, dgamma, dbeta, dprelu, Cn, HW, bstride, prelu_span, pidx, W, pg); break;
-        default: launch_in_bwd<64>(st, planes, dy, z, mean, rstd, gamma, beta, prelu_a, dz, dgamma, dbeta, dprelu, Cn, HW, bstride, prelu_span, pidx, W, pg); break;
-    }
+    const KanNormRoute r = norm_route(true, planes, HW, norm_pool_mode(pidx, pg), true);
+    bool ok;
+    if (r.kernel == KAN_NORM_REGS)                            // register-resident variants: G lanes x EPL elements cover the plane
+        ok = pick_regs_plain(r, [&](auto v) { launch_in_bwd_regs<decltype(v)::G, decltype(v)::EPL, decltype(v)::PPI>(st, r, planes, dy, z, mean, rstd, gamma, beta, prelu_a, dz, dgamma, dbeta, dprelu, Cn, HW, bstride, prelu_span, pidx, W); });
+    else
+        ok = pick_generic(r, [&](auto v) { launch_in_bwd<decltype(v)::G>(st, r, planes, dy, z, mean, rstd, gamma, beta, prelu_a, dz, dgamma, dbeta, dprelu, Cn, HW, bstride, prelu_span, pidx, W, pg); });
+    if (!ok) return fail("instnorm_bwd: no kernel for the route");
     return launch_ok("instnorm_bwd");
 }
 
@@ -3114,6 +3136,18 @@ int kan_instnorm_prelu_poolk_bwd(const float* dy_pooled, const unsigned char* po
     if (pool_geo(H, W, pool_k, pool_s, &pg)) return -1;
     return instnorm_bwd_any(dy_pooled, z, mean, rstd, gamma, beta, prelu_a, dz, dgamma, dbeta, dprelu, B, Cn, H * W, bstride, prelu_span,
                             pool_idx, W, stream, pg);
+}
+
+int kan_norm_route(int backward, int B, int Cn, int H, int W, long long bstride, int n_slabs, long long slab_elems, int pool2x2, int pool_k,
+                   int pool_s, int aligned8, KanNormRoute* route) {
+    if (!route || n_slabs < 1 || B < 1 || Cn < 1 || H < 1 || W < 1) return fail("bad norm_route arguments");
+    if (pool2x2 && (pool_k || H < 2 || W < 2 || (H & 1) || (W & 1))) return fail("fused 2x2 max-pool needs even H and W");
+    PoolGeo pg{};
+    if (pool_k && pool_geo(H, W, pool_k, pool_s, &pg)) return -1;
+    const int HW = H * W;
+    *route = norm_route(backward != 0, B * Cn, HW, pool_k ? KAN_NORM_POOL_K : pool2x2 ? KAN_NORM_POOL_2X2 : KAN_NORM_POOL_NONE,
+                        aligned8 && norm_float2_ok(nullptr, nullptr, bstride, HW, slab_elems));
+    return 0;
 }
 
 int kan_adamw_step(float* p, const float* g, float* m, float* v, long long n, double lr, double beta1, double beta2, double eps,

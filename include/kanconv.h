@@ -265,6 +265,26 @@ int kan_instnorm_prelu_poolk_bwd(const float* dy_pooled, const unsigned char* po
                                  float* dz, float* dgamma, float* dbeta, float* dprelu,
                                  int B, int Cn, int H, int W, long long bstride, int prelu_span, int pool_k, int pool_s, void* stream);
 
+/* Which kernel variant the six kan_instnorm_prelu* entry points launch for a tensor, and with what launch shape.  Pure host arithmetic, no
+ * device work (like kan_plan); the entry points dispatch from this struct and from nothing else.
+ *   kernel  KAN_NORM_GENERIC: k_in_prelu_fwd / _bwd <G>, 256 threads;  KAN_NORM_REGS: k_in_prelu_fwd_regs / _bwd_regs <G, EPL, PPI, pool, NT>
+ *   G       lanes per (b, channel) plane;  EPL, PPI: elements per lane, plane groups per loop iteration (register kernels; 0 otherwise)
+ *   pool    KAN_NORM_POOL_NONE / _2X2 (even planes, windows never overlap) / _K (general MaxPool2d(pool_k, pool_s))
+ *   lds     general pool: the plane (forward) / its un-pooled gradient (backward) is staged in LDS
+ *   held    generic backward: the plane stays in registers between the two passes (otherwise it is read again)
+ *   blocks  workgroups launched;  strided: the grid is capped and some workgroup runs its grid-stride loop more than once */
+enum { KAN_NORM_GENERIC = 0, KAN_NORM_REGS = 1 };
+enum { KAN_NORM_POOL_NONE = 0, KAN_NORM_POOL_2X2 = 1, KAN_NORM_POOL_K = 2 };
+typedef struct KanNormRoute {
+    int kernel, G, EPL, PPI, NT, pool, lds, held, blocks, strided;
+} KanNormRoute;
+
+/* Fill `route` for the forward (backward = 0) or backward launch over B x Cn planes of H x W pixels.  pool2x2 != 0: the fused MaxPool2d(2, 2)
+ * entry points (H, W even); pool_k != 0: the general ones (pool2x2 must be 0; same limits as kan_instnorm_prelu_poolk_fwd); both 0: no pool.
+ * aligned8: z and z_out are 8-byte aligned (what the forward tests on its pointers before it takes the float2 kernels; ignored otherwise). */
+int kan_norm_route(int backward, int B, int Cn, int H, int W, long long bstride, int n_slabs, long long slab_elems,
+                   int pool2x2, int pool_k, int pool_s, int aligned8, KanNormRoute* route);
+
 /* OPT-IN split-precision forward: NOT reached from kan_conv_fwd, never the default.  Every fp32 operand is cut into three bf16
  * pieces (hi + mid + lo = 24 mantissa bits) and six bf16 MFMA products per 16-deep block are accumulated in fp32: the fp32 result to ~4e-6 of its
  * largest element at K = 20 736 (one fp32 accumulation chain; the exact path sits at ~1e-6), at ~1.7x the speed of the exact fp32 MFMA kernel.

@@ -35,6 +35,7 @@ def test_struct_layouts_match_header():
     assert ctypes.sizeof(L.KanBasis) == 4 * 4 + 2 * 4 + 32 * 4 + 8 and L.KanBasis.chan_table.offset == 152      # + the phase-table pointer
     assert ctypes.sizeof(L.KanPlan) == 22 * 4 + 6 * 8           # 22 ints (incl. kernel-variant and expanded-copy flags), 6 x int64
     assert ctypes.sizeof(L.KanWavGeom) == 16 * 4 + 16 and L.KanWavGeom.wavelet.offset == 60 and L.KanWavGeom.x_bstride.offset == 64
+    assert ctypes.sizeof(L.KanNormRoute) == 10 * 4 and L.KanNormRoute.strided.offset == 36              # 10 ints
 
 
 def _plan(C, O, H, k=3, p=1, s=1, B=4, kind=L.BASIS_BSPLINE, nb=8, order=3, act=L.ACT_SILU, table=None):
