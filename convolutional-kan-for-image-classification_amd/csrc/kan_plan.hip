@@ -415,6 +415,10 @@ int plan_conv(const KanGeom* g, const KanBasis* b, ConvPlan* cp) {
     }
     pl->fwd_target = pl->bwd_data_target = pl->bwd_weight_target = 0;
     const bool rowblk_fwd = halo && g->H == 4 && g->W == 4 && c.fc.TO == 256;
+    // quadrant tiles (32 images x a 2x2 quadrant) where the row-block order is taken and whole 32-image groups exist: same tile count (B / 8),
+    // same splits and slabs -- an internal choice of pixel order, invisible in KanPlan.  Forward only: the same tile in bwd-data issued 25/30 of
+    // the MFMAs and was no faster (its per-image 4-byte gathers and stores)
+    c.quad_fwd = rowblk_fwd && g->B % 32 == 0 && !tuning_off("KAN_QUAD_FWD");
     if (dw) {                                   // direct depthwise kernels: no split-K on the data path, no position-major copies
         pl->fwd_splits = pl->bwd_data_splits = 1;
         pl->bwd_weight_splits = dw_weight_chunks(g);

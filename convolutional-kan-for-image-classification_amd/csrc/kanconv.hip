@@ -521,43 +521,57 @@ __global__ __launch_bounds__(WO * WP * 64, (WO * WP > 4 ? 2 : 4)) void k_conv_fw
                  : "=&v"(r0), "=&v"(r1), "=&v"(r2) : "v"(addrA), "v"(addrB), "n"(oA0), "n"(oA1), "n"(oB) : "memory")
 #define LDS_WAIT3(r0, r1, r2, N) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(r0), "+v"(r1), "+v"(r2) :: "memory")
 
-template <int FAST, int WO, int W, int R, int NIMG>
+template <int FAST, int WO, int W, int R, int NIMG, int QUAD = 0>
 __global__ __launch_bounds__(WO * 2 * 64, ((WO > 2 && !(R * W == 16 && NIMG * W == 32)) ? 2 : 4)) void k_conv_fwd_halo(
     const float* __restrict__ x, const float* __restrict__ wp, float* __restrict__ z, DevGeom g, DevBasis bs, int Opad,
     int n_pairs, int pairs_per_split, long long slab_elems, unsigned x_bytes, int tiles_o) {
     constexpr int TO = WO * 64, TP = 128, NT = WO * 2 * 64, NW = WO * 2, P = fast_planes(FAST), KC = 2 * P, T = 9;
     constexpr int KIND = fast_kind(FAST);
-    constexpr int HW_ = W + 2, HIMG = (R + 2) * HW_, HALO = NIMG * HIMG;          // cells per plane
+    constexpr int HW_ = QUAD ? 3 : W + 2, HIMG = QUAD ? 9 : (R + 2) * HW_, HALO = (QUAD ? 32 : NIMG) * HIMG;          // cells per plane
     constexpr int RPI = 256 / TO, NQ = (KC + RPI - 1) / RPI;
     static_assert(NIMG * R * W == TP && HALO % 2 == 0, "tile shape");
+    static_assert(!QUAD || (R * W == 16 && NIMG * W == 32 && WO == 4), "the quadrant order is a variant of the row-block tile");
     // Whole planes of 4 rows in a tile (4x4 planes): the tile's pixels are ordered row-major ACROSS the images, n = (row, image, column),
     // so a 32-pixel MFMA block is one output row of all 8 images -- and for the taps whose source row leaves the plane (tap row 0 under
     // output row 0, tap row 2 under the last row) the whole block multiplies the zero border: its MFMAs are skipped (exact:
     // the skipped products are all zero).  A wave owns two rows, so it skips half of its work in 3 of the 9 steps; with 8 waves the
     // pixel half is chosen by wave >> 2, which puts one wave of each half on every SIMD -- the matrix pipe of a SIMD then sees 6 instead
     // of 8 MFMAs per k-pair in 6 of 9 steps (with wave & 1 the skipping waves share two SIMDs and the others wait at the step barrier: -2 % only).
-    constexpr bool ROWBLK = (R * W == 16 && NIMG * W == 32 && WO == 4);
+    // QUAD (the same planes, B a multiple of 32): the tile is 32 images x one 2x2 QUADRANT of the plane, pixel column n = block * 32 + image, so a
+    // 32-pixel MFMA block is ONE plane position of 32 images and is wholly live or wholly dead under a tap: exactly the 25 of 36 (position, tap)
+    // products that touch a real pixel are issued (5/6 = 30 of 36 with the row order).  Pixel half w_p holds the quadrant's row w_p, block q its
+    // column q; wave >> 2 again puts one wave of each half on every SIMD, so every SIMD issues 25/36 of the dense MFMAs whatever the pairing --
+    // and with a row per wave a lane holds two NEIGHBOURING outputs and stores them as one 8-byte word (a tile's stores are scattered over 32
+    // images: with the diagonal pairing {corner, interior} / {edge, edge} and 4-byte stores the store cost ate the whole gain on 256 -> 512).
+    // The halo holds the 3x3 input cells the quadrant reaches for each of the 32 images (all real inputs, no zero border; cell row / column =
+    // input row / column - quadrant row / column, 288 cells per plane as before); a dead block's LDS reads may leave its image's cells by up to
+    // 4 words, hence the pad of 4 words on either side.  tools/probe/quad_emul.py restates this index arithmetic in numpy.
+    constexpr bool ROWBLK = (R * W == 16 && NIMG * W == 32 && WO == 4) && !QUAD;
+    constexpr int HPAD = QUAD ? 4 : 0;
     __shared__ __attribute__((aligned(16))) float sW[2 * KC * TO];
-    __shared__ float sH[2 * P * HALO];
+    __shared__ float sH_[2 * P * HALO + 2 * HPAD];
+    float* const sH = sH_ + HPAD;
     __shared__ float sTab[KAN_MAX_TABLE];
     __shared__ float sDump[NT];
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int w_o = ROWBLK ? (wave & 3) : (wave >> 1), w_p = ROWBLK ? (wave >> 2) : (wave & 1);
+    const int w_o = (ROWBLK || QUAD) ? (wave & 3) : (wave >> 1), w_p = (ROWBLK || QUAD) ? (wave >> 2) : (wave & 1);
     const int HoWo = g.Ho * g.Wo, HW = g.H * g.W, Mtot = g.B * HoWo;
     const BlockId blk = xcd_block_order(true);
     const int grp = blk.y / tiles_o;
+    // (QUAD) tile blk.x = 32-image group * 4 + quadrant: the four quadrants of a group are neighbours and share their input lines in L2
+    const int qh = (blk.x >> 1) & 1, qw = blk.x & 1;
     const int px_tile0 = blk.x * TP, o_tile0 = (blk.y - grp * tiles_o) * TO;
     x += (size_t)grp * g.C * HW;
     z += (size_t)grp * g.O * HoWo;
     wp += (size_t)grp * n_pairs * (T * KC) * Opad;
 
     if (tid < KAN_MAX_TABLE) sTab[tid] = bs.tab[tid];
-    for (int i = tid; i < 2 * P * HALO; i += NT) sH[i] = 0.f;              // borders (and out-of-image cells) stay zero for good
+    for (int i = tid; i < 2 * P * HALO + 2 * HPAD; i += NT) sH_[i] = 0.f;  // borders (and out-of-image cells) stay zero for good
 
-    // the tile: NIMG images from b0, rows [h0, h0 + R)
-    const int b0 = px_tile0 / HoWo, h0 = (px_tile0 - b0 * HoWo) / W;
+    // the tile: NIMG images from b0, rows [h0, h0 + R); (QUAD) 32 images from b0, input rows [qh, qh + 3), columns [qw, qw + 3)
+    const int b0 = QUAD ? (blk.x >> 2) * 32 : px_tile0 / HoWo, h0 = QUAD ? 0 : (px_tile0 - b0 * HoWo) / W;
     // cells this thread expands every channel pair (fixed): cell -> (channel of the pair, image, halo row, halo column)
     constexpr int NCELL = 2 * HALO, CPT = (NCELL + NT - 1) / NT;
     int c_src[CPT], c_dst[CPT], c_ch[CPT]; unsigned c_ok = 0;               // x element offset (without channel) / sH offset / channel of the pair
@@ -566,7 +580,7 @@ __global__ __launch_bounds__(WO * 2 * 64, ((WO > 2 && !(R * W == 16 && NIMG * W 
         const int idx = tid + k * NT;
         const int ch = idx / HALO, cell = idx - ch * HALO;
         const int img = cell / HIMG, rc = cell - img * HIMG, hr = rc / HW_, hc = rc - hr * HW_;
-        const int b = b0 + img, h = h0 - 1 + hr, w = hc - 1;
+        const int b = b0 + img, h = QUAD ? qh + hr : h0 - 1 + hr, w = QUAD ? qw + hc : hc - 1;
         const bool ok = idx < NCELL && b < g.B && (unsigned)h < (unsigned)g.H && (unsigned)w < (unsigned)W;
         c_src[k] = b * (int)g.xbs + ch * HW + h * W + w;
         c_dst[k] = ch * (P * HALO) + cell;
@@ -578,11 +592,24 @@ __global__ __launch_bounds__(WO * 2 * 64, ((WO > 2 && !(R * W == 16 && NIMG * W 
     // B-operand addresses of this lane's two pixels (kh2 selects the channel of the pair)
     const int kh2 = lane >> 5;
     unsigned vb[2];
+    int q_hw[2] = {0, 0}; unsigned q_live[2] = {0x1ffu, 0x1ffu};          // (QUAD, wave-uniform) plane position of the wave's two blocks, their live taps
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
         const int n = w_p * 64 + q * 32 + (lane & 31);
         int img = n / (R * W), rem = n - img * (R * W), row = rem / W, col = rem - row * W;
         if (ROWBLK) { row = n / (NIMG * W); rem = n - row * (NIMG * W); img = rem / W; col = rem - img * W; }
+        if (QUAD) {
+            const int h = 2 * qh + w_p, w = 2 * qw + q;           // this wave's row of the quadrant, block q = column q
+            q_hw[q] = h * 4 + w;
+            unsigned m = 0;
+            for (int tap = 0; tap < 9; ++tap) {
+                const int r = tap / 3, t = tap - r * 3;
+                m |= (((unsigned)(h + r - 1) < 4u && (unsigned)(w + t - 1) < 4u) ? 1u : 0u) << tap;
+            }
+            q_live[q] = m;
+            vb[q] = lds_addr(sH + kh2 * (P * HALO) + (lane & 31) * HIMG + (h - qh) * HW_ + (w - qw));
+            continue;
+        }
         vb[q] = lds_addr(sH + kh2 * (P * HALO) + img * HIMG + (row + 1) * HW_ + (col + 1));
     }
     const int ao = w_o * 64 + (lane & 31);
@@ -640,7 +667,8 @@ __global__ __launch_bounds__(WO * 2 * 64, ((WO > 2 && !(R * W == 16 && NIMG * W 
             float fa[2][2], fb[2][2];
             // (ROWBLK) this wave's rows are 2 * w_p and 2 * w_p + 1: which of its two pixel blocks this tap leaves alive
             const int dead = !ROWBLK ? -1 : (r == 0 && w_p == 0) ? 0 : (r == 2 && w_p == 1) ? 1 : -1;
-            const bool live0 = dead != 0, live1 = dead != 1;                  // wave-uniform: scalar branches around two MFMAs each
+            // wave-uniform: scalar branches around two MFMAs each
+            const bool live0 = QUAD ? ((q_live[0] >> tap) & 1u) != 0 : dead != 0, live1 = QUAD ? ((q_live[1] >> tap) & 1u) != 0 : dead != 1;
             LDS_READ4H(fa[0][0], fa[0][1], fb[0][0], fb[0][1], aw, ab0, ab1, 0, 32 * 4, 0);
 #pragma unroll
             for (int kk = 0; kk < P; ++kk) {
@@ -652,11 +680,11 @@ __global__ __launch_bounds__(WO * 2 * 64, ((WO > 2 && !(R * W == 16 && NIMG * W 
                 } else {
                     LDS_WAIT4(fa[c_][0], fa[c_][1], fb[c_][0], fb[c_][1], 0);
                 }
-                if (!ROWBLK || live0) {
+                if (!(ROWBLK || QUAD) || live0) {
                     acc[0][0] = MFMA32(fa[c_][0], fb[c_][0], acc[0][0]);
                     acc[1][0] = MFMA32(fa[c_][1], fb[c_][0], acc[1][0]);
                 }
-                if (!ROWBLK || live1) {
+                if (!(ROWBLK || QUAD) || live1) {
                     acc[0][1] = MFMA32(fa[c_][0], fb[c_][1], acc[0][1]);
                     acc[1][1] = MFMA32(fa[c_][1], fb[c_][1], acc[1][1]);
                 }
@@ -667,6 +695,18 @@ __global__ __launch_bounds__(WO * 2 * 64, ((WO > 2 && !(R * W == 16 && NIMG * W 
 
     // ---- store (as k_conv_fwd)
     float* zs = z + (size_t)blk.z * slab_elems;
+    if (QUAD) {                                              // n = (block, image): the lane's two blocks are neighbours in the plane's row
+        float* zb = zs + (size_t)(b0 + (lane & 31)) * g.ybs + q_hw[0];
+#pragma unroll
+        for (int mi = 0; mi < 2; ++mi) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int o = o_tile0 + w_o * 64 + mi * 32 + mfma_row(r, lane);
+                if (o < g.O) *reinterpret_cast<float2*>(zb + (size_t)o * HoWo) = make_float2(acc[mi][0][r], acc[mi][1][r]);
+            }
+        }
+        return;
+    }
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni) {
         int px = px_tile0 + w_p * 64 + ni * 32 + (lane & 31);
@@ -2762,16 +2802,21 @@ int kan_conv_fwd(const float* x, const float* xn, const float* wp, float* z, con
         dim3 gridh(c.tiles_p, c.tiles_o * ngroups(g), pl.fwd_splits);
         dispatch_fast<ON_HALO_FWD>(cp.fast, [&](auto fv) {
             constexpr int F = decltype(fv)::value;
-            auto launch = [&](auto wo, auto w, auto r, auto nimg) {       // (output waves, plane width, rows per tile, images per tile)
+            auto launch = [&](auto wo, auto w, auto r, auto nimg, auto quad) {       // (output waves, plane width, rows per tile, images per tile, quadrant order)
                 constexpr int WOV = decltype(wo)::value;
-                hipLaunchKernelGGL((k_conv_fwd_halo<F, WOV, decltype(w)::value, decltype(r)::value, decltype(nimg)::value>), gridh, dim3(WOV * 128), 0,
-                                   st, x, wp, z, dgh, dbh, pl.Opad, n_pairs, pps, pl.fwd_slab_elems, x_bytes, c.tiles_o);
+                hipLaunchKernelGGL((k_conv_fwd_halo<F, WOV, decltype(w)::value, decltype(r)::value, decltype(nimg)::value, decltype(quad)::value>), gridh,
+                                   dim3(WOV * 128), 0, st, x, wp, z, dgh, dbh, pl.Opad, n_pairs, pps, pl.fwd_slab_elems, x_bytes, c.tiles_o);
             };
             auto planes = [&](auto wo) {
-                if (g->W == 32) launch(wo, IC<32>{}, IC<4>{}, IC<1>{});
-                else if (g->W == 16) launch(wo, IC<16>{}, IC<8>{}, IC<1>{});
-                else if (g->W == 8) launch(wo, IC<8>{}, IC<8>{}, IC<2>{});
-                else launch(wo, IC<4>{}, IC<4>{}, IC<8>{});
+                if constexpr (decltype(wo)::value == 4) {
+                    // 32 images x one quadrant (it stores 8-byte words: a z or a batch stride that is not 8-byte aligned keeps the row blocks)
+                    if (g->W == 4 && cp.quad_fwd && ((uintptr_t)z & 7u) == 0 && (g->y_bstride & 1) == 0 && (pl.fwd_slab_elems & 1) == 0)
+                        return launch(wo, IC<4>{}, IC<4>{}, IC<8>{}, IC<1>{});
+                }
+                if (g->W == 32) launch(wo, IC<32>{}, IC<4>{}, IC<1>{}, IC<0>{});
+                else if (g->W == 16) launch(wo, IC<16>{}, IC<8>{}, IC<1>{}, IC<0>{});
+                else if (g->W == 8) launch(wo, IC<8>{}, IC<8>{}, IC<2>{}, IC<0>{});
+                else launch(wo, IC<4>{}, IC<4>{}, IC<8>{}, IC<0>{});
             };
             if constexpr (fast_has(F, ON_BIG_TILES)) {
                 if (c.TO == 256) return planes(IC<4>{});

@@ -172,16 +172,26 @@ def _live_fraction(which: str, H: int, W: int, Ho: int, Wo: int, kh: int, kw: in
 _ROW_BLOCK_BIT = {"fwd": 1, "bwd_data": 2, "bwd_weight": 0}          # KanPlan.row_blocks: which launches run row-ordered 4x4 blocks
 
 
+def _quadrant_order(geom, plan, which: str) -> bool:
+    """The launch runs quadrant tiles (32 images x a 2x2 quadrant of a 4x4 plane) instead of row blocks: the planner's predicate restated
+    (kan_plan.hip, plan_conv: `c.quad_fwd = rowblk_fwd && g->B % 32 == 0`; the forward only, bwd-data keeps its row blocks).  The launcher also wants an 8-byte aligned
+    output, which every torch allocation is."""
+    return which == "fwd" and bool(plan.row_blocks & 1) and geom.B % 32 == 0
+
+
 def _executed_flops(geom, plan, which: str) -> float:
     """Dense count minus the dead (position, tap) products a position-major launch skips (plan.*_target > 0 marks one)."""
     target = {"fwd": plan.fwd_target, "bwd_data": plan.bwd_data_target, "bwd_weight": plan.bwd_weight_target}[which]
     dense = _conv_flops(geom, plan)
+    g = geom
     if target <= 0:
-        # row-ordered 4x4 launches skip the blocks of the first / last row under the tap row that leaves the plane: 2/3 * 1/4 of the work
+        # row-ordered 4x4 launches skip the blocks of the first / last row under the tap row that leaves the plane: 2/3 * 1/4 of the work;
+        # the quadrant order skips exactly the dead (position, tap) blocks
+        if _quadrant_order(geom, plan, which):
+            return dense * _live_fraction(which, g.H, g.W, g.Ho, g.Wo, g.kh, g.kw, g.sh, g.sw, g.ph, g.pw, g.dh, g.dw)
         if plan.row_blocks & _ROW_BLOCK_BIT[which]:
             return dense * (5.0 / 6.0)
         return dense
-    g = geom
     return dense * _live_fraction(which, g.H, g.W, g.Ho, g.Wo, g.kh, g.kw, g.sh, g.sw, g.ph, g.pw, g.dh, g.dw)
 
 

@@ -100,7 +100,8 @@ typedef struct KanPlan {
                                      unlock structural-zero tap skipping; optional, NULL keeps the image-major path */
     int bwd_weight_expanded;      /* the weight gradient reads the expanded copy (kan_conv_bwd_weight_expanded) */
     int row_blocks;               /* informational: bit 0 / bit 1 = the forward / bwd-data launch orders 4x4 planes in row blocks and skips
-                                     the 1/6 of its MFMA work that multiplies the zero border */
+                                     the 1/6 of its MFMA work that multiplies the zero border; with B a multiple of 32 the forward orders
+                                     them in quadrant tiles instead (32 images x a 2x2 quadrant) and skips exactly the dead 11/36 */
     int e_pm_wanted, fwd_expanded;/* small padded planes: the weight gradient (and, with fwd_expanded, the forward) reads the EXPANDED
                                      position-major copy: build it with kan_position_major_expanded (e_pm_elems floats) and call
                                      kan_conv_bwd_weight_expanded / kan_conv_fwd_expanded */
