@@ -440,13 +440,14 @@ inline DevGeom dev_geom(const KanGeom* g) {
 }
 inline DevBasis dev_basis(const KanBasis* b) {
     DevBasis d;
-    d.kind = b->kind; d.nb = b->n_basis; d.order = b->order; d.act = b->act;
+    d.kind = b->kind; d.nb = b->n_basis; d.act = b->act;
+    d.order = KAN_ORDER_MODE(b->order); d.first = KAN_ORDER_FIRST(b->order);      // the one place the packed `order` is taken apart: kernels see DevBasis.first
     d.hb = b->act != KAN_ACT_NONE ? 1 : 0; d.P = b->n_basis + d.hb;
     d.p0 = b->p0; d.p1 = b->p1; d.inv_h = 0.f; d.g0 = 0.f; d.gN = 0.f;
     for (int i = 0; i < KAN_MAX_TABLE; ++i) d.tab[i] = b->table[i];
-    d.ctab = (b->kind == KAN_BASIS_RELU || b->kind == KAN_BASIS_GRAM) ? b->chan_table : nullptr;
+    d.ctab = (b->kind == KAN_BASIS_RELU || b->kind == KAN_BASIS_GRAM || b->kind == KAN_BASIS_POLY) ? b->chan_table : nullptr;
     if (b->kind == KAN_BASIS_BSPLINE) {
-        int nk = b->n_basis + b->order + 1;
+        int nk = b->n_basis + d.order + 1;
         float span = b->table[nk - 1] - b->table[0];
         d.inv_h = span > 0.f ? (float)(nk - 1) / span : 0.f;
         d.g0 = b->table[0]; d.gN = b->table[nk - 1];

@@ -16,7 +16,10 @@ struct DevBasis {            // by-value kernel argument
     float p0, p1, inv_h;
     float g0, gN;            // B-spline: first / last knot (the span outside which every basis is zero)
     float tab[KAN_MAX_TABLE];
-    const float* ctab;       // device-memory parameters: ReLU-KAN per-channel phases [C][2][nb]; Gram coefficients [nb]
+    int first;               // Poly / Cheby / Fourier: the family's own index of the first plane this launch emits (a plane window; else 0).
+                             // It sits in what was the padding in front of the pointer: no other member moves, the argument block keeps its size
+    const float* ctab;       // device-memory parameters: ReLU-KAN per-channel phases [C][2][nb]; Gram coefficients [nb];
+                             // Poly: the coefficient table [3 (first + nb)] where it does not fit `tab` (null: `tab`, first == 0)
 };
 
 // ---------------------------------------------------------------- transcendentals of the hot loops
@@ -159,11 +162,23 @@ __device__ __forceinline__ bool bspline_uniform(int S, float x, const float* kn,
 // KIND is a template parameter so that each kernel instantiation carries ONE basis family's code
 // (all families inlined at every staging site made the kernels thrash the instruction cache).
 // `c` is the channel inside its group; only families with per-channel parameters (ReLU-KAN) look at it.
+template <int KIND, bool DERIV, typename F>
+__device__ __forceinline__ void kan_planes_each(const DevBasis& bs, const float* tabs, float xa, float xb, int c, F&& emit);
+
 template <int KIND, bool DERIV>
 __device__ __forceinline__ void kan_planes(const DevBasis& bs, const float* tabs, float xa, float xb,
                                            float (&v)[KAN_PMAX], int c = 0) {
 #pragma unroll
     for (int p = 0; p < KAN_PMAX; ++p) v[p] = 0.f;
+    if (KIND == KAN_BASIS_POLY || KIND == KAN_BASIS_FOURIER || KIND == KAN_BASIS_CHEBY) {
+        // The families whose planes can start in the middle (bs.first) are written down ONCE, in kan_planes_each below: its run-time loop
+        // over the family's true index hands over plane p, which lands in v[p] by a select per slot (v stays in registers).
+        kan_planes_each<KIND, DERIV>(bs, tabs, xa, xb, c, [&](int p, float val) {
+#pragma unroll
+            for (int q = 0; q < KAN_PMAX; ++q) v[q] = q == p ? val : v[q];
+        });
+        return;
+    }
     const int hb = bs.hb;
     if (hb) v[0] = DERIV ? kan_act_grad(bs.act, xa) : kan_act(bs.act, xa);
 
@@ -189,26 +204,6 @@ __device__ __forceinline__ void kan_planes(const DevBasis& bs, const float* tabs
                 float u = (xb - tabs[j]) / dn;
                 float e = expf(-(u * u));
                 v[p] = DERIV ? e * (-2.0f * u) / dn : e;
-            }
-        }
-    } else if (KIND == KAN_BASIS_FOURIER) {
-        // fourier_kan_layers.py:163-187: planes cos(k x), k = 1..G, then sin(k x), k = 1..G (nb = 2G).  ONE sincos(x); the harmonics by the
-        // angle-addition recurrence (c_{k+1}, s_{k+1}) = (c_k c_1 - s_k s_1, s_k c_1 + c_k s_1), restarted at the head of the sine block -- a few ulp
-        // per step against the reference's cos(fl(k x)), whose own argument rounding is of the same size (|k x| ulp); 2G sincosf calls per value
-        // were most of this family's expansion time.
-        const int G = bs.nb >> 1;
-        float s1, c1;
-        sincosf(xb, &s1, &c1);
-        float ck = c1, sk = s1, kf = 1.f;
-#pragma unroll
-        for (int p = 0; p < KAN_PMAX; ++p) {
-            const int j = p - hb;
-            if (j >= 0 && j < bs.nb) {
-                if (j == G) { ck = c1; sk = s1; kf = 1.f; }
-                const bool is_cos = j < G;
-                v[p] = is_cos ? (DERIV ? -kf * sk : ck) : (DERIV ? kf * ck : sk);
-                const float cn = ck * c1 - sk * s1, sn = sk * c1 + ck * s1;
-                ck = cn; sk = sn; kf += 1.f;
             }
         }
     } else if (KIND == KAN_BASIS_RELU) {
@@ -254,55 +249,6 @@ __device__ __forceinline__ void kan_planes(const DevBasis& bs, const float* tabs
                 }
             }
         }
-    } else if (KIND == KAN_BASIS_POLY) {
-        // Three-term-recurrence families (bessel / fibonacci / gegenbauer / hermite / laguerre / lucas / taylor / jacobi
-        // _kan_layers.py, compute_*_basis): on t = tanh(x) (order = 1) or t = x (order = 0),
-        //   T_0 = c0,  T_1 = a1 t + b1,  T_k = (A_k t + B_k) T_{k-1} + C_k T_{k-2}   (k >= 2)
-        // with the per-family coefficients precomputed on the host: tab = [c0, a1, b1, A_2, B_2, C_2, A_3, ...].
-        // The derivative runs the differentiated recurrence alongside: T_k' = A_k T_{k-1} + (A_k t + B_k) T_{k-1}' + C_k T_{k-2}'.
-        const float t = bs.order ? tanhf(xb) : xb;
-        const float chain = bs.order ? (1.0f - t * t) : 1.0f;
-        float Tm = tabs[0], Tc = tabs[1] * t + tabs[2];
-        float Dm = 0.f, Dc = tabs[1];
-#pragma unroll
-        for (int p = 0; p < KAN_PMAX; ++p) {
-            const int k = p - hb;
-            if (k >= 0 && k < bs.nb) {
-                if (k == 0) v[p] = DERIV ? 0.f : Tm;
-                else {
-                    v[p] = DERIV ? Dc * chain : Tc;
-                    if (k + 1 < bs.nb) {
-                        const float A = tabs[3 * k], B = tabs[3 * k + 1], Cc = tabs[3 * k + 2];      // coefficients of T_{k+1}
-                        const float s = A * t + B;
-                        const float Tn = s * Tc + Cc * Tm, Dn = A * Tc + s * Dc + Cc * Dm;
-                        Tm = Tc; Tc = Tn; Dm = Dc; Dc = Dn;
-                    }
-                }
-            }
-        }
-    } else {
-        // cheby_kan_layers.py:93-96  T_k = cos(k * acos(t)), t = clamp(tanh x, lo, hi), evaluated by the three-term
-        // recurrence T_k = 2 t T_{k-1} - T_{k-2} (SURVEY.md section 8(a): max |delta| 9.8e-7 vs the reference for
-        // degree 4).  Gradient as autograd forms it: dT_k/dx = k sin(k th)/sin(th) * (1 - tanh^2 x) inside the clamp
-        // = k U_{k-1}(t) (1 - t0^2), zero where the clamp is active (clamp passes gradient on [lo, hi]).
-        const float t0 = tanhf(xb);
-        const float t = fminf(fmaxf(t0, bs.p0), bs.p1);
-        const bool inside = (t0 >= bs.p0) && (t0 <= bs.p1);
-        const float chain = inside ? (1.0f - t0 * t0) : 0.f;
-        float Tm = 1.f, Tc = t;              // T_{k-1}, T_k   at k = 1
-        float Um = 0.f, Uc = 1.f;            // U_{k-2}, U_{k-1} at k = 1  (U_{-1} = 0, U_0 = 1)
-#pragma unroll
-        for (int p = 0; p < KAN_PMAX; ++p) {
-            const int k = p - hb;
-            if (k >= 0 && k < bs.nb) {
-                if (k == 0) v[p] = DERIV ? 0.f : 1.f;
-                else {
-                    v[p] = DERIV ? (float)k * Uc * chain : Tc;
-                    const float Tn = 2.f * t * Tc - Tm; Tm = Tc; Tc = Tn;
-                    const float Un = 2.f * t * Uc - Um; Um = Uc; Uc = Un;
-                }
-            }
-        }
     }
 }
 
@@ -311,6 +257,9 @@ __device__ __forceinline__ void kan_planes(const DevBasis& bs, const float* tabs
 // unrolled over all KAN_PMAX planes with run-time plane counts, which is what made the generic (run-time P) conv kernels 8 000 lines of ISA
 // with 150 - 280 spilled scalar registers (each spill a v_readlane / v_writelane, i.e. a vector instruction next to the fp32 MFMAs).  The
 // generic staging (stage_unit) and the generic bwd-data epilogue use this form; formulas and their order are kan_planes' own.
+// Poly, Cheby and Fourier are written down HERE only (kan_planes calls this form for them): their planes can start in the middle (bs.first, a
+// plane window of a layer with more planes than one launch holds), and one run-time loop over the true index is what makes a window's planes
+// the same instructions -- the same bits -- as the planes of a launch that starts at 0.
 template <int KIND, bool DERIV, typename F>
 __device__ __forceinline__ void kan_planes_each(const DevBasis& bs, const float* tabs, float xa, float xb, int c, F&& emit) {
     const int hb = bs.hb, nb = bs.nb;
@@ -338,15 +287,22 @@ __device__ __forceinline__ void kan_planes_each(const DevBasis& bs, const float*
             emit(hb + j, DERIV ? e * (-2.0f * u) / dn : e);
         }
     } else if (KIND == KAN_BASIS_FOURIER) {
-        const int G = nb >> 1;
+        // fourier_kan_layers.py:163-187: planes cos(k x), k = 1..G, then sin(k x), k = 1..G (nb = 2G).  ONE sincos(x); the harmonics by the
+        // angle-addition recurrence (c_{k+1}, s_{k+1}) = (c_k c_1 - s_k s_1, s_k c_1 + c_k s_1), restarted at the head of the sine block -- a few ulp
+        // per step against the reference's cos(fl(k x)), whose own argument rounding is of the same size (|k x| ulp); 2G sincosf calls per value
+        // were most of this family's expansion time.
+        // A window (bs.first = f skipped frequencies, nb = 2m) holds cos(k x), k = f+1 .. f+m, then sin(k x) for the same k: ONE loop over the
+        // true frequency in both blocks with a conditional emit, so plane k is the same instructions whatever f is.
+        const int f = bs.first, Gt = f + (nb >> 1);
         float s1, c1;
         sincosf(xb, &s1, &c1);
         float ck = c1, sk = s1, kf = 1.f;
+        int slot = hb;                                           // planes leave in plane order: the window's cosines, then its sines
 #pragma unroll 1
-        for (int j = 0; j < nb; ++j) {
-            if (j == G) { ck = c1; sk = s1; kf = 1.f; }
-            const bool is_cos = j < G;
-            emit(hb + j, is_cos ? (DERIV ? -kf * sk : ck) : (DERIV ? kf * ck : sk));
+        for (int j = 0; j < 2 * Gt; ++j) {
+            if (j == Gt) { ck = c1; sk = s1; kf = 1.f; }
+            const bool is_cos = j < Gt;
+            if ((is_cos ? j : j - Gt) >= f) emit(slot++, is_cos ? (DERIV ? -kf * sk : ck) : (DERIV ? kf * ck : sk));      // frequency - 1 >= first
             const float cn = ck * c1 - sk * s1, sn = sk * c1 + ck * s1;
             ck = cn; sk = sn; kf += 1.f;
         }
@@ -379,33 +335,53 @@ __device__ __forceinline__ void kan_planes_each(const DevBasis& bs, const float*
             }
         }
     } else if (KIND == KAN_BASIS_POLY) {
+        // Three-term-recurrence families (bessel / fibonacci / gegenbauer / hermite / laguerre / lucas / taylor / jacobi
+        // _kan_layers.py, compute_*_basis): on t = tanh(x) (order = 1) or t = x (order = 0),
+        //   T_0 = c0,  T_1 = a1 t + b1,  T_k = (A_k t + B_k) T_{k-1} + C_k T_{k-2}   (k >= 2)
+        // with the per-family coefficients precomputed on the host: [c0, a1, b1, A_2, B_2, C_2, A_3, ...] -- the by-value table (`tabs`, at
+        // most 11 planes), or the device table bs.ctab of 3 (first + nb) floats where that is too short (uniform reads, as GRAM's cf[k + 1]).
+        // The derivative runs the differentiated recurrence alongside: T_k' = A_k T_{k-1} + (A_k t + B_k) T_{k-1}' + C_k T_{k-2}'.
+        // ONE loop over the true index k = 0 .. first + nb - 1 with a conditional emit: the planes of a window (first > 0) are bit for bit
+        // the planes the same k gets in a launch that starts at 0.
+        const float* dt = bs.ctab;
+        const bool dev = dt != nullptr;
         const float t = bs.order ? tanhf(xb) : xb;
         const float chain = bs.order ? (1.0f - t * t) : 1.0f;
-        float Tm = tabs[0], Tc = tabs[1] * t + tabs[2];
-        float Dm = 0.f, Dc = tabs[1];
-        emit(hb, DERIV ? 0.f : Tm);
+        const float c0 = dev ? dt[0] : tabs[0], a1 = dev ? dt[1] : tabs[1], b1 = dev ? dt[2] : tabs[2];
+        float Tm = c0, Tc = a1 * t + b1;
+        float Dm = 0.f, Dc = a1;
+        const int first = bs.first, end = first + nb;
 #pragma unroll 1
-        for (int k = 1; k < nb; ++k) {
-            emit(hb + k, DERIV ? Dc * chain : Tc);
-            if (k + 1 < nb) {
-                const float A = tabs[3 * k], B = tabs[3 * k + 1], Cc = tabs[3 * k + 2];      // coefficients of T_{k+1}
+        for (int k = 0; k < end; ++k) {
+            if (k >= first) emit(hb + k - first, k == 0 ? (DERIV ? 0.f : Tm) : (DERIV ? Dc * chain : Tc));
+            if (k >= 1 && k + 1 < end) {
+                const float A = dev ? dt[3 * k] : tabs[3 * k], B = dev ? dt[3 * k + 1] : tabs[3 * k + 1],
+                            Cc = dev ? dt[3 * k + 2] : tabs[3 * k + 2];      // coefficients of T_{k+1}
                 const float sA = A * t + B;
                 const float Tn = sA * Tc + Cc * Tm, Dn = A * Tc + sA * Dc + Cc * Dm;
                 Tm = Tc; Tc = Tn; Dm = Dc; Dc = Dn;
             }
         }
     } else {      // Chebyshev
+        // cheby_kan_layers.py:93-96  T_k = cos(k * acos(t)), t = clamp(tanh x, lo, hi), evaluated by the three-term
+        // recurrence T_k = 2 t T_{k-1} - T_{k-2} (SURVEY.md section 8(a): max |delta| 9.8e-7 vs the reference for
+        // degree 4).  Gradient as autograd forms it: dT_k/dx = k sin(k th)/sin(th) * (1 - tanh^2 x) inside the clamp
+        // = k U_{k-1}(t) (1 - t0^2), zero where the clamp is active (clamp passes gradient on [lo, hi]).
+        // One loop over the true degree k with a conditional emit, as the recurrence families above.
         const float t0 = tanhf(xb);
         const float t = fminf(fmaxf(t0, bs.p0), bs.p1);
         const bool inside = (t0 >= bs.p0) && (t0 <= bs.p1);
         const float chain = inside ? (1.0f - t0 * t0) : 0.f;
-        float Tm = 1.f, Tc = t, Um = 0.f, Uc = 1.f;
-        emit(hb, DERIV ? 0.f : 1.f);
+        float Tm = 1.f, Tc = t;              // T_{k-1}, T_k   at k = 1
+        float Um = 0.f, Uc = 1.f;            // U_{k-2}, U_{k-1} at k = 1  (U_{-1} = 0, U_0 = 1)
+        const int first = bs.first, end = first + nb;
 #pragma unroll 1
-        for (int k = 1; k < nb; ++k) {
-            emit(hb + k, DERIV ? (float)k * Uc * chain : Tc);
-            const float Tn = 2.f * t * Tc - Tm; Tm = Tc; Tc = Tn;
-            const float Un = 2.f * t * Uc - Um; Um = Uc; Uc = Un;
+        for (int k = 0; k < end; ++k) {
+            if (k >= first) emit(hb + k - first, k == 0 ? (DERIV ? 0.f : 1.f) : (DERIV ? (float)k * Uc * chain : Tc));
+            if (k >= 1) {
+                const float Tn = 2.f * t * Tc - Tm; Tm = Tc; Tc = Tn;
+                const float Un = 2.f * t * Uc - Um; Um = Uc; Uc = Un;
+            }
         }
     }
 }

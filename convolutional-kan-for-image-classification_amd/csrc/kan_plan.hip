@@ -28,11 +28,17 @@ int check(const KanGeom* g, const KanBasis* b) {
     if (g->x_bstride < (long long)ngroups(g) * g->C * g->H * g->W || g->y_bstride < (long long)ngroups(g) * g->O * g->Ho * g->Wo)
         return fail("batch stride smaller than groups * channels * plane");
     if (b->kind < 0 || b->kind > KAN_BASIS_GRAM) return fail("unknown basis kind");
+    const int first = KAN_ORDER_FIRST(b->order), mode = KAN_ORDER_MODE(b->order);      // plane windows (kanconv.h): order = mode | first << 8
+    if (first < 0) return fail("negative first-plane offset");
+    if (first != 0 && b->kind != KAN_BASIS_POLY && b->kind != KAN_BASIS_CHEBY && b->kind != KAN_BASIS_FOURIER)
+        return fail("a first-plane offset (upper bits of order) is taken by the Poly, Cheby and Fourier bases only");
     if (b->kind == KAN_BASIS_GRAM && (b->order < 0 || b->order >= b->n_basis || b->n_basis < 2 || b->act == KAN_ACT_NONE))
         return fail("Gram basis needs degree >= 1, an activation, and a mode (order) in 0..degree-1");
     if (b->kind == KAN_BASIS_RELU && (b->order < 0 || b->order > 2)) return fail("ReLU basis mode (order) must be 0, 1 or 2");
     if (b->kind == KAN_BASIS_FOURIER && (b->n_basis & 1)) return fail("Fourier basis needs an even plane count (cos and sin per frequency)");
-    if (b->kind == KAN_BASIS_POLY && (b->n_basis > 11 || b->order < 0 || b->order > 1)) return fail("bad recurrence-basis parameters");
+    if (b->kind == KAN_BASIS_POLY && (mode < 0 || mode > 1)) return fail("bad recurrence-basis parameters");
+    if (b->kind == KAN_BASIS_POLY && first + b->n_basis > 11 && !b->chan_table)
+        return fail("a recurrence basis of first + n_basis > 11 planes needs its coefficients as a device table (chan_table)");
     if (b->act < KAN_ACT_NONE || b->act > KAN_ACT_GELU_TANH) return fail("unknown activation");
     int P = b->n_basis + (b->act != KAN_ACT_NONE);
     if (b->n_basis < 1 || P > KAN_MAX_PLANES) return fail("planes per channel exceed KAN_MAX_PLANES");
@@ -56,6 +62,8 @@ int check(const KanGeom* g, const KanBasis* b) {
 
 // Compile-time specialisation available?  (FAST_* in kan_internal.h)
 int fast_variant(const KanBasis* b) {
+    // a plane window (first != 0) or a device coefficient table is what the compile-time specs do not know: a tail window of 4 planes is no degree-3 layer
+    if (KAN_ORDER_FIRST(b->order) != 0 || (b->kind == KAN_BASIS_POLY && b->chan_table)) return FAST_GENERIC;
     if (b->kind == KAN_BASIS_BSPLINE && b->n_basis == 8 && b->order == 3)
         return b->act == KAN_ACT_SILU ? FAST_BSPLINE_SILU : b->act == KAN_ACT_GELU ? FAST_BSPLINE_GELU : FAST_GENERIC;
     if (b->kind == KAN_BASIS_RBF && b->act == KAN_ACT_SILU && (b->n_basis == 8 || b->n_basis == 5)) return b->n_basis == 8 ? FAST_RBF8 : FAST_RBF5;

@@ -221,6 +221,59 @@ class _HipLayer(nn.Module):
     def conv_spec(self) -> ops.ConvSpec:
         return self._spec(**self._basis_kw())
 
+    # ---- plane windows: any degree / grid size on launches of at most KAN_MAX_PLANES planes
+    plane_window = L.KAN_MAX_PLANES     # planes per launch, base included (a test lowers it to force windows on a layer that fits one launch)
+    _window_unit = 1                    # planes per window index (FourierKAN: 2, a cos and a sin plane per frequency)
+
+    def _check_planes_3d(self):
+        """3-D layers run one launch set per depth tap (conv3d_stage) and have no window loop: above the plane limit they raise here."""
+        kw = self._basis_kw()
+        planes = kw["n_basis"] + int(kw["act"] != L.ACT_NONE)
+        if getattr(self, "ndim", 2) == 3 and planes > L.KAN_MAX_PLANES:
+            raise NotImplementedError(f"{planes} planes per channel exceed KAN_MAX_PLANES = {L.KAN_MAX_PLANES}: 3-D layers have no plane windows "
+                                      "(the 1-D and 2-D layers take any degree / grid size)")
+
+    def _window_kw(self, kw, j0, j1, base):
+        """The basis description of window [j0, j1) of the layer's `_basis_kw()`: how a family starts in the middle.  Recurrence families and
+        ChebyKAN: the kernels run the recurrence from 0 and emit from plane `first` on; the coefficient table stays whole."""
+        return dict(kw, first=j0, n_basis=j1 - j0, act=kw["act"] if base else L.ACT_NONE)
+
+    def _window_weights(self, ws, j0, j1, n):
+        """Basis weights of window [j0, j1) out of n: per-group [O, C*n, ...] (channel index c*n + j) -> [O, C*(j1 - j0), ...]."""
+        return [w.reshape(w.shape[0], w.shape[1] // n, n, *w.shape[2:])[:, :, j0:j1].reshape(w.shape[0], -1, *w.shape[2:]) for w in ws]
+
+    def _plane_windows(self):
+        """The library holds at most KAN_MAX_PLANES = 16 planes per channel in one launch; the reference takes any degree / grid_size.
+        The conv stage is linear in the planes, so a layer of more planes runs one launch set per window of <= `plane_window` planes
+        (the first carries the base branch) and sums the results: [(spec, j0, j1, with_base), ...], [j0, j1) in window units."""
+        kw = self._basis_kw()
+        u = self._window_unit
+        n, has_act = kw["n_basis"] // u, kw["act"] != L.ACT_NONE
+        out, j0 = [], 0
+        while j0 < n:
+            base = j0 == 0 and has_act
+            j1 = min(n, j0 + max(1, (self.plane_window - int(base)) // u))
+            out.append((self._spec(**self._window_kw(kw, j0, j1, base)), j0, j1, base))
+            j0 = j1
+        return out
+
+    def _conv_stage(self, spec, xa, xb, wb, ws, phases=None):
+        """The conv stage of a (lifted) layer: one launch set, or -- more planes than one launch holds -- the sum over plane windows
+        (differentiable: autograd routes the gradient of each weight / phase slice back into its Parameter).  `xb`: the basis tensor where
+        it is not `xa` (host-applied activation, FastKAN's normalised input, Legendre's x_n): a window without the base branch reads it alone."""
+        def stage(sp, x, xn, w_base, w_basis, ph):
+            if ph is None:
+                return ops.kan_conv(sp, x, xn, w_base, w_basis)
+            return ops.kan_conv_phased(sp, x, ph, w_base, w_basis, xn=xn)
+        if spec.n_basis + int(spec.has_base) <= self.plane_window:
+            return stage(spec, xa, xb, wb, ws, phases)
+        n, z = spec.n_basis // self._window_unit, None
+        for wspec, j0, j1, base in self._plane_windows():
+            part = stage(wspec, xa if base else (xb if xb is not None else xa), xb if base else None, wb if base else [],
+                         self._window_weights(ws, j0, j1, n), phases[:, :, j0:j1].contiguous() if phases is not None else None)
+            z = part if z is None else z + part
+        return z
+
     def _build(self, conv_class, norm_class, cg, og, basis=None, planes=0, prelus=False, norm_dim=None, plane_major=0):
         """The per-group module lists, created and initialised in the order every family's reference constructor uses (a seeded
         construction draws the same weights): ``base_conv``, the basis convs `planes * cg -> og` under the attribute name `basis`,
@@ -311,7 +364,7 @@ class _FusedTailLayer(_HipLayer):
         ws = self._w(getattr(self, self._basis))
         prelus = [m.weight for m in self.prelus] if self._has_base else None
         xa, xb = self._base_input(x) if self._has_base else (x, None)      # (act(x), x) when the host applies the activation
-        windowed = spec.n_basis + int(spec.has_base) > L.KAN_MAX_PLANES    # more planes than one launch holds: KANConvNDLayer._windowed_stage
+        windowed = spec.n_basis + int(spec.has_base) > self.plane_window    # more planes than one launch holds: _HipLayer._conv_stage
         if not windowed and xb is None and _fusable_instnorm(self.layer_norm) and all(p.numel() == 1 for p in prelus or ()):
             gam, bet = _norm_affine(self.layer_norm)
             if pool and self.ndim == 2 and self.dropout is None and ops.pool_fusable(pool, *spec.out_hw(x.shape[2], x.shape[3])):
@@ -319,7 +372,7 @@ class _FusedTailLayer(_HipLayer):
             y = self._lower(ops.kan_conv_in_prelu(spec, x, wb, ws, gam, bet, prelus, eps=self.layer_norm[0].eps))
         else:
             # other norm classes (e.g. BatchNorm2d), a host-applied activation or plane windows: HIP conv stage, then the un-fused tail
-            y = self._norm_prelu(self._windowed_stage(xa, xb, wb, ws) if windowed else ops.kan_conv(spec, xa, xb, wb, ws))
+            y = self._norm_prelu(self._conv_stage(spec, xa, xb, wb, ws))
         if self.dropout is not None:
             y = self.dropout(y)
         return _unfused_pool(y, pool) if pool else y
@@ -351,39 +404,16 @@ class KANConvNDLayer(_FusedTailLayer):
         self.grid = torch.linspace(self.grid_range[0] - h * spline_order, self.grid_range[1] + h * spline_order,
                                    grid_size + 2 * spline_order + 1, dtype=torch.float32)
         self._act_code = _act_code(self.base_activation, host_ok=True)
+        self._check_planes_3d()
 
     def _basis_kw(self):
         return dict(kind=L.BASIS_BSPLINE, n_basis=self.grid_size + self.spline_order, order=self.spline_order,
                     act=self._act_code, p0=0.0, p1=0.0, table=tuple(float(v) for v in self.grid.tolist()))
 
-    def _plane_windows(self):
-        """The library holds at most KAN_MAX_PLANES = 16 planes per channel in one launch; the reference takes any grid_size
-        (kan_layers.py:117-131).  B-spline basis j is a function of knots j .. j + order + 1 alone, so bases [j0, j1) of this layer ARE the
-        bases of a B-spline layer built on knots[j0 : j1 + order + 1] -- and the conv stage is linear in the planes.  A layer of more than
-        16 planes therefore runs one launch set per window of <= 16 planes (the first carries the base branch) and sums the results:
-        [(spec, j0, j1, with_base), ...]."""
-        kw = self._basis_kw()
-        n, S, knots = kw["n_basis"], self.spline_order, kw["table"]
-        out, j0, first = [], 0, True
-        while j0 < n:
-            has_base = first and self._act_code != L.ACT_NONE
-            j1 = min(n, j0 + L.KAN_MAX_PLANES - (1 if has_base else 0))
-            out.append((self._spec(**dict(kw, n_basis=j1 - j0, act=self._act_code if has_base else L.ACT_NONE, table=knots[j0:j1 + S + 1])),
-                        j0, j1, has_base))
-            j0, first = j1, False
-        return out
-
-    def _windowed_stage(self, xa, xb, wb, ws):
-        """Conv stage of a layer with more than 16 planes per channel: sum over plane windows (differentiable: autograd routes the
-        gradient of each weight slice back into spline_conv[g].weight)."""
-        n = self.grid_size + self.spline_order
-        z = None
-        for spec, j0, j1, has_base in self._plane_windows():
-            wsl = [w.reshape(w.shape[0], w.shape[1] // n, n, *w.shape[2:])[:, :, j0:j1].reshape(w.shape[0], -1, *w.shape[2:]) for w in ws]
-            part = ops.kan_conv(spec, xa if has_base else (xb if xb is not None else xa), None if (not has_base or xb is None) else xb,
-                                wb if has_base else [], wsl)
-            z = part if z is None else z + part
-        return z
+    def _window_kw(self, kw, j0, j1, base):
+        """B-spline basis j is a function of knots j .. j + order + 1 alone, so bases [j0, j1) of this layer ARE the bases of a B-spline
+        layer built on knots[j0 : j1 + order + 1] (kan_layers.py:117-131 takes any grid_size): a window is a slice of the knots."""
+        return dict(kw, n_basis=j1 - j0, act=kw["act"] if base else L.ACT_NONE, table=kw["table"][j0:j1 + self.spline_order + 1])
 
 
 class KANConv3DLayer(KANConvNDLayer):
@@ -444,6 +474,11 @@ class FastKANConvNDLayer(_HipLayer):
         self.dropout = _dropout2d(dropout, ndim)
         self._act_code = _act_code(self.base_activation, host_ok=True)
         self._centres = tuple(float(v) for v in self.rbf.grid.detach().tolist())
+        self._check_planes_3d()
+
+    def _window_kw(self, kw, j0, j1, base):
+        """A FastKAN window is a slice of the centres (the denominator is the layer's)."""
+        return dict(kw, n_basis=j1 - j0, act=kw["act"] if base else L.ACT_NONE, table=kw["table"][j0:j1])
 
     def _basis_kw(self):
         return dict(kind=L.BASIS_RBF, n_basis=self.grid_size, order=0, act=self._act_code, p0=float(self.rbf.denominator), p1=0.0,
@@ -471,7 +506,7 @@ class FastKANConvNDLayer(_HipLayer):
             xn = ops.instance_norm(xn.contiguous(), *_gamma_beta(self.layer_norm), eps=self.layer_norm[0].eps)
         else:
             xn = self._lift(torch.cat([self.layer_norm[g](xs[:, g * cg:(g + 1) * cg]) for g in range(self.groups)], dim=1))
-        return self._lower(ops.kan_conv(self.conv_spec(), self._lift(self._base_input(x)[0]), xn, self._w(self.base_conv), self._w(self.spline_conv)))
+        return self._lower(self._conv_stage(self.conv_spec(), self._lift(self._base_input(x)[0]), xn, self._w(self.base_conv), self._w(self.spline_conv)))
 
 
 class FastKANConv1DLayer(FastKANConvNDLayer):
@@ -528,6 +563,7 @@ class ChebyKANConvNDLayer(_FusedTailLayer):
             # cheby_kan_layers.py:88-90 (normal_ first, then overwritten; `**` requires an int kernel_size, as there)
             nn.init.normal_(conv.weight, mean=0.0, std=1 / (input_dim * (degree + 1) * kernel_size ** ndim))
             nn.init.kaiming_normal_(conv.weight, mode='fan_in', nonlinearity='relu')
+        self._check_planes_3d()
 
     def _basis_kw(self):
         lo = float(np.float32(-1 + self.epsilon))       # torch.clamp casts its Python-float bounds to fp32

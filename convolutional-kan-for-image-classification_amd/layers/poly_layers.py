@@ -68,8 +68,7 @@ class _RecurrenceKANConvNDLayer(_FusedTailLayer):
         self._build(conv_class, norm_class, self.input_dim_group, self.output_dim_group, "poly_conv", self._n_planes(), prelus=True)
         self.dropout = _dropout2d(dropout, ndim)
         self._act_code = _act_code(self.base_activation, host_ok=True)
-        if self._n_planes() > 11:
-            raise NotImplementedError("the HIP recurrence basis holds at most 11 planes per channel (degree <= 10)")
+        self._check_planes_3d()      # 1-D / 2-D: any degree (above 11 planes the coefficients travel as a device table, above 16 in plane windows)
 
     def _n_planes(self) -> int:
         return self.degree + 1
@@ -405,8 +404,6 @@ class FourierKANConvNDLayer(_FusedTailLayer):
         _check_groups(groups, input_dim, output_dim)
         if grid_size < 1:
             raise ValueError('grid_size must be at least 1')
-        if 2 * grid_size + 1 > L.KAN_MAX_PLANES:
-            raise NotImplementedError(f"the HIP conv stage holds at most {L.KAN_MAX_PLANES} planes per channel (grid_size <= 7)")
         self.input_dim, self.output_dim, self.kernel_size, self.grid_size = input_dim, output_dim, kernel_size, grid_size
         self.groups, self.padding, self.stride, self.dilation, self.ndim = groups, padding, stride, dilation, ndim
         self.base_activation = base_activation() if base_activation is not None else nn.Identity()
@@ -416,6 +413,16 @@ class FourierKANConvNDLayer(_FusedTailLayer):
         self._build(conv_class, norm_class, self.input_dim_group, self.output_dim_group, "fourier_conv", 2 * grid_size, prelus=True)
         self.dropout = _dropout2d(dropout, ndim)
         self._act_code = _act_code(self.base_activation, host_ok=True)
+        self._check_planes_3d()
+
+    _window_unit = 2             # a window is a range of FREQUENCIES [f0, f1): cos(k x), k = f0+1 .. f1, then sin(k x) for the same k
+
+    def _window_kw(self, kw, j0, j1, base):
+        return dict(kw, first=j0, n_basis=2 * (j1 - j0), act=kw["act"] if base else L.ACT_NONE)
+
+    def _window_weights(self, ws, j0, j1, n):
+        """The [O, C, 2, G, ...] view of the channel index c*2G + (k-1) (cosines) / c*2G + G + (k-1) (sines), cut to frequencies [j0, j1)."""
+        return [w.reshape(w.shape[0], w.shape[1] // (2 * n), 2, n, *w.shape[2:])[:, :, :, j0:j1].reshape(w.shape[0], -1, *w.shape[2:]) for w in ws]
 
     def _basis_kw(self):
         return dict(kind=L.BASIS_FOURIER, n_basis=2 * self.grid_size, order=0, act=self._act_code, p0=0.0, p1=0.0, table=())
@@ -466,8 +473,8 @@ class _PlaneMajorPolyLayer(_HipLayer):
         self.conv_w_fun, self.ndim, self.norm_kwargs = conv_w_fun, ndim, norm_kwargs
         self.dropout = _dropout2d(dropout)
         _check_groups(groups, input_dim, output_dim)
-        if degree < 1 or degree > 10:
-            raise NotImplementedError(f"{name} on the HIP path needs 1 <= degree <= 10")
+        if degree < 1:
+            raise NotImplementedError(f"{name} on the HIP path needs degree >= 1")
         if not isinstance(kernel_size, int):
             raise TypeError(f"{name} takes an int kernel_size (the reference builds poly_weights from `kernel_size` repeated ndim times)")
         self._build(conv_class, norm_class, input_dim // groups, output_dim // groups, plane_major=degree + 1)
@@ -508,7 +515,7 @@ class JacobiKANConvNDLayer(_PlaneMajorPolyLayer):
         return dict(kind=L.BASIS_POLY, n_basis=n, order=1, act=L.ACT_IDENTITY, p0=0.0, p1=0.0, table=_table(self._coeffs(), n))
 
     def forward(self, x):
-        z = ops.kan_conv(self.conv_spec(), x, None, [m.weight for m in self.base_conv], _channel_major(self.poly_weights, self.degree + 1))
+        z = self._conv_stage(self.conv_spec(), x, None, [m.weight for m in self.base_conv], _channel_major(self.poly_weights, self.degree + 1))
         return self._norm_act(z)
 
 
@@ -546,8 +553,8 @@ class LegendreKANConvNDLayer(_PlaneMajorPolyLayer):
         xn = (2 * (xg - lo) / (hi - lo) - 1).reshape(B, G * cg, H, W)
         if self.dropout is not None:
             xn = self.dropout(xn)
-        z = ops.kan_conv(self.conv_spec(), x, xn.contiguous(), [m.weight for m in self.base_conv],
-                         _channel_major(self.poly_weights, self.degree + 1))
+        z = self._conv_stage(self.conv_spec(), x, xn.contiguous(), [m.weight for m in self.base_conv],       # x_n is the second input of every window
+                             _channel_major(self.poly_weights, self.degree + 1))
         return self._norm_act(z)
 
 
@@ -579,7 +586,7 @@ class BersnsteinKANConvNDLayer(_PlaneMajorPolyLayer):
         return dict(kind=L.BASIS_POLY, n_basis=n, order=1, act=L.ACT_IDENTITY, p0=0.0, p1=0.0, table=_table(c, n))
 
     def forward(self, x):
-        z = ops.kan_conv(self.conv_spec(), x, None, [m.weight for m in self.base_conv], [self.poly_weights[g] for g in range(self.groups)])
+        z = self._conv_stage(self.conv_spec(), x, None, [m.weight for m in self.base_conv], [self.poly_weights[g] for g in range(self.groups)])
         return self._norm_act(z)
 
 

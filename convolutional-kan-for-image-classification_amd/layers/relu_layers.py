@@ -38,8 +38,6 @@ class ReLUConvNDLayer(_HipLayer):
         self.conv_w_fun, self.ndim, self.norm_kwargs, self.p_dropout = conv_w_fun, ndim, norm_kwargs, dropout
         self.dropout = _dropout2d(dropout, ndim)
         _check_groups(groups, input_dim, output_dim)
-        if g + k + 1 > L.KAN_MAX_PLANES:
-            raise NotImplementedError(f"g + k + 1 = {g + k + 1} planes per channel exceed KAN_MAX_PLANES = {L.KAN_MAX_PLANES}")
         cg, og = input_dim // groups, output_dim // groups
         self._build(conv_class, norm_class, cg, og, "relukan_conv", g + k)
         phase_low = torch.arange(-k, g) / g                      # relu_kan_layers.py:97-98
@@ -47,6 +45,9 @@ class ReLUConvNDLayer(_HipLayer):
         dims = (1, cg, k + g) + (1,) * ndim
         self.phase_low = nn.Parameter(phase_low[None, :].expand(cg, -1).reshape(*dims).clone(), requires_grad=train_ab)
         self.phase_high = nn.Parameter(phase_high[None, :].expand(cg, -1).reshape(*dims).clone(), requires_grad=train_ab)
+
+    def _window_kw(self, kw, j0, j1, base):
+        return dict(kw, n_basis=j1 - j0, act=kw["act"] if base else L.ACT_NONE)      # the phases are sliced with the weights
 
     def _basis_kw(self):
         return dict(kind=L.BASIS_RELU, n_basis=self.g + self.k, order=0, act=_act_code(self.base_activation, host_ok=True), p0=float(self.r),
@@ -58,8 +59,9 @@ class ReLUConvNDLayer(_HipLayer):
             x = self.dropout(x)                                  # relu_kan_layers.py:120-121: on the input, both branches see it
         phases = torch.stack([self.phase_low.reshape(cg, n), self.phase_high.reshape(cg, n)], dim=1)
         xa, xb = self._base_input(x)                              # (act(x), x) when the host applies the activation (no device functor for the module)
-        z = ops.kan_conv_phased(self.conv_spec(), self._lift(xa), phases, self._w(self.base_conv), self._w(self.relukan_conv),
-                                xn=self._lift(xb) if xb is not None else None)
+        # more than KAN_MAX_PLANES planes: plane windows, each on a differentiable contiguous slice phases[:, :, j0:j1] (_HipLayer._conv_stage)
+        z = self._conv_stage(self.conv_spec(), self._lift(xa), self._lift(xb) if xb is not None else None, self._w(self.base_conv),
+                             self._w(self.relukan_conv), phases=phases)
         return self._norm_act(z)
 
 

@@ -44,6 +44,7 @@ class ConvSpec:
     padding: Tuple[int, int]
     dilation: Tuple[int, int]
     groups: int = 1
+    first: int = 0                # plane window of a Poly / Cheby / Fourier basis: the family's index of the first plane (frequency) emitted
 
     @property
     def has_base(self) -> bool:
@@ -54,9 +55,17 @@ class ConvSpec:
         return (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
 
 
+def _device_table(spec: ConvSpec) -> bool:
+    """A recurrence (Poly) basis whose coefficients do not fit the by-value table: the kernels read them from device memory."""
+    return spec.kind == L.BASIS_POLY and len(spec.table) > L.KAN_MAX_TABLE
+
+
 def _basis_struct(spec: ConvSpec) -> L.KanBasis:
     b = L.KanBasis()
-    b.kind, b.n_basis, b.order, b.act, b.p0, b.p1 = spec.kind, spec.n_basis, spec.order, spec.act, spec.p0, spec.p1
+    b.kind, b.n_basis, b.act, b.p0, b.p1 = spec.kind, spec.n_basis, spec.act, spec.p0, spec.p1
+    b.order = spec.order | (spec.first << 8)          # KAN_ORDER_PACK (include/kanconv.h)
+    if _device_table(spec):
+        return b                                      # chan_table is set per call (_with_table)
     if len(spec.table) > L.KAN_MAX_TABLE:
         raise L.KanConvError(f"basis table of {len(spec.table)} entries exceeds KAN_MAX_TABLE={L.KAN_MAX_TABLE}")
     for i, v in enumerate(spec.table):
@@ -76,7 +85,13 @@ def _plan_cached(spec: ConvSpec, B: int, Cg: int, H: int, W: int, Og: int, C_tot
     g.groups = spec.groups
     b = _basis_struct(spec)
     p = L.KanPlan()
-    L.check(L.load().kan_plan(C.byref(g), C.byref(b), C.byref(p)), "kan_plan")
+    bp = b
+    if _device_table(spec):
+        # the plan is pure host arithmetic and keyed by the spec alone, not the device: it sees a stand-in for the table pointer that
+        # every launch sets on its own copy (_with_table); the cached struct keeps NULL, which the launchers' checks reject
+        bp = L.KanBasis.from_buffer_copy(b)
+        bp.chan_table = 1
+    L.check(L.load().kan_plan(C.byref(g), C.byref(bp), C.byref(p)), "kan_plan")
     return g, b, p
 
 
@@ -92,6 +107,23 @@ def _with_phases(basis: L.KanBasis, phases: Optional[torch.Tensor], mode: int = 
         return basis
     b = L.KanBasis.from_buffer_copy(basis)
     b.chan_table, b.order = phases.data_ptr(), mode
+    return b
+
+
+_TABLES: "dict[tuple, torch.Tensor]" = {}           # (coefficient table, device) -> fp32 device tensor; the cache keeps it alive
+
+
+def _with_table(basis: L.KanBasis, spec: ConvSpec, device) -> L.KanBasis:
+    """Per-call copy of a cached basis struct carrying the device pointer of a long recurrence-coefficient table
+    ([c0, a1, b1, A_2, B_2, C_2, ...], padded to 3 floats per plane).  Not a module buffer: state_dict() keys stay the reference's."""
+    if not _device_table(spec):
+        return basis
+    key = (spec.table, torch.device(device))
+    t = _TABLES.get(key)
+    if t is None:
+        t = _TABLES[key] = torch.tensor(list(spec.table) + [0.0] * 3, dtype=torch.float32, device=device)
+    b = L.KanBasis.from_buffer_copy(basis)
+    b.chan_table = t.data_ptr()
     return b
 
 
@@ -418,7 +450,7 @@ def _conv_forward(spec: ConvSpec, x, xn, w_base, w_basis, need_dgrad: bool = Tru
     Ct = x.shape[1]
     plan_key = _plan_key(spec, x.shape, w_basis[0].shape[0])
     geom, basis, plan = _plan_cached(*plan_key)
-    basis = _with_phases(basis, phases)
+    basis = _with_table(_with_phases(basis, phases), spec, x.device)
     st = _stream(x)
     z = torch.empty((plan.fwd_splits, geom.B, geom.O * spec.groups, geom.Ho, geom.Wo), device=x.device, dtype=torch.float32)
     wp, wd = _pack(lib, spec, geom, basis, plan, plan_key, w_base, w_basis, need_dgrad, phases, x.device, st)
@@ -484,7 +516,7 @@ def _conv_backward(spec: ConvSpec, x, xn, packed, dz, need_x: bool, need_xn: boo
     Ot = dz.shape[1]
     Og = Ot // G
     geom, basis, plan = _plan_cached(*_plan_key(spec, x.shape, Og))
-    basis = _with_phases(basis, phases, mode)
+    basis = _with_table(_with_phases(basis, phases, mode), spec, x.device)
     kh, kw = spec.kernel
     st = _stream(x)
     xs = xn if xn is not None else x

@@ -62,7 +62,9 @@ typedef struct KanGeom {
  *   Poly     : three-term-recurrence families (Bessel, Fibonacci, Gegenbauer, Hermite, Laguerre, Lucas, Taylor, Jacobi:
  *              layers/<family>_kan_layers.py compute_*_basis).  n_basis planes T_0..T_{n-1} of t = tanh(x) (order = 1)
  *              or t = x (order = 0):  T_0 = table[0], T_1 = table[1]*t + table[2],
- *              T_k = (table[3k-3]*t + table[3k-2]) * T_{k-1} + table[3k-1] * T_{k-2} for k >= 2;  n_basis <= 11
+ *              T_k = (table[3k-3]*t + table[3k-2]) * T_{k-1} + table[3k-1] * T_{k-2} for k >= 2.  `table` holds 11 planes;
+ *              a longer basis (or a plane window, below) passes the same coefficients as a device table: chan_table =
+ *              [c0, a1, b1, A_2, B_2, C_2, ...], 3 * (first + n_basis) floats, read instead of `table` when non-NULL
  *   Fourier  : n_basis = 2*grid_size planes cos(k x), k = 1..grid_size, then sin(k x)
  *              (layers/fourier_kan_layers.py:163-187)
  *   ReLU     : n_basis = g + k planes  (r * relu(x - lo[c][j]) * relu(hi[c][j] - x))^2, p0 = r = 4 g^2 / (k+1)^2
@@ -78,12 +80,25 @@ typedef struct KanGeom {
  *              unused; one row for the whole layer).  `order` = 0: the basis; m >= 1: its derivative w.r.t. c_{m+1}
  *              (base plane zero), for the coefficient gradient through kan_conv_bwd_weight as for ReLU.
  * `act` is the base-branch activation (KAN_ACT_NONE: no base branch, no base weight).
- * Planes per channel P = n_basis + (act != KAN_ACT_NONE); P <= KAN_MAX_PLANES. */
+ * Planes per channel P = n_basis + (act != KAN_ACT_NONE); P <= KAN_MAX_PLANES.
+ *
+ * Plane windows.  The conv stage is linear in the planes, so a layer of more planes than one launch holds runs one launch set per
+ * window of <= KAN_MAX_PLANES planes and sums the results.  Poly, Cheby and Fourier planes depend on the planes below them, so their
+ * launches take a first-plane offset in the upper bits of `order`:
+ *     order = KAN_ORDER_PACK(mode, first)       mode = the `order` value described above (low 8 bits), first >= 0
+ * The launch emits the family's planes first .. first + n_basis - 1 (Poly: T_first ..; Cheby: T_first ..; Fourier: `first` counts
+ * skipped FREQUENCIES -- n_basis = 2m planes cos(k x), k = first+1 .. first+m, then sin(k x) for the same k), bit for bit the planes
+ * the same indices get in a launch that starts at 0.  Poly needs chan_table as soon as first + n_basis > 11.  The other kinds take
+ * first = 0 only (a B-spline / RBF / ReLU window is a slice of the knots / centres / phases).  Windowed launches run the generic kernels. */
+#define KAN_ORDER_PACK(mode, first) ((int)(mode) | ((int)(first) << 8))
+#define KAN_ORDER_MODE(order) ((int)(order) & 0xff)
+#define KAN_ORDER_FIRST(order) ((int)(order) >> 8)
 typedef struct KanBasis {
     int kind, n_basis, order, act;
     float p0, p1;
     float table[KAN_MAX_TABLE];
-    const float* chan_table;      /* device pointer: KAN_BASIS_RELU [C][2][n_basis] floats, KAN_BASIS_GRAM [n_basis] floats; else NULL */
+    const float* chan_table;      /* device pointer: KAN_BASIS_RELU [C][2][n_basis] floats, KAN_BASIS_GRAM [n_basis] floats,
+                                     KAN_BASIS_POLY NULL or the coefficient table [3 * (first + n_basis)] floats; else NULL */
 } KanBasis;
 
 /* Launch plan for one geometry: split counts and workspace sizes (bytes). */
