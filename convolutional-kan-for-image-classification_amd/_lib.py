@@ -18,6 +18,7 @@ KAN_MAX_TABLE = 32
 KAN_FP_WORDS = 192
 BASIS_BSPLINE, BASIS_RBF, BASIS_CHEBY, BASIS_POLY, BASIS_FOURIER, BASIS_RELU, BASIS_GRAM = 0, 1, 2, 3, 4, 5, 6
 ACT_NONE, ACT_IDENTITY, ACT_GELU, ACT_SILU, ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_GELU_TANH = -1, 0, 1, 2, 3, 4, 5, 6
+ORDER_QUAD_FWD, ORDER_ROWBLK8_FWD, ORDER_QUAD_BWD_DATA = 1, 2, 4          # kan_tile_orders bits (KAN_ORDER_*)
 
 
 class KanGeom(C.Structure):
@@ -60,6 +61,7 @@ SIGNATURES = {
     "kan_version": (C.c_char_p, []),
     "kan_last_error": (C.c_char_p, []),
     "kan_plan": (_I, [_GP, _BP, C.POINTER(KanPlan)]),
+    "kan_tile_orders": (_I, [_GP, _BP]),
     "kan_pack_weights": (_I, [_P, _P, _P, _P, _GP, _BP, _P]),
     "kan_pack_cacheable": (_I, [_GP, _BP]),
     "kan_pack_weights_cached": (_I, [_P, _P, _P, _P, _GP, _BP, _P, _I, _I, _I, _P]),

@@ -176,6 +176,8 @@ struct ConvPlan {
     bool pm_fwd, pm_bwd_data, pm_bwd_weight;     // position-major launches offered (taken when the caller passes the copies)
     bool rowblk_bwd_data;                 // 4x4 planes: row-ordered pixel blocks in the image-major bwd-data launch
     bool quad_fwd;                        // ... B a multiple of 32: the halo forward takes quadrant tiles instead (exact tap skipping)
+    bool quad_bd;                         // ... and bwd-data takes quadrant tiles when the caller passes dz_pm (single-tensor specs)
+    bool rowblk8_fwd;                     // 8x8 planes, 256-output tiles, B a multiple of 4: the halo forward takes half-plane tiles in row order (1/12 skipped)
     bool pmdma_xcd, pm_lpt, pm_xcd;       // expanded launches: XCD order of the forward, longest-first and XCD order of the weight gradient
     FwdCfg fc;                            // tap-major / halo / expanded forward tiles
     BdCfg bd;                             // bwd-data tiles

@@ -424,9 +424,14 @@ int plan_conv(const KanGeom* g, const KanBasis* b, ConvPlan* cp) {
     pl->fwd_target = pl->bwd_data_target = pl->bwd_weight_target = 0;
     const bool rowblk_fwd = halo && g->H == 4 && g->W == 4 && c.fc.TO == 256;
     // quadrant tiles (32 images x a 2x2 quadrant) where the row-block order is taken and whole 32-image groups exist: same tile count (B / 8),
-    // same splits and slabs -- an internal choice of pixel order, invisible in KanPlan.  Forward only: the same tile in bwd-data issued 25/30 of
-    // the MFMAs and was no faster (its per-image 4-byte gathers and stores)
+    // same splits and slabs -- an internal choice of pixel order, invisible in KanPlan
     c.quad_fwd = rowblk_fwd && g->B % 32 == 0 && !tuning_off("KAN_QUAD_FWD");
+    // bwd-data on the same tile, its dz copies fed from the position-major copy the caller passes for the expanded weight gradient (128 contiguous bytes per
+    // (output, position) and 32 images); without dz_pm the launcher keeps the row blocks
+    c.quad_bd = c.rowblk_bwd_data && g->B % 32 == 0 && !tuning_off("KAN_QUAD_BD");
+    // 8x8 planes: row blocks on half-plane tiles of 4 images (k_conv_fwd_halo<4, 8, 4, 4>) instead of whole planes of 2: the same B / 2 tiles, splits
+    // and slabs, again invisible in KanPlan (row_blocks stays 0 for these geometries)
+    c.rowblk8_fwd = halo && g->H == 8 && g->W == 8 && c.fc.TO == 256 && g->B % 4 == 0 && !tuning_off("KAN_ROWBLK8_FWD");
     if (dw) {                                   // direct depthwise kernels: no split-K on the data path, no position-major copies
         pl->fwd_splits = pl->bwd_data_splits = 1;
         pl->bwd_weight_splits = dw_weight_chunks(g);

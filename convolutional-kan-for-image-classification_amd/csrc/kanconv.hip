@@ -546,7 +546,12 @@ __global__ __launch_bounds__(WO * 2 * 64, ((WO > 2 && !(R * W == 16 && NIMG * W 
     // The halo holds the 3x3 input cells the quadrant reaches for each of the 32 images (all real inputs, no zero border; cell row / column =
     // input row / column - quadrant row / column, 288 cells per plane as before); a dead block's LDS reads may leave its image's cells by up to
     // 4 words, hence the pad of 4 words on either side.  tools/probe/quad_emul.py restates this index arithmetic in numpy.
-    constexpr bool ROWBLK = (R * W == 16 && NIMG * W == 32 && WO == 4) && !QUAD;
+    // The row order carries over to 8x8 planes with a HALF-plane tile, 4 images x 4 rows x 8 columns (B a multiple of 4): tile t = images 4 (t >> 1) .. + 3,
+    // rows 4 (t & 1) .. + 3 -- the same B / 2 tiles as the 2-image tile -- and a 32-pixel block is one plane row of the 4 images.  Only the block of plane
+    // row 0 (tap row 0) or of plane row H - 1 (tap row 2) is dead, so a tile skips one of its four blocks in three of the nine taps: 1/12 of the
+    // MFMAs, every tile alike (top-half tiles skip in their pixel half 0, bottom-half tiles in half 1).
+    constexpr bool ROWBLK = (NIMG * W == 32 && R == 4 && WO == 4) && !QUAD;
+    constexpr bool HALFPL = ROWBLK && W == 8;               // tiles are half planes of 8 rows
     constexpr int HPAD = QUAD ? 4 : 0;
     __shared__ __attribute__((aligned(16))) float sW[2 * KC * TO];
     __shared__ float sH_[2 * P * HALO + 2 * HPAD];
@@ -571,7 +576,8 @@ __global__ __launch_bounds__(WO * 2 * 64, ((WO > 2 && !(R * W == 16 && NIMG * W 
     for (int i = tid; i < 2 * P * HALO + 2 * HPAD; i += NT) sH_[i] = 0.f;  // borders (and out-of-image cells) stay zero for good
 
     // the tile: NIMG images from b0, rows [h0, h0 + R); (QUAD) 32 images from b0, input rows [qh, qh + 3), columns [qw, qw + 3)
-    const int b0 = QUAD ? (blk.x >> 2) * 32 : px_tile0 / HoWo, h0 = QUAD ? 0 : (px_tile0 - b0 * HoWo) / W;
+    const int b0 = QUAD ? (blk.x >> 2) * 32 : HALFPL ? (blk.x >> 1) * NIMG : px_tile0 / HoWo;
+    const int h0 = QUAD ? 0 : HALFPL ? (blk.x & 1) * R : (px_tile0 - b0 * HoWo) / W;
     // cells this thread expands every channel pair (fixed): cell -> (channel of the pair, image, halo row, halo column)
     constexpr int NCELL = 2 * HALO, CPT = (NCELL + NT - 1) / NT;
     int c_src[CPT], c_dst[CPT], c_ch[CPT]; unsigned c_ok = 0;               // x element offset (without channel) / sH offset / channel of the pair
@@ -665,8 +671,8 @@ __global__ __launch_bounds__(WO * 2 * 64, ((WO > 2 && !(R * W == 16 && NIMG * W 
             const unsigned sh = (unsigned)(((r - 1) * HW_ + (t - 1)) * 4);
             const unsigned aw = lds_addr(sW + buf * (KC * TO) + kh2 * TO + ao), ab0 = vb[0] + sh, ab1 = vb[1] + sh;
             float fa[2][2], fb[2][2];
-            // (ROWBLK) this wave's rows are 2 * w_p and 2 * w_p + 1: which of its two pixel blocks this tap leaves alive
-            const int dead = !ROWBLK ? -1 : (r == 0 && w_p == 0) ? 0 : (r == 2 && w_p == 1) ? 1 : -1;
+            // (ROWBLK) this wave's rows are h0 + 2 * w_p and h0 + 2 * w_p + 1: which of its two pixel blocks this tap leaves alive
+            const int dead = !ROWBLK ? -1 : (r == 0 && w_p == 0 && h0 == 0) ? 0 : (r == 2 && w_p == 1 && h0 + R == g.H) ? 1 : -1;
             // wave-uniform: scalar branches around two MFMAs each
             const bool live0 = QUAD ? ((q_live[0] >> tap) & 1u) != 0 : dead != 0, live1 = QUAD ? ((q_live[1] >> tap) & 1u) != 0 : dead != 1;
             LDS_READ4H(fa[0][0], fa[0][1], fb[0][0], fb[0][1], aw, ab0, ab1, 0, 32 * 4, 0);
@@ -712,7 +718,7 @@ __global__ __launch_bounds__(WO * 2 * 64, ((WO > 2 && !(R * W == 16 && NIMG * W 
         int px = px_tile0 + w_p * 64 + ni * 32 + (lane & 31);
         if (ROWBLK) {                                        // n = (row, image, column) -> the plane-major pixel index
             const int l = lane & 31;
-            px = px_tile0 + (l >> 2) * (R * W) + (w_p * 2 + ni) * W + (l & 3);
+            px = (b0 + l / W) * HoWo + (h0 + w_p * 2 + ni) * W + l % W;
         }
         if (px >= Mtot) continue;
         const int b = px / HoWo, hw = px - b * HoWo;
@@ -769,6 +775,39 @@ __device__ __forceinline__ void wave_reduce_scatter(float (&v)[M], int lane, int
 // outer tap rows: a mixed step holds 8 outputs of tap (0, t) in its first four k-pairs and the same 8 outputs of tap (2, t) in the last
 // four -- the waves of rows 0-1 skip a block in the second half, those of rows 2-3 in the first: 24 instead of 32 MFMAs each.  The middle
 // tap row keeps plain 16-output steps.  Step index: [0, 3 n_ob) plain (t, output block), then (t, 8-output group) mixed.
+// RB = 2 (the same planes, B a multiple of 32, dz given as its position-major copy dz_pm[(o * 16 + position) * B + image]): the tile is 32 images x one 2x2
+// QUADRANT of the input plane, column n = block * 32 + image, tile blk.x = 32-image group * 4 + quadrant.  A 32-pixel block is one plane position and is
+// wholly live or wholly dead under a tap (the forward's rule with the tap mirrored): exactly the 25 of 36 (position, tap) blocks with a source are issued.
+// The four waves sit one per SIMD, so the blocks are paired diagonally -- pixel half 0 = {corner, interior}, half 1 = {edge, edge} -- and the halves hold
+// 2/2 live blocks in four taps, 1/1 in four and 1/0 in one: 13/18 of dense between barriers.  Depth steps stay plain (tap, 16 outputs).  The dz tile is
+// sG[block][16 outputs][32 images]: the source of (block, output) under a tap is 128 contiguous bytes of dz_pm, so wave w copies block w with two 16-byte
+// LDS-DMA instructions (8 outputs each), a fixed per-lane offset and the (tap, output block) part in the scalar offset; dead blocks are not copied.
+// tools/probe/quad_bwd_emul.py restates this index arithmetic in numpy.
+// One step on that tile: operand B k-rows are 32 floats apart, the wave's second block 512 floats on; l0 / l1 = the wave's blocks alive (wave-uniform)
+#define KAN_MFMA_STEP_QUAD(NK, addrA, LDA, addrB, l0, l1)                                                                           \
+    do {                                                                                                                           \
+        float fa_[2][2], fb_[2][2];                                                                                                \
+        LDS_READ4(fa_[0][0], fa_[0][1], fb_[0][0], fb_[0][1], addrA, addrB, 0, 32 * 4, 0, 512 * 4);                                \
+        _Pragma("unroll") for (int kk = 0; kk < (NK); ++kk) {                                                                       \
+            const int c_ = kk & 1, n_ = c_ ^ 1;                                                                                    \
+            if (kk + 1 < (NK)) {                                                                                                   \
+                LDS_READ4(fa_[n_][0], fa_[n_][1], fb_[n_][0], fb_[n_][1], addrA, addrB, (2 * (kk + 1)) * (LDA) * 4,                \
+                          (2 * (kk + 1)) * (LDA) * 4 + 128, (2 * (kk + 1)) * 32 * 4, (2 * (kk + 1)) * 32 * 4 + 512 * 4);           \
+                LDS_WAIT4(fa_[c_][0], fa_[c_][1], fb_[c_][0], fb_[c_][1], 4);                                                      \
+            } else {                                                                                                               \
+                LDS_WAIT4(fa_[c_][0], fa_[c_][1], fb_[c_][0], fb_[c_][1], 0);                                                      \
+            }                                                                                                                      \
+            if (l0) {                                                                                                              \
+                acc[0][0] = MFMA32(fa_[c_][0], fb_[c_][0], acc[0][0]);                                                             \
+                acc[1][0] = MFMA32(fa_[c_][1], fb_[c_][0], acc[1][0]);                                                             \
+            }                                                                                                                      \
+            if (l1) {                                                                                                              \
+                acc[0][1] = MFMA32(fa_[c_][0], fb_[c_][1], acc[0][1]);                                                             \
+                acc[1][1] = MFMA32(fa_[c_][1], fb_[c_][1], acc[1][1]);                                                             \
+            }                                                                                                                      \
+        }                                                                                                                          \
+    } while (0)
+
 template <int KIND, int FAST, int RB = 0>
 __global__ __launch_bounds__(256, 4) void k_conv_bwd_data(
     const float* __restrict__ dz, const float* __restrict__ x, const float* __restrict__ xn, const float* __restrict__ wd,
@@ -794,13 +833,26 @@ __global__ __launch_bounds__(256, 4) void k_conv_bwd_data(
     {
         const size_t xo = (size_t)grp * g.C * HW;
         x += xo; xn += xo; dx += xo; if (dxn) dxn += xo;
-        dz += (size_t)grp * g.O * HoWo * (g.pix_major ? g.B : 1);
+        dz += (size_t)grp * g.O * HoWo * ((g.pix_major || RB == 2) ? g.B : 1);
         wd += (size_t)grp * (g.kh * g.kw) * Opad16 * ncol;
     }
 
     if (tid < KAN_MAX_TABLE) sTab[tid] = bs.tab[tid];
     // tile column pxl holds pixel my_px: plane-major, or (RB) column = (row, image, column) -> pixel = image * 16 + row * 4 + column
-    const int my_px = px_tile0 + (RB ? ((pxl >> 2) & 7) * 16 + (pxl >> 5) * 4 + (pxl & 3) : pxl);
+    // (RB == 2) column = (block, image): block -> plane position by the diagonal pairing (0 = the plane's corner, 1 = the interior position diagonal to
+    // it, 2 / 3 = the edge positions in the corner's row / column)
+    const int q_qh = (blk.x >> 1) & 1, q_qw = blk.x & 1, q_b0 = (blk.x >> 2) * 32;
+    auto q_pos = [&](int bk) { return ((bk == 0 || bk == 2) ? 3 * q_qh : 1 + q_qh) * 4 + ((bk == 0 || bk == 3) ? 3 * q_qw : 1 + q_qw); };
+    auto q_mask = [&](int hw) {                                // taps under which position hw has a source (an output it fed)
+        unsigned m = 0;
+        for (int tap = 0; tap < 9; ++tap) {
+            const int r = tap / 3, t = tap - r * 3;
+            m |= (((unsigned)((hw >> 2) + 1 - r) < 4u && (unsigned)((hw & 3) + 1 - t) < 4u) ? 1u : 0u) << tap;
+        }
+        return m;
+    };
+    const int my_px = RB == 2 ? (q_b0 + (pxl & 31)) * 16 + q_pos(pxl >> 5)
+                              : px_tile0 + (RB == 1 ? ((pxl >> 2) & 7) * 16 + (pxl >> 5) * 4 + (pxl & 3) : pxl);
     const bool pv = my_px < Min;
     int pb, ph_, pw_;
     {
@@ -904,6 +956,31 @@ __global__ __launch_bounds__(256, 4) void k_conv_bwd_data(
         }
     };
 
+    // (RB == 2) wave wv copies block wv: its position and live taps; the per-lane part of the source offset is fixed (lane = 8 outputs x 8 chunks of 4 images)
+    const int cp_hw = q_pos(wv); const unsigned cp_live = q_mask(cp_hw);
+    const unsigned q_live0 = q_mask(q_pos(2 * w_p)), q_live1 = q_mask(q_pos(2 * w_p + 1));      // the two blocks this wave multiplies
+    const unsigned q_voff = (unsigned)((lane >> 3) * 16 * g.B + (lane & 7) * 4) * 4u;
+    int pend_tap = 0;
+    auto issue_q = [&](int ch, int buf) {
+        const int tap = ch / n_ob, o0 = (ch - tap * n_ob) * KD;                       // scalar
+        pend_tap = tap;
+        float* dW = smem + buf * (2 * KD * 128);
+        float* dG = dW + KD * 128 + wv * 512;
+        if ((cp_live >> tap) & 1u) {                                                   // uniform: a dead block's copy is not issued
+            const int r = tap / 3, t = tap - r * 3;
+            const unsigned so = (unsigned)((o0 * 16 + cp_hw + (1 - r) * 4 + (1 - t)) * g.B + q_b0) * 4u;      // scalar part: (output block, source position, image group)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(dz_rs, (__attribute__((address_space(3))) void*)dG, 16, (int)q_voff, (int)so, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(dz_rs, (__attribute__((address_space(3))) void*)(dG + 256), 16, (int)q_voff,
+                                                     (int)(so + (unsigned)(8 * 16 * g.B) * 4u), 0, 0);
+        }
+        const char* wsrc = (const char*)(wd + ((size_t)tap * Opad16 + o0) * ncol + ct * 128);      // scalar
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int blk2 = j * 4 + wv;
+            glds16((const float*)(wsrc + (size_t)blk2 * 2 * ncol * 4 + wlane), dW + blk2 * 256);
+        }
+    };
+
     f32x16 acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
@@ -940,18 +1017,23 @@ __global__ __launch_bounds__(256, 4) void k_conv_bwd_data(
         return ch1;
     };
     int ch = next_live(ch0);
-    if (ch < ch1) { if (RB) issue_rb(ch, 0); else issue(ch, 0); }
+    if (ch < ch1) { if (RB == 2) issue_q(ch, 0); else if (RB) issue_rb(ch, 0); else issue(ch, 0); }
     const int ar = w_r * 64 + (lane & 31), bp = w_p * 64 + (lane & 31), kh2 = lane >> 5;
     for (int cur = 0; ch < ch1; cur ^= 1) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's async copies of the step have landed ...
         __syncthreads();                                   // ... and so have everyone else's; also orders the two buffers
         const bool mixed_now = pend_mixed;
+        const int tap_now = pend_tap;
         ch = next_live(ch + 1);
-        if (ch < ch1) { if (RB) issue_rb(ch, cur ^ 1); else issue(ch, cur ^ 1); }
+        if (ch < ch1) { if (RB == 2) issue_q(ch, cur ^ 1); else if (RB) issue_rb(ch, cur ^ 1); else issue(ch, cur ^ 1); }
         const float* cW = smem + cur * (2 * KD * 128);
         const float* cG = cW + KD * 128;
         const unsigned aw = lds_addr(cW + kh2 * 128 + ar), ag = lds_addr(cG + kh2 * TP + bp);
-        if (RB) {
+        if (RB == 2) {
+            const unsigned agq = lds_addr(cG + (2 * w_p) * 512 + kh2 * 32 + (lane & 31));
+            const bool l0 = ((q_live0 >> tap_now) & 1u) != 0, l1 = ((q_live1 >> tap_now) & 1u) != 0;
+            if (!idle_rows) KAN_MFMA_STEP_QUAD(KD / 2, aw, 128, agq, l0, l1);
+        } else if (RB) {
             // rows 2 w_p and 2 w_p + 1: row 0 has no source under tap row 2 (second half of a mixed step), row 3 none under tap row 0 (first half)
             const bool l0b = !(mixed_now && w_p == 0), l1a = !(mixed_now && w_p == 1);
             if (!idle_rows) KAN_MFMA_STEP_LIVE(KD / 2, aw, 128, ag, TP, true, l0b, l1a, true);
@@ -2718,6 +2800,13 @@ int kan_pack_weights(const float* w_base, const float* w_basis, float* wp, float
     return pack_weights_impl(w_base, w_basis, wp, wd, g, b, nullptr, 0, stream);
 }
 
+int kan_tile_orders(const KanGeom* g, const KanBasis* b) {
+    ConvPlan cp;
+    if (plan_conv(g, b, &cp)) return 0;
+    const bool halo = cp.fwd == Route::HALO;
+    return (halo && cp.quad_fwd ? KAN_ORDER_QUAD_FWD : 0) | (halo && cp.rowblk8_fwd ? KAN_ORDER_ROWBLK8_FWD : 0) | (cp.quad_bd ? KAN_ORDER_QUAD_BWD_DATA : 0);
+}
+
 int kan_pack_cacheable(const KanGeom* g, const KanBasis* b) {
     ConvPlan cp;
     if (plan_conv(g, b, &cp)) return 0;
@@ -2815,7 +2904,12 @@ int kan_conv_fwd(const float* x, const float* xn, const float* wp, float* z, con
                 }
                 if (g->W == 32) launch(wo, IC<32>{}, IC<4>{}, IC<1>{}, IC<0>{});
                 else if (g->W == 16) launch(wo, IC<16>{}, IC<8>{}, IC<1>{}, IC<0>{});
-                else if (g->W == 8) launch(wo, IC<8>{}, IC<8>{}, IC<2>{}, IC<0>{});
+                else if (g->W == 8) {
+                    if constexpr (decltype(wo)::value == 4) {          // 4 images x half a plane, row blocks (B a multiple of 4)
+                        if (cp.rowblk8_fwd) return launch(wo, IC<8>{}, IC<4>{}, IC<4>{}, IC<0>{});
+                    }
+                    launch(wo, IC<8>{}, IC<8>{}, IC<2>{}, IC<0>{});
+                }
                 else launch(wo, IC<4>{}, IC<4>{}, IC<8>{}, IC<0>{});
             };
             if constexpr (fast_has(F, ON_BIG_TILES)) {
@@ -2910,14 +3004,18 @@ static int conv_bwd_data_impl(const float* dz, const float* x, const float* xn, 
     const int fast = (fast_spec(cp.fast).xn_bwd ? (x != xn && dxn) : (x == xn && !dxn)) ? cp.fast : FAST_GENERIC;
     // 4x4 planes in tiles of 8 whole images: row-ordered pixel blocks, dead (row, tap row) blocks skipped (see the kernel)
     const bool rb = !dg.pix_major && cp.rowblk_bwd_data;
+    // ... with whole 32-image groups and the position-major copy of dz at hand: quadrant tiles fed from dz_pm (same tile count, splits and slabs)
+    const bool quad = rb && cp.quad_bd && dz_pm && x == xn && !dxn;
     const unsigned dz_bytes = (unsigned)((long long)g->B * g->y_bstride * 4);
     auto launch = [&](auto kind, auto fast, auto rbv) {
-        hipLaunchKernelGGL((k_conv_bwd_data<decltype(kind)::value, decltype(fast)::value, decltype(rbv)::value>), grid, dim3(256), 0, st, dz, x, xn, wd,
+        hipLaunchKernelGGL((k_conv_bwd_data<decltype(kind)::value, decltype(fast)::value, decltype(rbv)::value>), grid, dim3(256), 0, st,
+                           decltype(rbv)::value == 2 ? dz_pm : dz, x, xn, wd,
                            dx, dxn, dg, db, c.CH, c.tiles_c, c.n_ob, c.Opad32, c.chunks, cps, pl.bwd_data_slab_elems, dz_bytes, perm, dpar);
     };
     const bool launched = dispatch_fast<ON_TAP_MAJOR>(fast, [&](auto fv) {
         constexpr int F = decltype(fv)::value;
         if constexpr (fast_has(F, ON_ROWBLK_BWD_DATA)) {
+            if (quad) return launch(IC<fast_kind(F)>{}, fv, IC<2>{});
             if (rb) return launch(IC<fast_kind(F)>{}, fv, IC<1>{});
         }
         launch(IC<fast_kind(F)>{}, fv, IC<0>{});

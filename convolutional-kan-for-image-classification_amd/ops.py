@@ -92,6 +92,7 @@ def _plan_cached(spec: ConvSpec, B: int, Cg: int, H: int, W: int, Og: int, C_tot
         bp = L.KanBasis.from_buffer_copy(b)
         bp.chan_table = 1
     L.check(L.load().kan_plan(C.byref(g), C.byref(bp), C.byref(p)), "kan_plan")
+    p.tile_orders = L.load().kan_tile_orders(C.byref(g), C.byref(bp))      # the launchers' pixel order inside a tile: not a KanPlan field (kanconv.h)
     return g, b, p
 
 
@@ -206,12 +207,24 @@ _ROW_BLOCK_BIT = {"fwd": 1, "bwd_data": 2, "bwd_weight": 0}          # KanPlan.r
 
 def _quadrant_order(geom, plan, which: str) -> bool:
     """The launch runs quadrant tiles (32 images x a 2x2 quadrant of a 4x4 plane) instead of row blocks: the planner's predicate restated
-    (kan_plan.hip, plan_conv: `c.quad_fwd = rowblk_fwd && g->B % 32 == 0`; the forward only, bwd-data keeps its row blocks).  The launcher also wants an 8-byte aligned
+    (kan_plan.hip, plan_conv: `c.quad_fwd = rowblk_fwd && g->B % 32 == 0`; the forward only: bwd-data has its own predicate, `_quadrant_bwd_data`, as it also needs dz_pm).  The launcher also wants an 8-byte aligned
     output, which every torch allocation is."""
     return which == "fwd" and bool(plan.row_blocks & 1) and geom.B % 32 == 0
 
 
-def _executed_flops(geom, plan, which: str) -> float:
+def _quadrant_bwd_data(geom, plan, have_dz_pm: bool) -> bool:
+    """bwd-data runs quadrant tiles fed from the position-major copy of dz (kan_plan.hip, plan_conv: `c.quad_bd`; the launcher takes them when it is given
+    dz_pm and a single input tensor -- `_conv_backward` builds dz_pm only without xn): exactly the live (position, tap) blocks are issued."""
+    return bool(have_dz_pm) and bool(plan.row_blocks & 2) and bool(getattr(plan, "tile_orders", 0) & L.ORDER_QUAD_BWD_DATA)
+
+
+def _row_blocks8_forward(geom, plan) -> bool:
+    """The forward runs half-plane row-block tiles on 8x8 planes (4 images x 4 rows; kan_plan.hip, plan_conv: `c.rowblk8_fwd`): the block of the plane's
+    first / last row is skipped under the tap row that leaves the plane, 1/12 of the MFMA work.  `plan.row_blocks` stays 0 for these geometries."""
+    return geom.H == 8 and geom.W == 8 and bool(getattr(plan, "tile_orders", 0) & L.ORDER_ROWBLK8_FWD)
+
+
+def _executed_flops(geom, plan, which: str, have_dz_pm: bool = False) -> float:
     """Dense count minus the dead (position, tap) products a position-major launch skips (plan.*_target > 0 marks one)."""
     target = {"fwd": plan.fwd_target, "bwd_data": plan.bwd_data_target, "bwd_weight": plan.bwd_weight_target}[which]
     dense = _conv_flops(geom, plan)
@@ -219,10 +232,12 @@ def _executed_flops(geom, plan, which: str) -> float:
     if target <= 0:
         # row-ordered 4x4 launches skip the blocks of the first / last row under the tap row that leaves the plane: 2/3 * 1/4 of the work;
         # the quadrant order skips exactly the dead (position, tap) blocks
-        if _quadrant_order(geom, plan, which):
+        if _quadrant_order(geom, plan, which) or (which == "bwd_data" and _quadrant_bwd_data(geom, plan, have_dz_pm)):
             return dense * _live_fraction(which, g.H, g.W, g.Ho, g.Wo, g.kh, g.kw, g.sh, g.sw, g.ph, g.pw, g.dh, g.dw)
         if plan.row_blocks & _ROW_BLOCK_BIT[which]:
             return dense * (5.0 / 6.0)
+        if which == "fwd" and _row_blocks8_forward(geom, plan):
+            return dense * (11.0 / 12.0)
         return dense
     return dense * _live_fraction(which, g.H, g.W, g.Ho, g.Wo, g.kh, g.kw, g.sh, g.sw, g.ph, g.pw, g.dh, g.dw)
 
@@ -248,9 +263,9 @@ def _sample(which: str, geom, plan, pm: bool, two: bool = False, expanded: bool 
         halo = plan.fwd_halo if which == "fwd" else (plan.bwd_weight_halo and not two)
         name = f"k_conv_{which}{'_halo' if halo else ''}/o{tile}"
     # zero products are skipped by the expanded launches, by launches that got their position-major copies, and by the row-ordered 4x4 ones
-    skips = expanded or pm or bool(plan.row_blocks & _ROW_BLOCK_BIT[which])
+    skips = expanded or pm or bool(plan.row_blocks & _ROW_BLOCK_BIT[which]) or (which == "fwd" and _row_blocks8_forward(geom, plan))
     dense = _conv_flops(geom, plan)
-    return name, dense, _executed_flops(geom, plan, which) if skips else dense, _layer_tag(geom)
+    return name, dense, _executed_flops(geom, plan, which, pm) if skips else dense, _layer_tag(geom)
 
 
 # --------------------------------------------------------------------------------------- raw stages

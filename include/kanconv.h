@@ -138,6 +138,19 @@ const char* kan_last_error(void);
 /* Fill `plan` for (geom, basis).  Pure host arithmetic, no device work. */
 int kan_plan(const KanGeom* geom, const KanBasis* basis, KanPlan* plan);
 
+/* Informational, for profiling tools and tests: the pixel order inside the tiles of this geometry's launches, which the launchers choose
+ * among orders of the same tile count, splits and slabs (so nothing in KanPlan moves with it).  Bits:
+ *   KAN_ORDER_QUAD_FWD     4x4 planes, B % 32 == 0: the halo forward runs quadrant tiles (exactly the live 25/36 of the MFMA blocks issued)
+ *   KAN_ORDER_ROWBLK8_FWD  8x8 planes, 256-output tiles, B % 4 == 0: the halo forward runs half-plane tiles of 4 images in row order and skips
+ *                          the block of the plane's first / last row under the tap row that leaves the plane (11/12 issued)
+ *   KAN_ORDER_QUAD_BWD_DATA 4x4 planes, B % 32 == 0, O % 16 == 0: bwd-data runs quadrant tiles (25/36 issued) when it is given dz_pm and one input tensor;
+ *                          otherwise it keeps the row blocks of KanPlan.row_blocks bit 1
+ * 0 for a geometry the planner rejects. */
+#define KAN_ORDER_QUAD_FWD 1
+#define KAN_ORDER_ROWBLK8_FWD 2
+#define KAN_ORDER_QUAD_BWD_DATA 4
+int kan_tile_orders(const KanGeom* geom, const KanBasis* basis);
+
 /* Pack the reference-layout weights of one group into the GEMM layouts of the kernels:
  *   wp (forward):   wp[k(item,p)][o],  item = tap*C + c (tap-major), T = kh*kw,
  *                   k = (item / IPC)*KC + (item % IPC)*P + p;  plane p = 0 is the base branch

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """CPU emulation (numpy) of the quadrant tile's index arithmetic on 4x4 planes: tile <-> pixel, halo cell, shifted read, live table, dz gather.
 3x3 / stride 1 / pad 1, B a multiple of 32.  The forward half is what k_conv_fwd_halo QUAD (csrc/kanconv.hip) runs, line by line, with the
-"rows" pairing of the blocks; the bwd-data half (diagonal pairing, per-tap dz gather) restates the variant of k_conv_bwd_data that was measured
-and not shipped.  tests/test_quadrant_order.py checks both against F.conv2d.  python tools/probe/quad_emul.py"""
+"rows" pairing of the blocks; the bwd-data half (diagonal pairing, per-tap dz gather from NCHW) restates the first variant of k_conv_bwd_data<.., RB = 2>,
+which was measured and not shipped; the shipped one keeps this tile and pairing and copies dz from its position-major copy
+(tools/probe/quad_bwd_emul.py).  tests/test_quadrant_order.py checks both against F.conv2d.  python tools/probe/quad_emul.py"""
 import numpy as np
 
 PLANE, NIMG, TP = 4, 32, 128          # plane side, images per tile, pixels per tile (4 blocks of 32)
