@@ -52,6 +52,16 @@ class KanWavGeom(C.Structure):
                [("x_bstride", C.c_longlong), ("u_bstride", C.c_longlong)]
 
 
+class KanWavRoute(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("TH", "TW", "NIMG", "RH", "RW", "tiles_h", "tiles_w", "fwd_shrunk", "fwd_nimg_cut", "fwd_lds_bytes", "fwd_fits",
+                                       "fwd_blocks", "bwd_input_kernel", "bwd_input_blocks", "params_kernel", "passes", "chunks", "BH", "NI", "RU",
+                                       "CU", "XP", "UP", "bands", "items", "items_per_chunk", "lds_bytes", "px_per_chunk")]
+
+
+WAV_BI_TAPS9, WAV_BI_STRIDE1, WAV_BI_STRIDED = 0, 1, 2
+WAV_PAR_TILED, WAV_PAR_PIXEL = 0, 1
+
+
 WAVELETS = {"mexican_hat": 0, "morlet": 1, "dog": 2, "meyer": 3, "shannon": 4}
 
 # every symbol include/kanconv.h declares, with its argument types
@@ -90,6 +100,7 @@ SIGNATURES = {
     "kan_wav_bwd_input": (_I, [_P, _P, _P, _P, _P, _P, C.POINTER(KanWavGeom), _P]),
     "kan_wav_param_workspace": (_LL, [C.POINTER(KanWavGeom)]),
     "kan_wav_bwd_params": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(KanWavGeom), _P]),
+    "kan_wav_route": (_I, [C.POINTER(KanWavGeom), C.POINTER(KanWavRoute)]),
     "kan_adamw_step": (_I, [_P, _P, _P, _P, _LL, _D, _D, _D, _D, _D, _I, _F, _P]),
     "kan_adamw_step_segments": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _D, _D, _D, _D, _D, _I, _F, _P]),
 }

@@ -307,7 +307,7 @@ __global__ __launch_bounds__(256) void k_wav_bwd_params(const float* __restrict_
     const float* wk = w + ((size_t)o * g.C + c) * T;
     float* out = part + ((size_t)chunk * g.O * g.C + (size_t)o * g.C + c) * (T + 2);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int t0 = 0; t0 < T; t0 += TMAX) {                                       // (kernels above 27 taps take several passes; dtrans / dscale in the first)
+    for (int t0 = 0; t0 < T; t0 += TMAX) {                                       // (kernels above 9 taps take several passes; every pass adds its share of dtrans / dscale)
         const int nt = min(TMAX, T - t0);
         float sw_[TMAX], st = 0.f, ss = 0.f;
 #pragma unroll
@@ -475,23 +475,81 @@ static int wav_check(const KanWavGeom* g) {
     return 0;
 }
 
-// tile of the forward kernel: up to 256 output pixels (whole small planes of several images, or a TH x TW patch), input region <= 1792 cells (LDS: 4 wavelet planes + the cell tables)
-static WavTile wav_tile(const KanWavGeom* g) {
-    WavTile t;
-    t.TW = g->Wo < 16 ? g->Wo : 16;
-    t.TH = g->Ho < 256 / t.TW ? g->Ho : 256 / t.TW;
+// Every launch decision of the wavelet stage (kan_wav_route exports it; the four entry points dispatch from it and from nothing else).
+//   forward: a tile of up to 256 output pixels (whole small planes of several images, or a TH x TW patch), input region <= 1792 cells (LDS: 4
+//   wavelet planes + the cell tables);  bwd-input: the register-table kernel up to 9 taps, else the generic one (stride 1 or not);  bwd-params:
+//   the tiled kernel while NI images x a band of BH rows (x and the scattered du, 16 channels / outputs each) fit 56 KB of LDS, else (very wide
+//   rows / large dilated kernels) the per-pixel kernel.
+constexpr int WAV_TAPS = 9;                       // taps per pass of the parameter kernels; the register table of k_wav_bwd_input9
+constexpr long long WAV_REGION_CELLS = 1792;
+constexpr size_t WAV_FWD_LDS = 64 * 1024, WAV_BAND_LDS = 56 * 1024;
+
+static int wav_sat(long long v) { return v > 2147483647ll ? 2147483647 : (int)v; }
+
+static void wav_plan(const KanWavGeom* g, KanWavRoute& r, long long& fwd_blocks, long long& bi_blocks, size_t& fwd_smem, size_t& par_smem) {
+    r = KanWavRoute{};
+    const int T = g->kh * g->kw;
+    // ---- forward
+    r.TW = g->Wo < 16 ? g->Wo : 16;
+    r.TH = g->Ho < 256 / r.TW ? g->Ho : 256 / r.TW;
     auto region = [&](int th, int tw, int& rh, int& rw) { rh = (th - 1) * g->sh + (g->kh - 1) * g->dh + 1; rw = (tw - 1) * g->sw + (g->kw - 1) * g->dw + 1; };
-    region(t.TH, t.TW, t.RH, t.RW);
-    while ((long long)t.RH * t.RW > 1792 && (t.TH > 1 || t.TW > 1)) {
-        if (t.TH >= t.TW && t.TH > 1) t.TH = (t.TH + 1) / 2; else t.TW = (t.TW + 1) / 2;
-        region(t.TH, t.TW, t.RH, t.RW);
+    region(r.TH, r.TW, r.RH, r.RW);
+    while ((long long)r.RH * r.RW > WAV_REGION_CELLS && (r.TH > 1 || r.TW > 1)) {
+        if (r.TH >= r.TW && r.TH > 1) r.TH = (r.TH + 1) / 2; else r.TW = (r.TW + 1) / 2;
+        region(r.TH, r.TW, r.RH, r.RW);
+        r.fwd_shrunk = 1;
     }
-    t.NIMG = 256 / (t.TH * t.TW);
-    if (t.NIMG < 1) t.NIMG = 1;
-    while (t.NIMG > 1 && (long long)t.NIMG * t.RH * t.RW > 1792) --t.NIMG;
-    if (t.NIMG > g->B) t.NIMG = g->B;
-    t.tiles_h = (g->Ho + t.TH - 1) / t.TH; t.tiles_w = (g->Wo + t.TW - 1) / t.TW;
-    return t;
+    r.NIMG = 256 / (r.TH * r.TW);
+    if (r.NIMG < 1) r.NIMG = 1;
+    const int nimg_free = r.NIMG < g->B ? r.NIMG : g->B;
+    while (r.NIMG > 1 && (long long)r.NIMG * r.RH * r.RW > WAV_REGION_CELLS) --r.NIMG;
+    if (r.NIMG > g->B) r.NIMG = g->B;
+    r.fwd_nimg_cut = r.NIMG < nimg_free;
+    r.tiles_h = (g->Ho + r.TH - 1) / r.TH; r.tiles_w = (g->Wo + r.TW - 1) / r.TW;
+    fwd_blocks = (long long)((g->B + r.NIMG - 1) / r.NIMG) * r.tiles_h * r.tiles_w;
+    const size_t n_cells = (size_t)r.NIMG * r.RH * r.RW;
+    fwd_smem = ((size_t)WAV_OB * (n_cells + 2 * T + 4) + ((n_cells + 1) & ~(size_t)1)) * sizeof(float) + n_cells * sizeof(long long);
+    r.fwd_fits = fwd_smem <= WAV_FWD_LDS;
+    r.fwd_lds_bytes = wav_sat((long long)fwd_smem);
+    r.fwd_blocks = wav_sat(fwd_blocks);
+    // ---- bwd-input
+    r.bwd_input_kernel = T <= WAV_TAPS ? KAN_WAV_BI_TAPS9 : (g->sh == 1 && g->sw == 1 ? KAN_WAV_BI_STRIDE1 : KAN_WAV_BI_STRIDED);
+    const long long total = (long long)g->B * g->H * g->W;
+    bi_blocks = (total + 255) / 256;
+    r.bwd_input_blocks = wav_sat(bi_blocks);
+    // ---- bwd-params
+    r.passes = (T + WAV_TAPS - 1) / WAV_TAPS;
+    const int BH = g->W >= 256 ? 1 : (256 / g->W < g->H ? 256 / g->W : g->H);
+    const int RU = BH + (g->kh - 1) * g->dh, CU = g->W + (g->kw - 1) * g->dw;
+    const int XP = (BH * g->W) | 1, UP = (RU * CU) | 1;
+    int NI = 256 / (BH * g->W); if (NI < 1) NI = 1; if (NI > g->B) NI = g->B;
+    auto bytes = [&](int ni) { return (size_t)ni * 16 * ((size_t)XP + UP) * sizeof(float); };
+    while (NI > 1 && bytes(NI) > WAV_BAND_LDS) --NI;
+    par_smem = bytes(NI);
+    long long chunks;
+    if (par_smem <= WAV_BAND_LDS) {
+        r.params_kernel = KAN_WAV_PAR_TILED;
+        r.BH = BH; r.NI = NI; r.RU = RU; r.CU = CU; r.XP = XP; r.UP = UP;
+        r.lds_bytes = (int)par_smem;
+        r.bands = (g->H + BH - 1) / BH;
+        r.items = ((g->B + NI - 1) / NI) * r.bands;
+        const long long pairs = (long long)((g->C + 15) / 16) * ((g->O + 15) / 16);
+        chunks = (2048 + pairs - 1) / pairs;
+        if (chunks > r.items) chunks = r.items;
+        if (chunks > 65535) chunks = 65535;
+        r.items_per_chunk = (int)((r.items + chunks - 1) / chunks);
+        chunks = (r.items + r.items_per_chunk - 1) / r.items_per_chunk;
+    } else {
+        r.params_kernel = KAN_WAV_PAR_PIXEL;
+        par_smem = 0;
+        const long long pairs = (long long)g->O * g->C;
+        chunks = (4096 + pairs - 1) / pairs;                             // enough blocks to fill the chip, >= 256 pixels each
+        if (chunks > (total + 255) / 256) chunks = (total + 255) / 256;
+        if (chunks < 1) chunks = 1;
+        if (chunks > 65535) chunks = 65535;
+        r.px_per_chunk = (int)((total + chunks - 1) / chunks);
+    }
+    r.chunks = (int)chunks;
 }
 
 #define KAN_WAV_DISPATCH(CALL)                                  \
@@ -507,18 +565,25 @@ static WavTile wav_tile(const KanWavGeom* g) {
 
 extern "C" {
 
+int kan_wav_route(const KanWavGeom* g, KanWavRoute* route) {
+    if (int rc = wav_check(g)) return rc;
+    if (!route) return fail("null route in kan_wav_route");
+    long long fwd_blocks, bi_blocks; size_t fwd_smem, par_smem;
+    wav_plan(g, *route, fwd_blocks, bi_blocks, fwd_smem, par_smem);
+    return 0;
+}
+
 int kan_wav_fwd(const float* x, const float* scale, const float* trans, const float* w, float* u, const KanWavGeom* g, void* stream) {
     if (int rc = wav_check(g)) return rc;
     if (!x || !scale || !trans || !w || !u) return fail("null pointer in kan_wav_fwd");
-    const WavTile tl = wav_tile(g);
+    KanWavRoute r; long long blocks, bi_blocks; size_t smem, par_smem;
+    wav_plan(g, r, blocks, bi_blocks, smem, par_smem);
+    const WavTile tl = {r.TH, r.TW, r.NIMG, r.RH, r.RW, r.tiles_h, r.tiles_w};
     const WavDev d = wav_dev(g);
-    const long long blocks = (long long)((g->B + tl.NIMG - 1) / tl.NIMG) * tl.tiles_h * tl.tiles_w;
     const int oblocks = (g->O + WAV_OB - 1) / WAV_OB;
     if (blocks >= (1ll << 31) || oblocks > 65535) return fail("wavelet forward grid too large");
     static_assert(WAV_OB == 4, "k_wav_fwd reads its taps as float4");
-    const size_t n_cells = (size_t)tl.NIMG * tl.RH * tl.RW;
-    const size_t smem = ((size_t)WAV_OB * (n_cells + 2 * g->kh * g->kw + 4) + ((n_cells + 1) & ~(size_t)1)) * sizeof(float) + n_cells * sizeof(long long);
-    if (smem > 64 * 1024) return fail("wavelet forward tile does not fit in LDS (kernel / stride / dilation too large)");
+    if (!r.fwd_fits) return fail("wavelet forward tile does not fit in LDS (kernel / stride / dilation too large)");
 #define KAN_WAV_F(WT) hipLaunchKernelGGL((k_wav_fwd<WT>), dim3((unsigned)blocks, oblocks), dim3(256), smem, (hipStream_t)stream, x, scale, trans, w, u, d, tl)
     KAN_WAV_DISPATCH(KAN_WAV_F)
 #undef KAN_WAV_F
@@ -529,54 +594,28 @@ int kan_wav_bwd_input(const float* du, const float* x, const float* scale, const
                       void* stream) {
     if (int rc = wav_check(g)) return rc;
     if (!du || !x || !scale || !trans || !w || !dx) return fail("null pointer in kan_wav_bwd_input");
+    KanWavRoute r; long long fwd_blocks, blocks; size_t fwd_smem, par_smem;
+    wav_plan(g, r, fwd_blocks, blocks, fwd_smem, par_smem);
     const WavDev d = wav_dev(g);
-    const long long blocks = ((long long)g->B * g->H * g->W + 255) / 256;
     const int cblocks = (g->C + WAV_CB - 1) / WAV_CB;
     if (blocks >= (1ll << 31) || cblocks > 65535) return fail("wavelet bwd-input grid too large");
 #define KAN_WAV_I(WT) hipLaunchKernelGGL((k_wav_bwd_input<WT, true>), dim3((unsigned)blocks, cblocks), dim3(256), 0, (hipStream_t)stream, du, x, scale, trans, w, dx, d)
 #define KAN_WAV_IS(WT) hipLaunchKernelGGL((k_wav_bwd_input<WT, false>), dim3((unsigned)blocks, cblocks), dim3(256), 0, (hipStream_t)stream, du, x, scale, trans, w, dx, d)
 #define KAN_WAV_I9(WT) hipLaunchKernelGGL((k_wav_bwd_input9<WT>), dim3((unsigned)blocks, cblocks), dim3(256), 0, (hipStream_t)stream, du, x, scale, trans, w, dx, d)
-    if (g->kh * g->kw <= 9) { KAN_WAV_DISPATCH(KAN_WAV_I9) }
-    else if (g->sh == 1 && g->sw == 1) { KAN_WAV_DISPATCH(KAN_WAV_I) } else { KAN_WAV_DISPATCH(KAN_WAV_IS) }
+    static_assert(WAV_TAPS == 9, "k_wav_bwd_input9 holds a table of 9 taps");
+    if (r.bwd_input_kernel == KAN_WAV_BI_TAPS9) { KAN_WAV_DISPATCH(KAN_WAV_I9) }
+    else if (r.bwd_input_kernel == KAN_WAV_BI_STRIDE1) { KAN_WAV_DISPATCH(KAN_WAV_I) } else { KAN_WAV_DISPATCH(KAN_WAV_IS) }
 #undef KAN_WAV_I9
 #undef KAN_WAV_IS
 #undef KAN_WAV_I
     return launch_ok("wav_bwd_input");
 }
 
-static bool wav_band(const KanWavGeom* g, WavBand& wb, size_t& smem) {
-    wb.BH = g->W >= 256 ? 1 : (256 / g->W < g->H ? 256 / g->W : g->H);
-    wb.RU = wb.BH + (g->kh - 1) * g->dh; wb.CU = g->W + (g->kw - 1) * g->dw;
-    wb.XP = (wb.BH * g->W) | 1; wb.UP = (wb.RU * wb.CU) | 1;
-    wb.NI = 256 / (wb.BH * g->W); if (wb.NI < 1) wb.NI = 1; if (wb.NI > g->B) wb.NI = g->B;
-    auto bytes = [&](int ni) { return (size_t)ni * 16 * ((size_t)wb.XP + wb.UP) * sizeof(float); };
-    while (wb.NI > 1 && bytes(wb.NI) > 56 * 1024) --wb.NI;
-    smem = bytes(wb.NI);
-    if (smem > 56 * 1024) return false;                                   // very wide rows / large dilated kernels: the per-pixel kernel
-    wb.bands = (g->H + wb.BH - 1) / wb.BH;
-    wb.items = ((g->B + wb.NI - 1) / wb.NI) * wb.bands;
-    const long long pairs = (long long)((g->C + 15) / 16) * ((g->O + 15) / 16);
-    long long chunks = (2048 + pairs - 1) / pairs;
-    if (chunks > wb.items) chunks = wb.items;
-    if (chunks > 65535) chunks = 65535;
-    wb.items_per_chunk = (int)((wb.items + chunks - 1) / chunks);
-    return true;
-}
-
-static long long wav_param_chunks(const KanWavGeom* g) {
-    WavBand wb; size_t smem;
-    if (wav_band(g, wb, smem)) return (wb.items + wb.items_per_chunk - 1) / wb.items_per_chunk;
-    const long long pairs = (long long)g->O * g->C, total = (long long)g->B * g->H * g->W;
-    long long chunks = (4096 + pairs - 1) / pairs;                       // enough blocks to fill the chip, >= 256 pixels each
-    if (chunks > (total + 255) / 256) chunks = (total + 255) / 256;
-    if (chunks < 1) chunks = 1;
-    if (chunks > 65535) chunks = 65535;
-    return chunks;
-}
-
 long long kan_wav_param_workspace(const KanWavGeom* g) {
     if (wav_check(g)) return -1;
-    return wav_param_chunks(g) * (long long)g->O * g->C * (g->kh * g->kw + 2);
+    KanWavRoute r; long long fwd_blocks, bi_blocks; size_t fwd_smem, par_smem;
+    wav_plan(g, r, fwd_blocks, bi_blocks, fwd_smem, par_smem);
+    return r.chunks * (long long)g->O * g->C * (g->kh * g->kw + 2);
 }
 
 int kan_wav_bwd_params(const float* du, const float* x, const float* scale, const float* trans, const float* w, float* dw, float* dscale, float* dtrans,
@@ -584,14 +623,17 @@ int kan_wav_bwd_params(const float* du, const float* x, const float* scale, cons
     if (int rc = wav_check(g)) return rc;
     if (!du || !x || !scale || !trans || !w || !dw || !dscale || !dtrans || !workspace) return fail("null pointer in kan_wav_bwd_params");
     if (g->O > 65535 * 16) return fail("wavelet bwd-params grid too large");
+    KanWavRoute r; long long fwd_blocks, bi_blocks; size_t fwd_smem, smem;
+    wav_plan(g, r, fwd_blocks, bi_blocks, fwd_smem, smem);
     const WavDev d = wav_dev(g);
-    const int T = g->kh * g->kw;
-    const long long n = (long long)g->O * g->C * (T + 2), total = (long long)g->B * g->H * g->W;
-    const int chunks = (int)wav_param_chunks(g);
-    WavBand wb; size_t smem;
-    if (wav_band(g, wb, smem)) {
+    const int T = g->kh * g->kw, chunks = r.chunks;
+    const long long n = (long long)g->O * g->C * (T + 2);
+    static_assert(WAV_TAPS == 9, "the parameter kernels keep 9 taps in registers per pass (TMAX)");
+    if (r.params_kernel == KAN_WAV_PAR_TILED) {
+        const WavBand wb = {r.BH, r.NI, r.RU, r.CU, r.XP, r.UP, r.bands, r.items, r.items_per_chunk};
         const dim3 grid((g->C + 15) / 16, (g->O + 15) / 16, chunks);
-        for (int t0 = 0; t0 < T; t0 += 9) {                              // 9 taps per pass (dtrans / dscale add up over the passes)
+        for (int pass = 0; pass < r.passes; ++pass) {                    // 9 taps per pass (dtrans / dscale add up over the passes)
+            const int t0 = pass * WAV_TAPS;
 #define KAN_WAV_PT(WT) hipLaunchKernelGGL((k_wav_bwd_params_tiled<WT>), grid, dim3(256), smem, (hipStream_t)stream, du, x, scale, trans, w, workspace, d, wb, t0)
             KAN_WAV_DISPATCH(KAN_WAV_PT)
 #undef KAN_WAV_PT
@@ -599,7 +641,7 @@ int kan_wav_bwd_params(const float* du, const float* x, const float* scale, cons
         }
     } else {
         if (g->O > 65535) return fail("wavelet bwd-params grid too large");
-        const int ppc = (int)((total + chunks - 1) / chunks);
+        const int ppc = r.px_per_chunk;
 #define KAN_WAV_P(WT) hipLaunchKernelGGL((k_wav_bwd_params<WT>), dim3(g->C, g->O, chunks), dim3(256), 0, (hipStream_t)stream, du, x, scale, trans, w, workspace, d, ppc)
         KAN_WAV_DISPATCH(KAN_WAV_P)
 #undef KAN_WAV_P

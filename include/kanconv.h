@@ -372,6 +372,30 @@ long long kan_wav_param_workspace(const KanWavGeom* geom);
 int kan_wav_bwd_params(const float* du, const float* x, const float* scale, const float* trans, const float* w, float* dw, float* dscale,
                        float* dtrans, float* workspace, const KanWavGeom* geom, void* stream);
 
+/* Which kernels the four entry points above launch for a geometry, and with what launch shapes.  Pure host arithmetic, no device work (like
+ * kan_norm_route); kan_wav_fwd, kan_wav_bwd_input, kan_wav_bwd_params and kan_wav_param_workspace take their decisions from this struct and
+ * from nothing else.
+ *   forward     block = NIMG images x TH x TW output pixels (<= 256) x 4 outputs; RH x RW: the tile's input region (NIMG RH RW <= 1792 cells
+ *               unless a single pixel's region is larger);  tiles_h x tiles_w tiles per image;  fwd_shrunk: TH / TW were halved to get a tile's
+ *               region under 1792 cells;  fwd_nimg_cut: the same cap lowered NIMG below min(256 / (TH TW), B);  fwd_lds_bytes: dynamic LDS;
+ *               fwd_fits = 0: above 64 KB, kan_wav_fwd refuses;  fwd_blocks: tiles x image groups (x ceil(O / 4) in grid y)
+ *   bwd-input   TAPS9: k_wav_bwd_input9 (kh kw <= 9);  STRIDE1 / STRIDED: k_wav_bwd_input<true / false>;  bwd_input_blocks: ceil(B H W / 256)
+ *               (x ceil(C / 4) in grid y)
+ *   bwd-params  TILED: k_wav_bwd_params_tiled, one launch per pass -- work item = NI images x a band of BH input rows, `bands` bands per
+ *               image, `items` items, items_per_chunk of them per workgroup, RU x CU cells of du per output (row pitches XP / UP floats),
+ *               lds_bytes of dynamic LDS;  PIXEL (the band does not fit 56 KB): k_wav_bwd_params, all passes inside one launch, px_per_chunk
+ *               of the B H W input pixels per workgroup.  passes = ceil(kh kw / 9);  chunks: partial-sum slabs = grid z = what
+ *               kan_wav_param_workspace counts.  The fields of the kernel not taken are 0.
+ * Block counts that do not fit an int are reported as INT_MAX (the entry points refuse such a launch). */
+enum { KAN_WAV_BI_TAPS9 = 0, KAN_WAV_BI_STRIDE1 = 1, KAN_WAV_BI_STRIDED = 2 };
+enum { KAN_WAV_PAR_TILED = 0, KAN_WAV_PAR_PIXEL = 1 };
+typedef struct KanWavRoute {
+    int TH, TW, NIMG, RH, RW, tiles_h, tiles_w, fwd_shrunk, fwd_nimg_cut, fwd_lds_bytes, fwd_fits, fwd_blocks;
+    int bwd_input_kernel, bwd_input_blocks;
+    int params_kernel, passes, chunks, BH, NI, RU, CU, XP, UP, bands, items, items_per_chunk, lds_bytes, px_per_chunk;
+} KanWavRoute;
+int kan_wav_route(const KanWavGeom* geom, KanWavRoute* route);
+
 #ifdef __cplusplus
 }
 #endif

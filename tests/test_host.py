@@ -36,6 +36,8 @@ def test_struct_layouts_match_header():
     assert ctypes.sizeof(L.KanPlan) == 22 * 4 + 6 * 8           # 22 ints (incl. kernel-variant and expanded-copy flags), 6 x int64
     assert ctypes.sizeof(L.KanWavGeom) == 16 * 4 + 16 and L.KanWavGeom.wavelet.offset == 60 and L.KanWavGeom.x_bstride.offset == 64
     assert ctypes.sizeof(L.KanNormRoute) == 10 * 4 and L.KanNormRoute.strided.offset == 36              # 10 ints
+    assert ctypes.sizeof(L.KanWavRoute) == 28 * 4 and L.KanWavRoute.bwd_input_kernel.offset == 48       # 28 ints: 12 forward, 2 bwd-input, 14 bwd-params
+    assert L.KanWavRoute.params_kernel.offset == 56 and L.KanWavRoute.px_per_chunk.offset == 108
 
 
 def _plan(C, O, H, k=3, p=1, s=1, B=4, kind=L.BASIS_BSPLINE, nb=8, order=3, act=L.ACT_SILU, table=None):
