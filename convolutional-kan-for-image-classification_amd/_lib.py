@@ -92,6 +92,9 @@ SIGNATURES = {
     "kan_instnorm_prelu_poolk_fwd": (_I, [_P, _I, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _LL, _F, _I, _I, _I, _P]),
     "kan_instnorm_prelu_poolk_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _LL, _I, _I, _I, _P]),
     "kan_norm_route": (_I, [_I, _I, _I, _I, _I, _LL, _I, _LL, _I, _I, _I, _I, C.POINTER(KanNormRoute)]),
+    "kan_batchnorm_workspace_bytes": (_LL, [_I, _I]),
+    "kan_batchnorm_prelu_fwd": (_I, [_P, _I, _LL, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _LL, _F, _D, _I, _I, _P]),
+    "kan_batchnorm_prelu_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _LL, _I, _I, _P]),
     "kan_split_supported": (_I, [C.POINTER(KanGeom), C.POINTER(KanBasis)]),
     "kan_split_weight_bytes": (_LL, [C.POINTER(KanGeom), C.POINTER(KanBasis)]),
     "kan_split_pack_weights": (_I, [_P, _P, _P, C.POINTER(KanGeom), C.POINTER(KanBasis), _P]),

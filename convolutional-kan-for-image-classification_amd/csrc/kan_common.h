@@ -85,6 +85,20 @@ __device__ __forceinline__ int fastdiv(int a, FastDiv f) {
     return (int)((t + (((unsigned)a - t) >> 1)) >> (f.s - 1));
 }
 
+// Sum over the G lanes (a power of two <= 64, aligned) that share one (b, channel) plane in the norm kernels; every lane gets the result.
+template <int G>
+__device__ __forceinline__ float group_sum(float v) {
+#pragma unroll
+    for (int off = G / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+template <int G>
+__device__ __forceinline__ double group_sum(double v) {
+#pragma unroll
+    for (int off = G / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
 struct DevGeom {
     int B, C, H, W, O, Ho, Wo, kh, kw, sh, sw, ph, pw, dh, dw;
     int howo_shift, wo_shift;    // log2(Ho*Wo), log2(Wo) when both are powers of two, else -1 (pixel decode by shifts)

@@ -2058,18 +2058,7 @@ __global__ __launch_bounds__(256) void k_slab_reduce(const float* __restrict__ s
 // dy - mean(dy) is exactly zero and what survives is the small (x - mean) k term; with fp32 sums the bs-256 KAN-VGG11 weight
 // gradients were 1e-2 (L2) off the fp64 result where the reference's own fp32 path is 1e-4 off.  These kernels are
 // HBM-bound, the fp64 arithmetic is free.  mean / rstd are stored as fp32 (the reference's save_mean / save_invstd are too).
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-    for (int off = G / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-template <int G>
-__device__ __forceinline__ double group_sum(double v) {
-#pragma unroll
-    for (int off = G / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
+// (group_sum<G>: kan_common.h)
 
 // General MaxPool2d(k, s) (no padding, floor mode: the AlexNet pattern MaxPool2d(3, 2), kan_alexnet.py:38-42) fused behind the PReLU in the generic
 // norm kernels: windows overlap, so the backward of an element sums the pooled gradients of the <= ceil(k/s)^2 windows that picked it.  k == 0: not used

@@ -94,6 +94,45 @@ def _fusable_instnorm(mods) -> bool:
     return all(type(m) in (nn.InstanceNorm2d, nn.InstanceNorm1d) and not m.track_running_stats for m in mods)
 
 
+def _fusable_batchnorm(mods) -> bool:
+    """True when every per-group norm is a plain BatchNorm1d/2d/3d whose momentum is a number (None, the cumulative average, stays with
+    torch) and the groups share eps, momentum, affine and track_running_stats: the BatchNorm kernels then run all groups in one launch."""
+    def key(m):
+        return m.eps, m.momentum, m.affine, m.track_running_stats
+    return all(type(m) in (nn.BatchNorm1d, nn.BatchNorm2d, nn.BatchNorm3d) and type(m.momentum) in (int, float) and key(m) == key(mods[0]) and
+               m.track_running_stats == (m.running_mean is not None) for m in mods)
+
+
+def _batch_stats(mods, training: bool) -> ops.BatchStats:
+    """The `bn` argument of the norm ops for the per-group BatchNorm modules: running buffers of all groups concatenated (the buffers
+    themselves for one group), or None without running statistics."""
+    def cat(name):
+        if not mods[0].track_running_stats:
+            return None
+        return getattr(mods[0], name) if len(mods) == 1 else torch.cat([getattr(m, name) for m in mods])
+    return ops.BatchStats(cat("running_mean"), cat("running_var"), float(mods[0].momentum), training)
+
+
+def _commit_stats(mods, bn: ops.BatchStats) -> None:
+    """After a launch with `bn`: what nn.BatchNorm's forward does to its buffers in training mode -- the new running values back into each
+    group's module (one group: the kernel wrote them in place) and the batch counter, a torch in-place add (graph capture records it)."""
+    if not bn.training or bn.running_mean is None:
+        return
+    for g, m in enumerate(mods):
+        if len(mods) > 1:
+            m.running_mean.copy_(bn.running_mean.view(len(mods), -1)[g])
+            m.running_var.copy_(bn.running_var.view(len(mods), -1)[g])
+        m.num_batches_tracked.add_(1)
+
+
+def _batch_norm(mods, z, training: bool):
+    """The BatchNorm kernel alone over a [B, C, H, W] tensor, all groups in one launch (`_fusable_batchnorm(mods)` holds)."""
+    bn = _batch_stats(mods, training)
+    y = ops.batch_norm(z, *_gamma_beta(mods), bn.running_mean, bn.running_var, training, bn.momentum, mods[0].eps)
+    _commit_stats(mods, bn)
+    return y
+
+
 def _need_conv2d(conv_class, ndim, allow_3d: bool = False):
     ok = ((nn.Conv2d, 2), (nn.Conv1d, 1)) + (((nn.Conv3d, 3),) if allow_3d else ())
     if (conv_class, ndim) not in ok:
@@ -166,11 +205,14 @@ def _channel_major(poly_weights, n):
 
 
 def _norm3d(mods, prelus, z, og):
-    """Per-group norm (+ PReLU) of a [B, O, D, H, W] tensor: plain InstanceNorm3d runs on the InstanceNorm kernel with the
+    """Per-group norm (+ PReLU) of a [B, O, D, H, W] tensor: plain InstanceNorm3d / BatchNorm3d run on the norm kernels with the
     volume as one plane; anything else is the caller's own module."""
+    B, O, Dz, Hz, Wz = z.shape
     if all(type(m) is nn.InstanceNorm3d and not m.track_running_stats for m in mods):
-        B, O, Dz, Hz, Wz = z.shape
         y = ops.instance_norm(z.reshape(B, O, Dz * Hz, Wz), *_gamma_beta(mods), eps=mods[0].eps).view(B, O, Dz, Hz, Wz)
+        parts = [y[:, g * og:(g + 1) * og] for g in range(len(mods))]
+    elif _fusable_batchnorm(mods):
+        y = _batch_norm(mods, z.reshape(B, O, Dz * Hz, Wz), mods[0].training).view(B, O, Dz, Hz, Wz)
         parts = [y[:, g * og:(g + 1) * og] for g in range(len(mods))]
     else:
         parts = [mods[g](z[:, g * og:(g + 1) * og]) for g in range(len(mods))]
@@ -303,11 +345,13 @@ class _HipLayer(nn.Module):
 
     def _norm_act(self, z):
         """Tail of the 'norm, then activation' layers (Jacobi, Legendre, Bersnstein, ReLU-KAN, GRAM) for the (lifted) pre-norm
-        tensor: the InstanceNorm kernel, or the caller's own norm modules on the layer's own rank (nn.LayerNorm over the
+        tensor: the InstanceNorm / BatchNorm kernel, or the caller's own norm modules on the layer's own rank (nn.LayerNorm over the
         flattened group), then ``base_activation``."""
         mods = self.layer_norm
         if _fusable_instnorm(mods):
             y = self._lower(ops.instance_norm(z, *_gamma_beta(mods), eps=mods[0].eps))
+        elif _fusable_batchnorm(mods):
+            y = self._lower(_batch_norm(mods, z.contiguous(), self.training))
         else:
             z = self._lower(z)
             og = z.shape[1] // self.groups
@@ -328,11 +372,12 @@ class _FusedTailLayer(_HipLayer):
     pool_types = (bool, tuple)
 
     def _norm_prelu(self, z):
-        """Un-fused tail for the (lifted) [B, O, H, W] pre-norm tensor: the InstanceNorm kernel (or the caller's own norm
+        """Un-fused tail for the (lifted) [B, O, H, W] pre-norm tensor: the InstanceNorm / BatchNorm kernel (or the caller's own norm
         modules on the layer's own rank), then PReLU where the layer has them.  Returns the tensor in the layer's rank."""
         mods, og = self.layer_norm, z.shape[1] // self.groups
-        if _fusable_instnorm(mods):
-            n = self._lower(ops.instance_norm(z.contiguous(), *_gamma_beta(mods), eps=mods[0].eps))
+        if _fusable_instnorm(mods) or _fusable_batchnorm(mods):
+            n = ops.instance_norm(z.contiguous(), *_gamma_beta(mods), eps=mods[0].eps) if _fusable_instnorm(mods) else _batch_norm(mods, z.contiguous(), self.training)
+            n = self._lower(n)
             parts = [n[:, g * og:(g + 1) * og] for g in range(self.groups)]
         else:
             z = self._lower(z)
@@ -365,13 +410,20 @@ class _FusedTailLayer(_HipLayer):
         prelus = [m.weight for m in self.prelus] if self._has_base else None
         xa, xb = self._base_input(x) if self._has_base else (x, None)      # (act(x), x) when the host applies the activation
         windowed = spec.n_basis + int(spec.has_base) > self.plane_window    # more planes than one launch holds: _HipLayer._conv_stage
-        if not windowed and xb is None and _fusable_instnorm(self.layer_norm) and all(p.numel() == 1 for p in prelus or ()):
-            gam, bet = _norm_affine(self.layer_norm)
-            if pool and self.ndim == 2 and self.dropout is None and ops.pool_fusable(pool, *spec.out_hw(x.shape[2], x.shape[3])):
-                return ops.kan_conv_in_prelu(spec, x, wb, ws, gam, bet, prelus, eps=self.layer_norm[0].eps, pool=pool)
-            y = self._lower(ops.kan_conv_in_prelu(spec, x, wb, ws, gam, bet, prelus, eps=self.layer_norm[0].eps))
+        mods = self.layer_norm
+        bnorm = _fusable_batchnorm(mods) and ops.fits_one_launch(spec, x, ws)      # (batch statistics cannot be cut into runs of images)
+        if not windowed and xb is None and (_fusable_instnorm(mods) or bnorm) and all(p.numel() == 1 for p in prelus or ()):
+            gam, bet = _norm_affine(mods)
+            bn = _batch_stats(mods, self.training) if bnorm else None
+            fused_pool = bool(pool) and self.ndim == 2 and self.dropout is None and ops.pool_fusable(pool, *spec.out_hw(x.shape[2], x.shape[3]), batchnorm=bnorm)
+            y = ops.kan_conv_in_prelu(spec, x, wb, ws, gam, bet, prelus, eps=mods[0].eps, pool=pool if fused_pool else False, bn=bn)
+            if bnorm:
+                _commit_stats(mods, bn)
+            if fused_pool:
+                return y
+            y = self._lower(y)
         else:
-            # other norm classes (e.g. BatchNorm2d), a host-applied activation or plane windows: HIP conv stage, then the un-fused tail
+            # other norm classes (e.g. LayerNorm, GroupNorm), a host-applied activation or plane windows: HIP conv stage, then the un-fused tail
             y = self._norm_prelu(self._conv_stage(spec, xa, xb, wb, ws))
         if self.dropout is not None:
             y = self.dropout(y)
@@ -490,6 +542,9 @@ class FastKANConvNDLayer(_HipLayer):
         if all(type(m) is nn.InstanceNorm3d and not m.track_running_stats for m in self.layer_norm):
             B, C, D, H, W = xs.shape
             xn = ops.instance_norm(xs.reshape(B, C, D * H, W), *_gamma_beta(self.layer_norm), eps=self.layer_norm[0].eps).view(B, C, D, H, W)
+        elif _fusable_batchnorm(self.layer_norm):
+            B, C, D, H, W = xs.shape
+            xn = _batch_norm(self.layer_norm, xs.reshape(B, C, D * H, W), self.training).view(B, C, D, H, W)
         else:
             xn = torch.cat([self.layer_norm[g](xs[:, g * cg:(g + 1) * cg]) for g in range(self.groups)], dim=1)
         return conv3d_stage(self._basis_kw(), self.kernel_size, self.stride, self.padding, self.dilation, self.groups, self._base_input(x)[0], xn,
@@ -504,6 +559,8 @@ class FastKANConvNDLayer(_HipLayer):
         if _fusable_instnorm(self.layer_norm):
             xn = self._lift(xs) if xs.dim() == 3 else xs
             xn = ops.instance_norm(xn.contiguous(), *_gamma_beta(self.layer_norm), eps=self.layer_norm[0].eps)
+        elif _fusable_batchnorm(self.layer_norm):
+            xn = _batch_norm(self.layer_norm, (self._lift(xs) if xs.dim() == 3 else xs).contiguous(), self.training)
         else:
             xn = self._lift(torch.cat([self.layer_norm[g](xs[:, g * cg:(g + 1) * cg]) for g in range(self.groups)], dim=1))
         return self._lower(self._conv_stage(self.conv_spec(), self._lift(self._base_input(x)[0]), xn, self._w(self.base_conv), self._w(self.spline_conv)))

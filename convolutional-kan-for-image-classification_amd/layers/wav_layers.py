@@ -20,7 +20,7 @@ import torch.nn.functional as F
 from .. import _lib as L
 from .. import ops
 
-from .conv_layers import _HipLayer, _check_groups, _dropout2d, _filter_norm_kwargs, _fusable_instnorm, _gamma_beta, _norm3d, conv3d_stage
+from .conv_layers import _HipLayer, _batch_norm, _check_groups, _dropout2d, _filter_norm_kwargs, _fusable_batchnorm, _fusable_instnorm, _gamma_beta, _norm3d, conv3d_stage
 
 WAVELET_TYPES = ('mexican_hat', 'morlet', 'dog', 'meyer', 'shannon')
 
@@ -214,6 +214,8 @@ class WavKANConvNDLayer(_HipLayer):
         z = mixed + base
         if _fusable_instnorm(self.layer_norm):
             return self._lower(ops.instance_norm(z, *_gamma_beta(self.layer_norm), eps=self.layer_norm[0].eps))
+        if _fusable_batchnorm(self.layer_norm):
+            return self._lower(_batch_norm(self.layer_norm, z, self.training))
         z = self._lower(z)
         parts = [self.layer_norm[g](z[:, g * og:(g + 1) * og]) for g in range(G)]
         return parts[0] if G == 1 else torch.cat(parts, dim=1)

@@ -8,6 +8,8 @@ Two differentiable entry points, both launching only hand-written HIP kernels:
 * ``kan_conv_in_prelu``  -- the same followed by InstanceNorm2d [+ PReLU]
                             (kan_layers.py:241-243, cheby_kan_layers.py:98).
 * ``instance_norm``      -- InstanceNorm2d alone (fast_kan_layers.py:106, norm on the input).
+* ``batch_norm``         -- BatchNorm2d alone; ``kan_conv_in_prelu(..., bn=)`` is the fused tail of a layer built with
+                            ``norm_layer=BatchNorm2d`` (train.py:67-68: the default of the reference's training script).
 
 All tensors are fp32, NCHW, on a ROCm device.  Groups (kan_layers.py:249-258 loops over them in
 Python) run inside the SAME launches (KanGeom.groups; the group index is folded into the grid):
@@ -678,27 +680,61 @@ def _cat(ts: Sequence[Optional[torch.Tensor]]) -> Optional[torch.Tensor]:
     return ts[0] if len(ts) == 1 else torch.cat([t.reshape(-1) for t in ts])
 
 
-# --------------------------------------------------------------------------------------- InstanceNorm [+ PReLU] [+ max-pool] launchers
-# The only callers of the six kan_instnorm_prelu* entry points.  `pool`: False | True (= MaxPool2d(2, 2), the register-resident kernels, even
-# planes only) | (k, s) (= MaxPool2d(k, s), the generic kernels); `groups` > 1: one PReLU slope per C / groups channels.
+# --------------------------------------------------------------------------------------- InstanceNorm / BatchNorm [+ PReLU] [+ max-pool] launchers
+# The only callers of the six kan_instnorm_prelu* and the two kan_batchnorm_prelu* entry points.  `pool`: False | True (= MaxPool2d(2, 2), the
+# register-resident kernels, even planes only) | (k, s) (= MaxPool2d(k, s), the generic kernels); `groups` > 1: one PReLU slope per C / groups channels.
+@dataclass(frozen=True, eq=False)
+class BatchStats:
+    """What turns a norm launch into a BatchNorm one (`bn=`): the [C] running buffers (None: track_running_stats=False), the momentum of
+    their update and the module's training flag.  The kernels update the buffers in place."""
+    running_mean: Optional[torch.Tensor]
+    running_var: Optional[torch.Tensor]
+    momentum: float
+    training: bool
+
+    @property
+    def batch(self) -> bool:
+        """The statistics are the batch's (torch: training, or no running statistics to use instead)."""
+        return self.training or self.running_mean is None
+
+
+def _bn_workspace(B: int, Ct: int, device) -> torch.Tensor:
+    return torch.empty(L.load().kan_batchnorm_workspace_bytes(B, Ct), device=device, dtype=torch.uint8)
+
+
 def _pool_mode(pool, Ho: int, Wo: int):
     """(2, 2) on an even plane runs the register-resident 2x2 kernels."""
     return True if pool == (2, 2) and pool_fusable(True, Ho, Wo) else pool
 
 
-def _norm_fwd(zs, slab_elems: int, gamma, beta, slope, eps: float, groups: int = 1, pool=False):
+def _norm_fwd(zs, slab_elems: int, gamma, beta, slope, eps: float, groups: int = 1, pool=False, *, bn: Optional[BatchStats] = None):
     """zs: [S, B, C, H, W] partial slabs `slab_elems` apart, or one [B, C, H, W] tensor.  Returns (y, z, mean, rstd, pidx): z the summed
     pre-norm values (slab 0 itself when there is one slab, else a tensor of their own, so that the S-slab buffer can be freed), pidx the
-    uint8 argmax of each pool window (None without a pool)."""
+    uint8 argmax of each pool window (None without a pool).  `bn`: BatchNorm instead of InstanceNorm -- mean and rstd are then [C]."""
     lib = L.load()
     S, z = (1, zs) if zs.dim() == 4 else (zs.shape[0], zs[0])
     B, Ct, Ho, Wo = z.shape
     HW, span, st = Ho * Wo, (Ct // groups if groups > 1 else 0), _stream(zs)
-    mean = torch.empty(B * Ct, device=zs.device, dtype=torch.float32)
+    mean = torch.empty(B * Ct if bn is None else Ct, device=zs.device, dtype=torch.float32)
     rstd = torch.empty_like(mean)
     if S > 1:
         z = torch.empty_like(z)
     pool = _pool_mode(pool, Ho, Wo)
+    if bn is not None:
+        if isinstance(pool, tuple) or (pool and not pool_fusable(True, Ho, Wo)):
+            raise L.KanConvError(f"the BatchNorm kernels fuse MaxPool2d(2, 2) on even planes only, got pool {pool!r} on {Ho}x{Wo}")
+        if bn.training and B * HW < 2:
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(z.shape)}")
+        for t in (bn.running_mean, bn.running_var):
+            if t is not None and (_require(t, "running statistics") is not t or t.numel() != Ct):
+                raise L.KanConvError(f"running statistics must be contiguous [{Ct}] tensors")
+        y = torch.empty((B, Ct, Ho // 2, Wo // 2) if pool else z.shape, device=zs.device, dtype=torch.float32)
+        pidx = torch.empty(y.shape, device=zs.device, dtype=torch.uint8) if pool else None
+        L.check(lib.kan_batchnorm_prelu_fwd(_ptr(zs), S, slab_elems, _ptr(z), _ptr(gamma), _ptr(beta), _ptr(slope), _ptr(y),
+                                            C.c_void_p(pidx.data_ptr() if pool else 0), _ptr(mean), _ptr(rstd), _ptr(bn.running_mean), _ptr(bn.running_var),
+                                            C.c_void_p(_bn_workspace(B, Ct, zs.device).data_ptr()), B, Ct, Ho, Wo, Ct * HW, eps, bn.momentum, span,
+                                            int(bn.training), st), "kan_batchnorm_prelu_fwd")
+        return y, z, mean, rstd, pidx
     if not pool:
         y = torch.empty_like(z)
         L.check(lib.kan_instnorm_prelu_fwd(_ptr(zs), S, slab_elems, _ptr(z), _ptr(gamma), _ptr(beta), _ptr(slope), _ptr(y), _ptr(mean), _ptr(rstd),
@@ -721,15 +757,21 @@ def _norm_fwd(zs, slab_elems: int, gamma, beta, slope, eps: float, groups: int =
     return y, z, mean, rstd, pidx
 
 
-def _norm_bwd(dy, z, mean, rstd, gamma, beta, slope, pidx, groups: int = 1, pool=False):
+def _norm_bwd(dy, z, mean, rstd, gamma, beta, slope, pidx, groups: int = 1, pool=False, *, bn: Optional[BatchStats] = None):
     """Backward of `_norm_fwd` from what it returned.  Returns (dz, dgamma, dbeta, dslope), None for a parameter that is None."""
     lib = L.load()
     dy = dy.contiguous()
     B, Ct, Ho, Wo = z.shape
     HW, span, st = Ho * Wo, (Ct // groups if groups > 1 else 0), _stream(z)
     dz = torch.empty_like(z)
-    dgam, dbet, dslo = (torch.zeros_like(t) if t is not None else None for t in (gamma, beta, slope))
+    dgam, dbet, dslo = ((torch.zeros_like if bn is None else torch.empty_like)(t) if t is not None else None for t in (gamma, beta, slope))
     pool = _pool_mode(pool, Ho, Wo)
+    if bn is not None:                                  # (the parameter gradients are written, not accumulated)
+        L.check(lib.kan_batchnorm_prelu_bwd(_ptr(dy), C.c_void_p(pidx.data_ptr() if pidx is not None else 0), _ptr(z), _ptr(mean), _ptr(rstd), _ptr(gamma),
+                                            _ptr(beta), _ptr(slope), _ptr(dz), _ptr(dgam), _ptr(dbet), _ptr(dslo),
+                                            C.c_void_p(_bn_workspace(B, Ct, z.device).data_ptr()), B, Ct, Ho, Wo, Ct * HW, span, int(bn.batch), st),
+                "kan_batchnorm_prelu_bwd")
+        return dz, dgam, dbet, dslo
     if not pool:
         L.check(lib.kan_instnorm_prelu_bwd(_ptr(dy), _ptr(z), _ptr(mean), _ptr(rstd), _ptr(gamma), _ptr(beta), _ptr(slope), _ptr(dz),
                                            _ptr(dgam), _ptr(dbet), _ptr(dslo), B, Ct, HW, Ct * HW, span, st), "kan_instnorm_prelu_bwd")
@@ -744,12 +786,13 @@ def _norm_bwd(dy, z, mean, rstd, gamma, beta, slope, pidx, groups: int = 1, pool
 
 
 class _KanConvInPrelu(torch.autograd.Function):
-    """y = [MaxPool2d]([PReLU](InstanceNorm(conv stage))).
-    args: spec, eps, use_affine, use_prelu, pool, split, x, *[w_base_g], *[w_basis_g], *[gamma_g], *[beta_g], *[prelu_g]
-    `split`: run the conv stage in split precision where `kan_conv_fwd_split` takes it (inference only: nothing is kept for a backward)."""
+    """y = [MaxPool2d]([PReLU](InstanceNorm(conv stage))), or BatchNorm in its place.
+    args: spec, eps, use_affine, use_prelu, pool, split, bn, x, *[w_base_g], *[w_basis_g], *[gamma_g], *[beta_g], *[prelu_g]
+    `split`: run the conv stage in split precision where `kan_conv_fwd_split` takes it (inference only: nothing is kept for a backward).
+    `bn`: None, or the BatchStats of a BatchNorm tail (running buffers of all groups concatenated)."""
 
     @staticmethod
-    def forward(ctx, spec: ConvSpec, eps: float, use_affine: bool, use_prelu: bool, pool, split: bool, x, *params):
+    def forward(ctx, spec: ConvSpec, eps: float, use_affine: bool, use_prelu: bool, pool, split: bool, bn, x, *params):
         x = _require(x, "x")
         params = [_require(p, "parameter") for p in params]
         G = spec.groups
@@ -767,11 +810,11 @@ class _KanConvInPrelu(torch.autograd.Function):
                 wd = x_pm = None
                 plan = _plan_cached(*_plan_key(spec, x.shape, zs.shape[2] // G))[2]
             else:
-                zs, (wd, x_pm), _, _, plan = _conv_forward(spec, x, None, w_base, w_basis, bool(ctx.needs_input_grad[6]))
+                zs, (wd, x_pm), _, _, plan = _conv_forward(spec, x, None, w_base, w_basis, bool(ctx.needs_input_grad[7]))
             # all groups in one launch: per-channel gamma/beta concatenated, one PReLU slope per Og channels
             gamma, beta, slope = _cat(gammas), _cat(betas), _cat(prelus)
-            y, z, mean, rstd, pidx = _norm_fwd(zs, plan.fwd_slab_elems, gamma, beta, slope, eps, G, pool)
-        ctx.spec, ctx.pool = spec, pool
+            y, z, mean, rstd, pidx = _norm_fwd(zs, plan.fwd_slab_elems, gamma, beta, slope, eps, G, pool, bn=bn)
+        ctx.spec, ctx.pool, ctx.bn = spec, pool, bn
         ctx.wids = (id(w_base[0]) if spec.has_base else None, id(w_basis[0])) if G == 1 else None
         _save(ctx, x=x, z=z, mean=mean, rstd=rstd, wd=wd, x_pm=x_pm, gamma=gamma, beta=beta, slope=slope, pidx=pidx)
         return y
@@ -781,27 +824,28 @@ class _KanConvInPrelu(torch.autograd.Function):
         spec, G = ctx.spec, ctx.spec.groups
         x, z, mean, rstd, wd, x_pm, gamma, beta, slope, pidx = _saved(ctx, "x", "z", "mean", "rstd", "wd", "x_pm", "gamma", "beta", "slope", "pidx")
         with torch.cuda.device(x.device):
-            dz, dgam, dbet, dpre = _norm_bwd(dy, z, mean, rstd, gamma, beta, slope, pidx, G, ctx.pool)
+            dz, dgam, dbet, dpre = _norm_bwd(dy, z, mean, rstd, gamma, beta, slope, pidx, G, ctx.pool, bn=ctx.bn)
             nw = G * (2 if spec.has_base else 1)
-            need_x = ctx.needs_input_grad[6]
-            need_w = any(ctx.needs_input_grad[7:7 + nw])
+            need_x = ctx.needs_input_grad[7]
+            need_w = any(ctx.needs_input_grad[8:8 + nw])
             dx, _, dwb, dws = _conv_backward(spec, x, None, (wd, x_pm), dz, need_x, False, need_w, wids=ctx.wids)
         grads = _flat_grads(spec, dwb, dws)
         if gamma is not None:
             grads += tuple(dgam.view(G, -1).unbind(0)) + tuple(dbet.view(G, -1).unbind(0))
         if slope is not None:
             grads += tuple(dpre.view(G, 1).unbind(0))
-        return (None, None, None, None, None, None, dx if need_x else None) + grads
+        return (None, None, None, None, None, None, None, dx if need_x else None) + grads
 
 
 class _InstanceNorm(torch.autograd.Function):
-    """InstanceNorm2d over NCHW (args: x, gamma|None, beta|None, eps)."""
+    """InstanceNorm2d over NCHW, or BatchNorm2d when `bn` is a BatchStats (args: x, gamma|None, beta|None, eps, bn|None)."""
 
     @staticmethod
-    def forward(ctx, x, gamma, beta, eps: float):
+    def forward(ctx, x, gamma, beta, eps: float, bn=None):
         x = _require(x, "x")
         with torch.cuda.device(x.device):
-            y, _, mean, rstd, _ = _norm_fwd(x, 0, gamma, beta, None, eps)
+            y, _, mean, rstd, _ = _norm_fwd(x, 0, gamma, beta, None, eps, bn=bn)
+        ctx.bn = bn
         _save(ctx, x=x, mean=mean, rstd=rstd, gamma=gamma, beta=beta)
         return y
 
@@ -809,8 +853,8 @@ class _InstanceNorm(torch.autograd.Function):
     def backward(ctx, dy):
         x, mean, rstd, gamma, beta = _saved(ctx, "x", "mean", "rstd", "gamma", "beta")
         with torch.cuda.device(x.device):
-            dx, dg, db, _ = _norm_bwd(dy, x, mean, rstd, gamma, beta, None, None)
-        return dx, dg, db, None
+            dx, dg, db, _ = _norm_bwd(dy, x, mean, rstd, gamma, beta, None, None, bn=ctx.bn)
+        return dx, dg, db, None, None
 
 
 # --------------------------------------------------------------------------------------- Wav-KAN wavelet stage
@@ -886,6 +930,11 @@ def _image_runs(spec: ConvSpec, x: torch.Tensor, out_channels: int) -> Optional[
     return -(-B // runs)
 
 
+def fits_one_launch(spec: ConvSpec, x: torch.Tensor, w_basis: Sequence[torch.Tensor]) -> bool:
+    """The conv stage runs as one launch set, not once per run of images (what a fused BatchNorm tail needs)."""
+    return _image_runs(spec, x, sum(w.shape[0] for w in w_basis)) is None
+
+
 def _apply(stage, spec: ConvSpec, x, xn, w_base, w_basis, extra=()) -> torch.Tensor:
     """Body of the public entry points: stage(x, xn, *flattened weight lists, *extra), once, or once per run of whole images."""
     ws = (list(w_base) if spec.has_base else []) + list(w_basis) + list(extra)
@@ -909,11 +958,15 @@ def kan_conv_phased(spec: ConvSpec, x: torch.Tensor, phases: torch.Tensor, w_bas
     return _apply(lambda a, b, *ws: _KanConv.apply(spec, a, b, phases, *ws), spec, x, xn, w_base, w_basis)
 
 
-def pool_fusable(pool, ho: int, wo: int) -> bool:
+def pool_fusable(pool, ho: int, wo: int, batchnorm: bool = False) -> bool:
     """THE rule for whether the InstanceNorm(+PReLU) kernels can apply the max-pool `pool` to a ho x wo plane: a (k, s) window always
     (the generic kernels), True = MaxPool2d(2, 2) only on an even plane (the register-resident 2x2 kernels).  The layers ask before they
-    request a fused pool; `_norm_fwd` refuses a request that breaks it."""
-    return pool is not True or (ho % 2 == 0 and wo % 2 == 0)
+    request a fused pool; `_norm_fwd` refuses a request that breaks it.  `batchnorm`: the BatchNorm kernels, which fuse MaxPool2d(2, 2)
+    on an even plane and nothing else."""
+    even = ho % 2 == 0 and wo % 2 == 0
+    if batchnorm:
+        return even and (pool is True or tuple(pool) == (2, 2))
+    return pool is not True or even
 
 
 def _norm_pool(pool):
@@ -928,14 +981,17 @@ def _norm_pool(pool):
 
 def kan_conv_in_prelu(spec: ConvSpec, x: torch.Tensor, w_base: Sequence[torch.Tensor], w_basis: Sequence[torch.Tensor],
                       gammas: Optional[Sequence[torch.Tensor]], betas: Optional[Sequence[torch.Tensor]],
-                      prelus: Optional[Sequence[torch.Tensor]], eps: float = 1e-5, pool=False) -> torch.Tensor:
+                      prelus: Optional[Sequence[torch.Tensor]], eps: float = 1e-5, pool=False, bn: Optional[BatchStats] = None) -> torch.Tensor:
     """`pool=True` additionally applies MaxPool2d(kernel 2, stride 2) inside the same kernels (even output planes only); `pool=(k, s)` a general
-    MaxPool2d(k, s) without padding (overlapping windows allowed: the AlexNet pattern (3, 2))."""
+    MaxPool2d(k, s) without padding (overlapping windows allowed: the AlexNet pattern (3, 2)).  `bn`: the norm is BatchNorm2d (per-rank batch
+    statistics; 2x2 pool on even planes only) -- its statistics span the batch, so the call must fit one launch (`fits_one_launch`)."""
     pool = _norm_pool(pool)
+    if bn is not None and not fits_one_launch(spec, x, w_basis):
+        raise L.KanConvError("a BatchNorm tail cannot be cut into runs of images: run kan_conv, then batch_norm")
     split = _SPLIT_INFERENCE and not torch.is_grad_enabled()            # opt-in inference mode: decided where the caller's grad mode is visible
     aff = gammas is not None
     extra = (list(gammas) + list(betas) if aff else []) + (list(prelus) if prelus is not None else [])
-    return _apply(lambda a, _, *ps: _KanConvInPrelu.apply(spec, float(eps), aff, prelus is not None, pool, split, a, *ps),
+    return _apply(lambda a, _, *ps: _KanConvInPrelu.apply(spec, float(eps), aff, prelus is not None, pool, split, bn, a, *ps),
                   spec, x, None, w_base, w_basis, extra)
 
 
@@ -962,4 +1018,12 @@ def kan_conv_fwd_split(spec: ConvSpec, x: torch.Tensor, w_base: torch.Tensor, w_
 
 
 def instance_norm(x: torch.Tensor, gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None, eps: float = 1e-5):
-    return _InstanceNorm.apply(x, gamma, beta, float(eps))
+    return _InstanceNorm.apply(x, gamma, beta, float(eps), None)
+
+
+def batch_norm(x: torch.Tensor, gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None,
+               running_mean: Optional[torch.Tensor] = None, running_var: Optional[torch.Tensor] = None, training: bool = True,
+               momentum: float = 0.1, eps: float = 1e-5):
+    """BatchNorm2d over NCHW with this rank's batch statistics (F.batch_norm's semantics: the running buffers are updated in place when
+    training, used when not; without them the batch statistics serve both modes).  Raises ValueError for one value per channel in training."""
+    return _InstanceNorm.apply(x, gamma, beta, float(eps), BatchStats(running_mean, running_var, float(momentum), bool(training)))

@@ -314,6 +314,38 @@ typedef struct KanNormRoute {
 int kan_norm_route(int backward, int B, int Cn, int H, int W, long long bstride, int n_slabs, long long slab_elems,
                    int pool2x2, int pool_k, int pool_s, int aligned8, KanNormRoute* route);
 
+/* BatchNorm2d with per-rank batch statistics [+ scalar-slope PReLU] [+ MaxPool2d(2, 2)] behind the conv stage: replaces kan_layers.py:241-243
+ * (layer_norm -> prelus) of a layer built with norm_layer=BatchNorm2d, which train.py:67-68 makes the default of the reference's training
+ * script (--norm_layer / --kan_norm_layer), and cheby_kan_layers.py:98 / fast_kan_layers.py:106 (norm only: prelu_a = NULL).
+ * Three launches per direction (per-plane partials, a per-channel finalise, the apply pass) around `workspace`, a caller-owned device
+ * buffer of kan_batchnorm_workspace_bytes bytes that the backward may share with the forward once the forward has run.  No allocation, no
+ * synchronisation; every sum has a fixed order and no value goes through an atomic, so reruns are bit-identical, parameter gradients too.
+ *   z, n_slabs, slab_elems, z_out, gamma, beta, prelu_a, prelu_span, bstride: as in kan_instnorm_prelu_fwd.
+ *   mean / rstd: [Cn] outputs saved for the backward (rstd = 1 / sqrt(biased variance + eps)).
+ *   pool_idx: NULL = y is [B][Cn][H][W]; else (H, W even) y and pool_idx are the dense pooled [B][Cn][H/2][W/2] tensors, pool_idx the
+ *             position 2*dh + dw of each window's maximum, as in kan_instnorm_prelu_pool_fwd; the full-size activation is never written.
+ *   running_mean / running_var: [Cn], both or neither (NULL: track_running_stats=False).
+ *   training != 0: batch statistics; the running buffers, when given, move by `momentum` (the variance by its unbiased estimate N / (N - 1),
+ *             as ATen does), which needs more than one value per channel.
+ *   training == 0: mean = running_mean, rstd = 1 / sqrt(running_var + eps), nothing is updated; without running buffers batch statistics. */
+long long kan_batchnorm_workspace_bytes(int B, int Cn);
+int kan_batchnorm_prelu_fwd(const float* z, int n_slabs, long long slab_elems, float* z_out,
+                            const float* gamma, const float* beta, const float* prelu_a,
+                            float* y, unsigned char* pool_idx, float* mean, float* rstd,
+                            float* running_mean, float* running_var, void* workspace,
+                            int B, int Cn, int H, int W, long long bstride, float eps, double momentum,
+                            int prelu_span, int training, void* stream);
+
+/* Backward of the above (the same reference lines: kan_layers.py:241-243 with norm_layer=BatchNorm2d, train.py:67-68).  dy is the gradient of
+ * y: pooled and routed through pool_idx when that is given.  dz <- gradient of the summed pre-norm value; dgamma / dbeta ([Cn]) and dprelu
+ * ([1], or [Cn / prelu_span]) are WRITTEN, not accumulated.  training != 0: mean / rstd were the batch's (also what an eval-mode forward
+ * without running buffers used); 0: they were the running statistics, dz = (gradient of the normalised value) * rstd.
+ * Any of pool_idx, gamma, beta, prelu_a, dgamma, dbeta, dprelu may be NULL when that feature is off. */
+int kan_batchnorm_prelu_bwd(const float* dy, const unsigned char* pool_idx, const float* z, const float* mean, const float* rstd,
+                            const float* gamma, const float* beta, const float* prelu_a,
+                            float* dz, float* dgamma, float* dbeta, float* dprelu, void* workspace,
+                            int B, int Cn, int H, int W, long long bstride, int prelu_span, int training, void* stream);
+
 /* OPT-IN split-precision forward: NOT reached from kan_conv_fwd, never the default.  Every fp32 operand is cut into three bf16
  * pieces (hi + mid + lo = 24 mantissa bits) and six bf16 MFMA products per 16-deep block are accumulated in fp32: the fp32 result to ~4e-6 of its
  * largest element at K = 20 736 (one fp32 accumulation chain; the exact path sits at ~1e-6), at ~1.7x the speed of the exact fp32 MFMA kernel.
