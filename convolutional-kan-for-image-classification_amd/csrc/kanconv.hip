@@ -2654,15 +2654,19 @@ void launch_in_bwd_regs(hipStream_t st, const KanNormRoute& r, int planes, const
 
 // ============================================================================ optimizer step
 // AdamW over one flat fp32 block (generic_train.py:24 optim.AdamW(lr, weight_decay); formulas and their order as
-// torch/optim/adamw.py's single-tensor path):  p *= 1 - lr wd;  m = m + (g - m)(1 - b1);  v = v b2 + (1 - b2) g g;
-// p += -(lr / bc1) * (m / (sqrt(v) / sqrt(bc2) + eps)).  Pure HBM traffic: 16 B read + 12 B written per element, so the
-// kernel is float4 loads/stores over a grid-stride loop with correctly rounded sqrt / divide (free at this intensity).
-struct AdamArgs { float decay, w1, b2, w2, gscale, inv_bc2_sqrt, eps, neg_step; };
+// torch/optim/adamw.py's single-tensor path):  p *= 1 - lr wd;  m = lerp(m, g, 1 - b1);  v = v b2 + (1 - b2) g g;
+// p += -(lr / bc1) * (m / (sqrt(v) / sqrt(bc2) + eps)).  The lerp has ATen's two branches (one per launch): m + (g - m)(1 - b1) for a
+// weight 1 - b1 < 0.5, g - (g - m) b1 from 0.5 on.  The first form alone leaves m an absolute error of one ulp of the OLD m, which at
+// beta1 = 0 (m must equal g) and |g| << |m| is many times |g|.  Every scalar is formed in double on the host and rounded once; the
+// bias correction multiplies by 1 / sqrt(bc2) where torch divides by sqrt(bc2).  Pure HBM traffic: 16 B read + 12 B written per
+// element, so the kernel is float4 loads/stores over a grid-stride loop with correctly rounded sqrt / divide (free at this intensity).
+struct AdamArgs { float decay, w1, b1, b2, w2, gscale, inv_bc2_sqrt, eps, neg_step; };
 
 __device__ __forceinline__ void adam1(float& p, float g, float& m, float& v, const AdamArgs& a) {
     g *= a.gscale;
     p *= a.decay;
-    m = m + (g - m) * a.w1;
+    const float d = g - m;
+    m = a.w1 < 0.5f ? m + d * a.w1 : g - d * a.b1;
     v = v * a.b2 + a.w2 * g * g;
     const float denom = sqrtf(v) * a.inv_bc2_sqrt + a.eps;
     p += a.neg_step * (m / denom);
@@ -2713,7 +2717,7 @@ AdamArgs adam_args(double lr, double beta1, double beta2, double eps, double wei
     const double bc1 = 1.0 - pow(beta1, (double)step), bc2 = 1.0 - pow(beta2, (double)step);
     AdamArgs a;
     a.decay = (float)(1.0 - lr * weight_decay);                 // hyper-parameters arrive as doubles (Python floats): 1 - beta2 formed
-    a.w1 = (float)(1.0 - beta1); a.b2 = (float)beta2; a.w2 = (float)(1.0 - beta2);      // from a float beta2 is off by 1e-5 relative
+    a.w1 = (float)(1.0 - beta1); a.b1 = (float)beta1; a.b2 = (float)beta2; a.w2 = (float)(1.0 - beta2);      // from a float beta2 is off by 1e-5 relative
     a.gscale = grad_scale; a.inv_bc2_sqrt = (float)(1.0 / sqrt(bc2)); a.eps = (float)eps; a.neg_step = (float)(-lr / bc1);
     return a;
 }

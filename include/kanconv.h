@@ -363,9 +363,12 @@ int kan_conv_fwd_split(const float* x, const void* wc, float* z, const KanGeom* 
 /* One AdamW step over a flat fp32 block of n elements, in place (p, m = exp_avg, v = exp_avg_sq; g is read only and
  * multiplied by grad_scale first).  Replaces the per-tensor update loop of torch.optim.AdamW as the reference builds it
  * (generic_train.py:24 `optim.AdamW(model.parameters(), lr, weight_decay)`, stepped once per batch: evaluations.py train()),
- * same formulas in the same order, amsgrad / maximize off:
- *   p *= 1 - lr*weight_decay;  m += (g - m)(1 - beta1);  v = v*beta2 + (1 - beta2) g^2;
+ * the same formulas in the same order, amsgrad / maximize off:
+ *   p *= 1 - lr*weight_decay;  m = lerp(m, g, 1 - beta1);  v = v*beta2 + (1 - beta2) g^2;
  *   p -= lr / (1 - beta1^step) * m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+ * with ATen's two-branch lerp (m + (g - m)(1 - beta1) below a weight of 0.5, g - (g - m) beta1 from 0.5 on).  Not the same roundings: every
+ * scalar is formed in double and rounded to fp32 once, the bias correction multiplies by 1 / sqrt(1 - beta2^step), and the compiler may fuse
+ * a multiply with the add behind it; tests/test_gpu_adamw_matrix.py bounds the difference against an fp64 reference.
  * `step` counts from 1.  The four blocks must be 16-byte aligned.  HBM-bound: 28 bytes per element. */
 int kan_adamw_step(float* p, const float* g, float* m, float* v, long long n, double lr, double beta1, double beta2, double eps,
                    double weight_decay, int step, float grad_scale, void* stream);

@@ -1,5 +1,7 @@
 """FusedAdamW: host layout logic on CPU; the fused step against torch.optim.AdamW -- the optimizer
-the reference builds (generic_train.py:24) -- on the GPU."""
+the reference builds (generic_train.py:24) -- on the GPU: a short fp32 comparison, then trajectories against fp64 CPU copies (groups,
+add_param_group, ExponentialLR, every gradient form step() accepts, resume through state_dict in both directions).  The kernels' own launch
+cells: tests/test_gpu_adamw_matrix.py."""
 import copy
 
 import pytest
@@ -195,3 +197,194 @@ def test_packed_weights_follow_every_weight_update(gpu_lib, monkeypatch):
         layer.spline_conv[0].weight.data.mul_(1.2)                                   # raw write, not announced: picked up within the cadence
         outs = [layer(x) for _ in range(4)]
         assert torch.equal(outs[-1], uncached()) and not torch.equal(outs[-1], yc)
+
+
+# ------------------------------------------------------------------------------------------------ trajectories against fp64 torch.optim.AdamW
+# FusedAdamW on the GPU against torch.optim.AdamW(foreach=False) on fp64 CPU copies fed the same gradients; the same run in fp32 on the CPU is
+# the noise measure.  Judged as tests/adamw_cells.py judges a step: parameters that started at 0 and the rest, each class normalised by the fp64
+# reference's largest element in it; exp_avg by the reference's largest element; exp_avg_sq elementwise relative (a sum of non-negative terms).
+# Tolerance per tensor: max(2e-6, 4 x the fp32 CPU run's own error).
+def _grads(gen, shape, half=False):
+    """A gradient whose size varies from element to element and step to step (1e-3 .. 1e1); `half`: values an fp16 tensor holds exactly."""
+    g = torch.randn(shape, generator=gen) * 10.0 ** torch.randint(-3, 1, shape, generator=gen).float()
+    return g.half().float() if half else g
+
+
+def _start(gen, shape):
+    n = torch.Size(shape).numel()
+    return (torch.randn(shape, generator=gen) * (torch.arange(n).reshape(shape) % 3 != 0)).float()          # every third element starts at 0
+
+
+def _judge_trajectory(tag, p0, got, r64, r32):
+    """got / r64 / r32: (p, exp_avg, exp_avg_sq).  Returns the failures."""
+    from adamw_cells import FLOOR
+    d = lambda t: t.detach().double().cpu().reshape(-1)
+    zero, bad, line = d(p0) == 0, [], []
+
+    def errs(r):
+        e = {}
+        for name, sel in (("p(from 0)", zero), ("p(rest)", ~zero)):
+            if bool(sel.any()):
+                e[name] = float(((d(r[0]) - d(r64[0]))[sel].abs() / (d(r64[0])[sel].abs().max() + 1e-300)).max())
+        e["m"] = float(((d(r[1]) - d(r64[1])).abs() / (d(r64[1]).abs().max() + 1e-300)).max())
+        e["v"] = float(((d(r[2]) - d(r64[2])).abs() / (d(r64[2]) + 1e-300)).max())
+        return e
+    err, noise = errs(got), errs(r32)
+    for name, e in err.items():
+        tol = max(FLOOR, 4.0 * noise[name])
+        line.append(f"{name} {e:.1e} (tol {tol:.1e}, fp32 reference {noise[name]:.1e})")
+        if not e <= tol:
+            bad.append(f"{tag} {name}: error {e:.3e} > {tol:.3e} (fp32 reference {noise[name]:.3e})")
+    print(f"[adamw trajectory] {tag}: " + "; ".join(line))
+    return bad
+
+
+def _state_of(opt, p):
+    st = opt.state_dict()["state"]
+    idx = [id(q) for g in opt.param_groups for q in g["params"]].index(id(p))
+    if idx not in st:
+        return torch.zeros_like(p), torch.zeros_like(p), 0
+    return st[idx]["exp_avg"], st[idx]["exp_avg_sq"], int(st[idx]["step"])
+
+
+def _padding_is_zero(opt):
+    for flat in opt._flat:
+        if flat is None:
+            continue
+        pad = torch.ones(flat["n"], dtype=torch.bool)
+        for o, n in zip(flat["tab"]["seg_off"].tolist(), flat["tab"]["seg_n"].tolist()):
+            pad[o:o + n] = False
+        assert bool(pad.any()) and bool((flat["block"].cpu()[:, pad].view(torch.int32) == 0).all()), "alignment elements between parameters were written"
+
+
+@pytest.mark.gpu
+def test_trajectory_groups_scheduler_and_gradient_forms(gpu_lib):
+    """12 steps under ExponentialLR: two groups with their own lr / betas / eps / weight_decay and a third added through add_param_group;
+    a 20003-element parameter whose gradient is a view one float into a flat buffer (scalar path), a 5-element one with an fp16 gradient,
+    a frozen one, one with a non-contiguous gradient that only arrives from step 4, one whose gradient moves every step and is gone from
+    step 8, and a betas = (0, 0) group."""
+    gen = torch.Generator().manual_seed(11)
+    spec = dict(a=(20003,), b=(5,), frozen=(33,), c=(7, 9), d=(300,), e=(8195,))
+    p0 = {k: _start(gen, s) for k, s in spec.items()}
+    g0 = dict(lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-4)
+    g1 = dict(lr=3e-2, betas=(0.5, 0.9), eps=1e-3, weight_decay=0.3)
+    g2 = dict(lr=1e-2, betas=(0.0, 0.0), eps=1e-8, weight_decay=1e-2)
+
+    def build(make, cls):
+        ps = {k: nn.Parameter(make(v), requires_grad=k != "frozen") for k, v in p0.items()}
+        opt = cls([dict(params=[ps["a"], ps["b"], ps["frozen"]], **g0), dict(params=[ps["c"], ps["d"]], **g1)])
+        opt.add_param_group(dict(params=[ps["e"]], **g2))
+        return ps, opt, torch.optim.lr_scheduler.ExponentialLR(opt, gamma=0.8)
+    torch_adamw = lambda groups: torch.optim.AdamW(groups, foreach=False)
+    dev, opt, sch = build(lambda v: v.clone().cuda(), K.FusedAdamW)
+    r64, opt64, sch64 = build(lambda v: v.double(), torch_adamw)
+    r32, opt32, sch32 = build(lambda v: v.clone(), torch_adamw)
+    dev["b"].grad_dtype = None                                           # this parameter accepts a gradient of another dtype
+    flatbuf = torch.zeros(20003 + 8, device="cuda")
+    wide = torch.zeros(7, 18, device="cuda")
+    moved, uploads = [], 0
+    for it in range(12):
+        grads = dict(a=_grads(gen, (20003,)), b=_grads(gen, (5,), half=True), frozen=None, c=_grads(gen, (7, 9)) if it >= 3 else None,
+                     d=_grads(gen, (300,)) if it < 7 else None, e=_grads(gen, (8195,)))
+        for ps, cast in ((r64, torch.Tensor.double), (r32, torch.Tensor.clone)):
+            for k, g in grads.items():
+                ps[k].grad = None if g is None else cast(g)
+        flatbuf[1:20004].copy_(grads["a"])
+        dev["a"].grad = flatbuf[1:20004]
+        dev["b"].grad = grads["b"].half().cuda()
+        if grads["c"] is not None:
+            wide[:, ::2] = grads["c"].cuda()
+            dev["c"].grad = wide[:, ::2]
+        moved.append(grads["d"].cuda() if grads["d"] is not None else None)          # (kept alive: every step's gradient has a new address)
+        dev["d"].grad = moved[-1]
+        dev["e"].grad = grads["e"].cuda()
+        if it == 0:
+            assert dev["a"].grad.data_ptr() & 15 == 4 and dev["b"].grad.dtype == torch.float16
+        if it == 3:
+            assert not dev["c"].grad.is_contiguous()
+        before = opt._flat[1]["tab"]["grad_ptrs"]
+        for o, s in ((opt, sch), (opt64, sch64), (opt32, sch32)):
+            o.step(); s.step()
+        uploads += opt._flat[1]["tab"]["grad_ptrs"] != before
+    assert uploads >= 8, "group 1's address table is re-uploaded on every step until d's gradient is gone, and once after"
+    assert len({m.data_ptr() for m in moved if m is not None}) == 7
+    bad = []
+    for k in spec:
+        got = (dev[k], *_state_of(opt, dev[k])[:2])
+        bad += _judge_trajectory(k, p0[k], got, (r64[k], *_state_of(opt64, r64[k])[:2]), (r32[k], *_state_of(opt32, r32[k])[:2]))
+        assert _state_of(opt, dev[k])[2] == _state_of(opt64, r64[k])[2] == dict(a=12, b=12, frozen=0, c=9, d=7, e=12)[k], k
+    assert torch.equal(dev["frozen"].cpu(), p0["frozen"])
+    assert [abs(g["lr"] - h["lr"]) < 1e-15 for g, h in zip(opt.param_groups, opt64.param_groups)] == [True] * 3
+    _padding_is_zero(opt)
+    assert not bad, "\n  ".join(bad)
+
+
+def _resume_setup(seed):
+    gen = torch.Generator().manual_seed(seed)
+    spec = dict(w=(20003,), late=(64,), s=(5,))
+    p0 = {k: _start(gen, s) for k, s in spec.items()}
+    hyper = dict(lr=1e-2, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2)
+    grads = [dict(w=_grads(gen, (20003,)), late=_grads(gen, (64,)) if it >= 2 else None, s=_grads(gen, (5,))) for it in range(8)]
+    return spec, p0, hyper, grads
+
+
+def _feed(ps, opt, grads, cast):
+    for step in grads:
+        for k, g in step.items():
+            ps[k].grad = None if g is None else cast(g)
+        opt.step()
+
+
+@pytest.mark.gpu
+def test_resume_from_fused_into_torch_adamw(gpu_lib):
+    """4 fused steps, state_dict() into a fresh torch.optim.AdamW, 4 more on both sides: both end where an uninterrupted fp64 run ends."""
+    spec, p0, hyper, grads = _resume_setup(21)
+    make = lambda cast, cls, **kw: (lambda ps: (ps, cls(list(ps.values()), **hyper, **kw)))({k: nn.Parameter(cast(v)) for k, v in p0.items()})
+    r64, opt64 = make(torch.Tensor.double, torch.optim.AdamW, foreach=False)
+    r32, opt32 = make(torch.Tensor.clone, torch.optim.AdamW, foreach=False)
+    dev, opt = make(lambda v: v.clone().cuda(), K.FusedAdamW)
+    _feed(r64, opt64, grads, torch.Tensor.double)
+    _feed(r32, opt32, grads, torch.Tensor.clone)
+    _feed(dev, opt, grads[:4], lambda g: g.cuda())
+    sd = opt.state_dict()
+    assert [int(sd["state"][i]["step"]) for i in range(3)] == [4, 2, 4]
+    cont = {k: nn.Parameter(dev[k].detach().cpu().clone()) for k in spec}
+    opt_c = torch.optim.AdamW(list(cont.values()), foreach=False)
+    opt_c.load_state_dict(copy.deepcopy(sd))
+    _feed(cont, opt_c, grads[4:], torch.Tensor.clone)
+    _feed(dev, opt, grads[4:], lambda g: g.cuda())
+    bad = []
+    for k in spec:
+        ref = (r64[k], *_state_of(opt64, r64[k])[:2])
+        noise = (r32[k], *_state_of(opt32, r32[k])[:2])
+        bad += _judge_trajectory(k + " (fused throughout)", p0[k], (dev[k], *_state_of(opt, dev[k])[:2]), ref, noise)
+        bad += _judge_trajectory(k + " (torch after 4 fused steps)", p0[k], (cont[k], *_state_of(opt_c, cont[k])[:2]), ref, noise)
+        assert _state_of(opt_c, cont[k])[2] == _state_of(opt, dev[k])[2] == _state_of(opt64, r64[k])[2]
+    _padding_is_zero(opt)
+    assert not bad, "\n  ".join(bad)
+
+
+@pytest.mark.gpu
+def test_resume_from_torch_adamw_into_fused(gpu_lib):
+    """4 steps of torch.optim.AdamW (one parameter has 2: per-parameter step counts differ), its state_dict() into a fresh FusedAdamW, 4 more."""
+    spec, p0, hyper, grads = _resume_setup(22)
+    make = lambda cast, **kw: (lambda ps: (ps, torch.optim.AdamW(list(ps.values()), **hyper, foreach=False)))({k: nn.Parameter(cast(v)) for k, v in p0.items()})
+    r64, opt64 = make(torch.Tensor.double)
+    r32, opt32 = make(torch.Tensor.clone)
+    _feed(r64, opt64, grads, torch.Tensor.double)
+    _feed(r32, opt32, grads[:4], torch.Tensor.clone)
+    sd = copy.deepcopy(opt32.state_dict())
+    assert [int(sd["state"][i]["step"]) for i in range(3)] == [4, 2, 4]
+    dev = {k: nn.Parameter(r32[k].detach().clone().cuda()) for k in spec}
+    opt = K.FusedAdamW(list(dev.values()), lr=0.5, betas=(0.1, 0.1), weight_decay=0.0)          # every hyper-parameter comes from the loaded state
+    opt.load_state_dict(sd)
+    assert opt._flat[0]["steps"] == [4, 2, 4] and opt.param_groups[0]["lr"] == hyper["lr"] and tuple(opt.param_groups[0]["betas"]) == hyper["betas"]
+    _feed(r32, opt32, grads[4:], torch.Tensor.clone)
+    _feed(dev, opt, grads[4:], lambda g: g.cuda())
+    bad = []
+    for k in spec:
+        bad += _judge_trajectory(k, p0[k], (dev[k], *_state_of(opt, dev[k])[:2]), (r64[k], *_state_of(opt64, r64[k])[:2]),
+                                 (r32[k], *_state_of(opt32, r32[k])[:2]))
+        assert _state_of(opt, dev[k])[2] == _state_of(opt64, r64[k])[2] == 8 - 2 * (k == "late")
+    _padding_is_zero(opt)
+    assert not bad, "\n  ".join(bad)
