@@ -28,3 +28,6 @@ from .layers.wav_layers import (WaveletConvND, WaveletConvNDFast, WaveletConvNDF
 from .layers.kan_conv import wavkan_conv   # noqa: F401,E402
 from .layers.poly_layers import (BesselKANConv3DLayer, FibonacciKANConv3DLayer, GegenbauerKANConv3DLayer, HermiteKANConv3DLayer,   # noqa: F401,E402
                                  LaguerreKANConv3DLayer, LucasKANConv3DLayer, TaylorKANConv3DLayer, FourierKANConv3DLayer)
+from .layers.head_layers import (ChebyKANLayer, BesselKANLayer, FibonacciKANLayer, GegenbauerKANLayer, HermiteKANLayer, LaguerreKANLayer, LucasKANLayer,   # noqa: F401,E402
+                                 ChebyKAN, BesselKAN, FibonacciKAN, GegenbauerKAN, HermiteKAN, LaguerreKAN, LucasKAN, mlp_chebykan, mlp_besselkan,
+                                 mlp_fibonaccikan, mlp_gegenbauerkan, mlp_hermitekan, mlp_laguerrekan, mlp_lucaskan)

@@ -73,6 +73,7 @@ SIGNATURES = {
     "kan_plan": (_I, [_GP, _BP, C.POINTER(KanPlan)]),
     "kan_tile_orders": (_I, [_GP, _BP]),
     "kan_pack_weights": (_I, [_P, _P, _P, _P, _GP, _BP, _P]),
+    "kan_pack_weights_iod": (_I, [_P, _P, _P, _GP, _BP, _P]),
     "kan_pack_cacheable": (_I, [_GP, _BP]),
     "kan_pack_weights_cached": (_I, [_P, _P, _P, _P, _GP, _BP, _P, _I, _I, _I, _P]),
     "kan_conv_fwd": (_I, [_P, _P, _P, _P, _GP, _BP, _P, _P]),
@@ -84,6 +85,7 @@ SIGNATURES = {
     "kan_conv_fwd_expanded": (_I, [_P, _P, _P, _GP, _BP, _P]),
     "kan_conv_bwd_weight_expanded": (_I, [_P, _P, _P, _GP, _BP, _P]),
     "kan_unpack_wgrad": (_I, [_P, _P, _P, _GP, _BP, _P]),
+    "kan_unpack_wgrad_iod": (_I, [_P, _P, _GP, _BP, _P]),
     "kan_slab_reduce": (_I, [_P, _I, _LL, _P, _I, _I, _I, _LL, _P]),
     "kan_instnorm_prelu_fwd": (_I, [_P, _I, _LL, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _LL, _F, _I, _P]),
     "kan_instnorm_prelu_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _LL, _I, _P]),

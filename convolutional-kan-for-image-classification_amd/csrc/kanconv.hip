@@ -257,6 +257,105 @@ __global__ __launch_bounds__(256) void k_fold_slabs(float* __restrict__ slabs, i
     if (sg == 0 && i < n) slabs[i] = (part[0][e] + part[1][e]) + (part[2][e] + part[3][e]);
 }
 
+// ---------------------------------------------------------------------------- [I][O][n] coefficients of the MLP KAN heads
+// The seven recurrence / Chebyshev MLP layers keep ONE parameter, coeffs[c][o][k] (input-major, basis index minor), and no base branch;
+// their contraction is the conv stage on 1x1 planes with a 1x1 kernel.  The two kernels below move between that layout and the packed
+// ones directly -- wp[wp_row(c, k)][o] and the flat gradient dwp[row(c, k)][o] -- so that no [O][C*n] copy of a head's weights (604 MB at
+// 9216 -> 4096, degree 3) is ever made.  A tile is one input c x IOD_TO outputs: IOD_TO * n contiguous floats of coeffs on one side, n row
+// segments of IOD_TO floats on the other.  LDS holds it plane-major with a pitch of IOD_TO + 4, so that the row side moves whole float4s
+// (ds_read_b128 / ds_write_b128, conflict-free) and the coefficient side scatters / gathers single floats.
+// `vec` bit 0: the coeffs side is 16-byte aligned per tile (base pointer aligned, O * n % 4 == 0); bit 1: the packed side is.
+constexpr int IOD_TO = 256, IOD_PITCH = IOD_TO + 4;
+
+__device__ __forceinline__ float4 iod_ld4(const float* p, bool vec) {
+    return vec ? *reinterpret_cast<const float4*>(p) : make_float4(p[0], p[1], p[2], p[3]);
+}
+__device__ __forceinline__ void iod_st4(float* p, float4 v, bool vec) {
+    if (vec) *reinterpret_cast<float4*>(p) = v;
+    else { p[0] = v.x; p[1] = v.y; p[2] = v.z; p[3] = v.w; }
+}
+__device__ __forceinline__ float4 iod_add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+
+// Tile `tile_id` -> (c, o0, live outputs no, float4 groups of the padded row segment wq).  Opad is a multiple of 32, so a group of four
+// outputs is never cut by the end of a row.
+struct IodTile { int c, o0, no, wq; };
+__device__ __forceinline__ IodTile iod_tile(const PackGeo& q, long long tile_id, int o_tiles) {
+    IodTile t;
+    t.c = (int)(tile_id / o_tiles);
+    t.o0 = (int)(tile_id - (long long)t.c * o_tiles) * IOD_TO;
+    t.no = max(0, min(IOD_TO, q.O - t.o0));
+    t.wq = min(IOD_TO, q.Opad - t.o0) >> 2;
+    return t;
+}
+
+__global__ __launch_bounds__(256) void k_pack_iod(const float* __restrict__ coeffs, float* __restrict__ wp, PackGeo q, int o_tiles, long long n_tiles,
+                                                  int vec) {
+    __shared__ __attribute__((aligned(16))) float tile[KAN_MAX_PLANES * IOD_PITCH];
+    const int n = q.nb, tid = threadIdx.x;
+    for (long long tile_id = blockIdx.x; tile_id < n_tiles; tile_id += gridDim.x) {
+        const IodTile t = iod_tile(q, tile_id, o_tiles);
+        const float* src = coeffs + ((size_t)t.c * q.O + t.o0) * n;
+        const int cnt = t.no * n;                                   // contiguous source floats of this tile
+        auto put = [&](int f, float v) { const int o = fastdiv(f, q.divNb); tile[(f - o * n) * IOD_PITCH + o] = v; };
+        if (vec & 1) {                                              // (cnt is a multiple of 4 here: O * n and IOD_TO * n are)
+            for (int f = 4 * tid; f < cnt; f += 1024) {
+                const float4 v = *reinterpret_cast<const float4*>(src + f);
+                put(f, v.x); put(f + 1, v.y); put(f + 2, v.z); put(f + 3, v.w);
+            }
+        } else {
+            for (int f = tid; f < cnt; f += 256) put(f, src[f]);
+        }
+        __syncthreads();
+        for (int u = tid; u < n * t.wq; u += 256) {                 // row p of the tile, outputs o .. o + 3; outputs >= O are written as zeros
+            const int p = t.wq == IOD_TO / 4 ? u >> 6 : u / t.wq, o = 4 * (u - p * t.wq);
+            float4 v = *reinterpret_cast<const float4*>(&tile[p * IOD_PITCH + o]);
+            if (o + 3 >= t.no) { if (o >= t.no) v.x = 0.f; if (o + 1 >= t.no) v.y = 0.f; if (o + 2 >= t.no) v.z = 0.f; v.w = 0.f; }
+            iod_st4(wp + (size_t)wp_row(q, 0, t.c, p) * q.Opad + t.o0 + o, v, vec & 2);
+        }
+        __syncthreads();
+    }
+}
+
+// dcoeffs[c][o][k] = sum over the slabs of dwp[row(c, k)][o], the slabs added in the order of k_unpack (eight running sums over slabs
+// s, s + 8, ..., the remainder into the first, then a fixed tree), so both unpackers return the same bits.
+__global__ __launch_bounds__(256) void k_unpack_iod(const float* __restrict__ dwp, float* __restrict__ dcoeffs, PackGeo q, int o_tiles, long long n_tiles,
+                                                    int n_slabs, long long slab_elems, int vec) {
+    __shared__ __attribute__((aligned(16))) float tile[KAN_MAX_PLANES * IOD_PITCH];
+    const int n = q.nb, tid = threadIdx.x;
+    for (long long tile_id = blockIdx.x; tile_id < n_tiles; tile_id += gridDim.x) {
+        const IodTile t = iod_tile(q, tile_id, o_tiles);
+        for (int u = tid; u < n * t.wq; u += 256) {
+            const int p = t.wq == IOD_TO / 4 ? u >> 6 : u / t.wq, o = 4 * (u - p * t.wq);
+            if (o >= t.no) continue;                                // a group of padding columns only: never read back below
+            const float* a = dwp + (size_t)wp_row(q, 0, t.c, p) * q.Opad + t.o0 + o;
+            const bool v2 = vec & 2;
+            const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+            float4 s0 = z, s1 = z, s2 = z, s3 = z, s4 = z, s5 = z, s6 = z, s7 = z;
+            int sl = 0;
+            for (; sl + 8 <= n_slabs; sl += 8) {
+                const float* b = a + (size_t)sl * slab_elems;
+                s0 = iod_add4(s0, iod_ld4(b, v2)); s1 = iod_add4(s1, iod_ld4(b + slab_elems, v2));
+                s2 = iod_add4(s2, iod_ld4(b + 2 * slab_elems, v2)); s3 = iod_add4(s3, iod_ld4(b + 3 * slab_elems, v2));
+                s4 = iod_add4(s4, iod_ld4(b + 4 * slab_elems, v2)); s5 = iod_add4(s5, iod_ld4(b + 5 * slab_elems, v2));
+                s6 = iod_add4(s6, iod_ld4(b + 6 * slab_elems, v2)); s7 = iod_add4(s7, iod_ld4(b + 7 * slab_elems, v2));
+            }
+            for (; sl < n_slabs; ++sl) s0 = iod_add4(s0, iod_ld4(a + (size_t)sl * slab_elems, v2));
+            *reinterpret_cast<float4*>(&tile[p * IOD_PITCH + o]) =
+                iod_add4(iod_add4(iod_add4(s0, s1), iod_add4(s2, s3)), iod_add4(iod_add4(s4, s5), iod_add4(s6, s7)));
+        }
+        __syncthreads();
+        float* dst = dcoeffs + ((size_t)t.c * q.O + t.o0) * n;
+        const int cnt = t.no * n;
+        auto get = [&](int f) { const int o = fastdiv(f, q.divNb); return tile[(f - o * n) * IOD_PITCH + o]; };
+        if (vec & 1) {
+            for (int f = 4 * tid; f < cnt; f += 1024) *reinterpret_cast<float4*>(dst + f) = make_float4(get(f), get(f + 1), get(f + 2), get(f + 3));
+        } else {
+            for (int f = tid; f < cnt; f += 256) dst[f] = get(f);
+        }
+        __syncthreads();
+    }
+}
+
 // Backward-data weight layout, derived from the forward one by a per-tap tiled transpose:
 //   wd[(tap * Opad16 + o)][ct * 128 + half * 64 + cl * P + p] = wp[k((tap*C+c), p)][o],
 //   c = (ct*2 + half) * CH + cl,  CH = 64 / P whole channels per 64-column half
@@ -2747,8 +2846,31 @@ static bool pack_needs_clear(const KanGeom* g, const KanPlan& pl) {
     return pl.KC != pl.IPC * pl.P || (g->C * g->kh * g->kw) % pl.IPC != 0;
 }
 
+// The [I][O][n] layout of the MLP KAN heads (k_pack_iod / k_unpack_iod): what it covers, checked before any plan or launch.
+static int iod_scope(const KanGeom* g, const KanBasis* b) {
+    if (!g || !b) return fail("null geometry or basis");
+    if (g->kh != 1 || g->kw != 1) return fail("the [I][O][n] coefficient layout takes 1x1 kernels only");
+    if (ngroups(g) != 1) return fail("the [I][O][n] coefficient layout takes one group only");
+    if (b->act != KAN_ACT_NONE) return fail("the [I][O][n] coefficient layout has no base branch (act must be KAN_ACT_NONE)");
+    return 0;
+}
+// Tile count and grid of the two [I][O][n] kernels: one tile per (input, IOD_TO outputs), a capped grid that strides over them.
+struct IodLaunch { int o_tiles; long long n_tiles; unsigned blocks; };
+static IodLaunch iod_launch(const KanGeom* g, const KanPlan& pl) {
+    IodLaunch l;
+    l.o_tiles = ceil_div(pl.Opad, IOD_TO);
+    l.n_tiles = (long long)g->C * l.o_tiles;
+    l.blocks = (unsigned)(l.n_tiles < 16384 ? l.n_tiles : 16384);
+    return l;
+}
+static int iod_vec(const void* coeffs, const void* packed, const KanGeom* g, const KanBasis* b) {
+    return ((((size_t)coeffs & 15) == 0 && ((long long)g->O * b->n_basis) % 4 == 0) ? 1 : 0) | ((((size_t)packed & 15) == 0) ? 2 : 0);
+}
+
+// `iod`: w_basis is the [C][O][n_basis] coefficient tensor of an MLP KAN head (kan_pack_weights_iod) instead of the conv layout; only the
+// kernel that fills wp differs -- the clears before it and the bwd-data layout derived from wp are the same code.
 static int pack_weights_impl(const float* w_base, const float* w_basis, float* wp, float* wd, const KanGeom* g, const KanBasis* b,
-                             const unsigned long long* fp, int fp_cur, void* stream) {
+                             const unsigned long long* fp, int fp_cur, void* stream, bool iod = false) {
     ConvPlan cp;
     if (int rc = plan_conv(g, b, &cp)) return rc;
     const KanPlan& pl = cp.pub;
@@ -2775,7 +2897,12 @@ static int pack_weights_impl(const float* w_base, const float* w_basis, float* w
     const long long n_tiles = (long long)tiles_x * tiles_y;
     const long long cap = fp ? 1024 : 4096;             // cached mode: the usual outcome is an early exit, keep the grid small
     dim3 grid((unsigned)(n_tiles < cap ? n_tiles : cap), 1, G);
-    hipLaunchKernelGGL(k_pack, grid, dim3(256), 0, st, w_base, w_basis, wp, q, nb_base, wp_gs, tiles_x, tiles_y, fp, fp_cur);
+    if (iod) {
+        const IodLaunch l = iod_launch(g, pl);
+        hipLaunchKernelGGL(k_pack_iod, dim3(l.blocks), dim3(256), 0, st, w_basis, wp, q, l.o_tiles, l.n_tiles, iod_vec(w_basis, wp, g, b));
+    } else {
+        hipLaunchKernelGGL(k_pack, grid, dim3(256), 0, st, w_base, w_basis, wp, q, nb_base, wp_gs, tiles_x, tiles_y, fp, fp_cur);
+    }
     if (wd && cp.bwd_data == Route::DW) {
         if (hipMemcpyAsync(wd, wp, (size_t)pl.packed_weight_bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return fail("memcpy failed");
     } else if (wd) {
@@ -2791,6 +2918,11 @@ static int pack_weights_impl(const float* w_base, const float* w_basis, float* w
 
 int kan_pack_weights(const float* w_base, const float* w_basis, float* wp, float* wd, const KanGeom* g, const KanBasis* b, void* stream) {
     return pack_weights_impl(w_base, w_basis, wp, wd, g, b, nullptr, 0, stream);
+}
+
+int kan_pack_weights_iod(const float* coeffs, float* wp, float* wd, const KanGeom* g, const KanBasis* b, void* stream) {
+    if (int rc = iod_scope(g, b)) return rc;
+    return pack_weights_impl(nullptr, coeffs, wp, wd, g, b, nullptr, 0, stream, true);
 }
 
 int kan_tile_orders(const KanGeom* g, const KanBasis* b) {
@@ -2825,7 +2957,8 @@ int kan_pack_weights_cached(const float* w_base, const float* w_basis, float* wp
     return pack_weights_impl(w_base, w_basis, wp, wd, g, b, force ? nullptr : ring, cur, stream);
 }
 
-int kan_unpack_wgrad(const float* dwp, float* dw_base, float* dw_basis, const KanGeom* g, const KanBasis* b, void* stream) {
+// `iod`: dw_basis is the [C][O][n_basis] gradient of an MLP KAN head's coefficients (kan_unpack_wgrad_iod).
+static int unpack_wgrad_impl(const float* dwp, float* dw_base, float* dw_basis, const KanGeom* g, const KanBasis* b, void* stream, bool iod) {
     ConvPlan cp;
     if (int rc = plan_conv(g, b, &cp)) return rc;
     const KanPlan& pl = cp.pub;
@@ -2843,8 +2976,23 @@ int kan_unpack_wgrad(const float* dwp, float* dw_base, float* dw_basis, const Ka
     }
     const int nb_base = hb ? ceil_div(g->C * T, 32) : 0;
     dim3 grid(nb_base + ceil_div(g->C * b->n_basis * T, 32), ceil_div(g->O, 32), G);
-    hipLaunchKernelGGL(k_unpack, grid, dim3(256), 0, st, dwp, dw_base, dw_basis, q, nb_base, n_slabs, pl.bwd_weight_slab_elems, dwp_gs);
+    if (iod) {
+        const IodLaunch l = iod_launch(g, pl);
+        hipLaunchKernelGGL(k_unpack_iod, dim3(l.blocks), dim3(256), 0, st, dwp, dw_basis, q, l.o_tiles, l.n_tiles, n_slabs, pl.bwd_weight_slab_elems,
+                           iod_vec(dw_basis, dwp, g, b));
+    } else {
+        hipLaunchKernelGGL(k_unpack, grid, dim3(256), 0, st, dwp, dw_base, dw_basis, q, nb_base, n_slabs, pl.bwd_weight_slab_elems, dwp_gs);
+    }
     return launch_ok("unpack");
+}
+
+int kan_unpack_wgrad(const float* dwp, float* dw_base, float* dw_basis, const KanGeom* g, const KanBasis* b, void* stream) {
+    return unpack_wgrad_impl(dwp, dw_base, dw_basis, g, b, stream, false);
+}
+
+int kan_unpack_wgrad_iod(const float* dwp, float* dcoeffs, const KanGeom* g, const KanBasis* b, void* stream) {
+    if (int rc = iod_scope(g, b)) return rc;
+    return unpack_wgrad_impl(dwp, nullptr, dcoeffs, g, b, stream, true);
 }
 
 int kan_position_major(const float* src, float* dst, int B, int Cn, int HW, long long bstride, void* stream) {

@@ -3,7 +3,7 @@
   reference                                         this file
   layers/kan_layers.py:8-114     KANLayer            KANLayer   (same ctor, parameter names and state_dict keys)
   models/kans.py:300-327         KAN (MLP)           KAN
-  models/kans.py:481-485,556-574 mlp_kan / factory   mlp_kan, MLP_KAN_FACTORY["KAN"]
+  models/kans.py:481-485,556-574 mlp_kan / factory   mlp_kan, MLP_KAN_FACTORY["KAN"]; the ChebyKAN / recurrence-family keys come from head_layers.py
 
 A KANLayer is the conv layer's algebra on a 1x1 image with a 1x1 kernel:
 ``F.linear(act(x), W_b) + F.linear(B(x).flatten, W_s.view(O, I*n))`` with the basis index minor (kan_layers.py:104-106),
@@ -19,6 +19,7 @@ import torch.nn.functional as F
 from .. import _lib as L
 from .. import ops
 from .conv_layers import _act_code, _host_applied
+from .head_layers import HEAD_FACTORY
 
 
 class KANLayer(nn.Module):
@@ -89,5 +90,6 @@ def mlp_kan(layers_hidden: List[int], dropout: float = 0.0, grid_size: int = 5, 
                grid_range=grid_range, l1_decay=l1_decay, first_dropout=first_dropout)
 
 
-MLP_KAN_FACTORY = {"KAN": mlp_kan}
+# 8 of the reference's 17 keys; FastKAN, Legendre, Bersnstein, Jacobi, GRAM, Fourier, ReLU, Taylor and Wav heads (base branches, norms or biases) are not built
+MLP_KAN_FACTORY = {"KAN": mlp_kan, **HEAD_FACTORY}
 _ = F

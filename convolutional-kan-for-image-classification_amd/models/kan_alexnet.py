@@ -25,7 +25,7 @@ class AlexNetKAN(nn.Module):
                  classifier_degree: Optional[int] = None, **kwargs: Any) -> None:
         super().__init__()
         if classifier_type in ("KAN", "AlexNetKAN") and (kan_classifier or "KAN") not in MLP_KAN_FACTORY:
-            raise NotImplementedError(f"kan_classifier={kan_classifier!r}: only the B-spline MLP KAN head is built ({list(MLP_KAN_FACTORY)})")
+            raise NotImplementedError(f"kan_classifier={kan_classifier!r}: no MLP KAN head of that name is built on the HIP path (built: {list(MLP_KAN_FACTORY)})")
         if kan_conv not in CONV_KAN_FACTORY:
             raise ValueError(f"kan_conv={kan_conv!r} is not on the accelerated path: {list(CONV_KAN_FACTORY)}")
         make = CONV_KAN_FACTORY[kan_conv]

@@ -83,7 +83,7 @@ class VGGKAN(nn.Module):
         if classifier_type in ("KAN", "HiddenKAN", "VGGKAN"):
             name = kan_classifier or "KAN"
             if name not in MLP_KAN_FACTORY:
-                raise NotImplementedError(f"kan_classifier={name!r}: only the B-spline MLP KAN head is built ({list(MLP_KAN_FACTORY)})")
+                raise NotImplementedError(f"kan_classifier={name!r}: no MLP KAN head of that name is built on the HIP path (built: {list(MLP_KAN_FACTORY)})")
             # kan_vgg.py:258-283: the head inherits spline_order / grid_size / grid_range, SiLU base, no dropout, filtered by signature
             offered_h = dict(spline_order=spline_order, grid_size=grid_size, base_activation=nn.SiLU, grid_range=grid_range,
                              l1_decay=l1_decay, degree=degree, dropout=0.0, first_dropout=False, bias=False)

@@ -47,6 +47,8 @@ class ConvSpec:
     dilation: Tuple[int, int]
     groups: int = 1
     first: int = 0                # plane window of a Poly / Cheby / Fourier basis: the family's index of the first plane (frequency) emitted
+    w_layout: int = 0             # 0: the reference's conv weights [O, C*n, kh, kw] (+ base weights); W_IOD: ONE coefficient tensor [I, O, n]
+                                  # (the MLP KAN heads: 1x1 kernel, one group, no base branch), packed / unpacked by the *_iod kernels
 
     @property
     def has_base(self) -> bool:
@@ -55,6 +57,14 @@ class ConvSpec:
     def out_hw(self, H: int, W: int) -> Tuple[int, int]:
         (kh, kw), (sh, sw), (ph, pw), (dh, dw) = self.kernel, self.stride, self.padding, self.dilation
         return (H + 2 * ph - dh * (kh - 1) - 1) // sh + 1, (W + 2 * pw - dw * (kw - 1) - 1) // sw + 1
+
+
+W_IOD = 1
+
+
+def _outputs(spec: ConvSpec, w_basis: Sequence[torch.Tensor]) -> int:
+    """Output channels of the conv stage, all groups."""
+    return w_basis[0].shape[1] if spec.w_layout == W_IOD else sum(w.shape[0] for w in w_basis)
 
 
 def _device_table(spec: ConvSpec) -> bool:
@@ -426,6 +436,12 @@ def _pack(lib, spec, geom, basis, plan, plan_key, w_base, w_basis, need_dgrad, p
         wb_all, ws_all = _stack(w_base), _stack(w_basis)          # keep the stacked copies alive until the pack is enqueued
         L.check(lib.kan_pack_weights(_ptr(wb_all), _ptr(ws_all), _ptr(wp), _ptr(wd), C.byref(geom), C.byref(basis), st), "kan_pack_weights")
         return wp, wd
+    if spec.w_layout == W_IOD:
+        # packed afresh on every call: no _PACKED entry, no fingerprint ring (caching this layout is not built yet)
+        wp = torch.empty(plan.packed_weight_bytes // 4, device=device, dtype=torch.float32)
+        wd = torch.empty(plan.bwd_data_weight_bytes // 4, device=device, dtype=torch.float32) if need_dgrad else None
+        L.check(lib.kan_pack_weights_iod(_ptr(w_basis[0]), _ptr(wp), _ptr(wd), C.byref(geom), C.byref(basis), st), "kan_pack_weights_iod")
+        return wp, wd
     if _PACK_CACHE_MAX <= 0 or spec.groups != 1 or phases is not None or not _cacheable(plan_key):
         return fresh()
     ws, wb = w_basis[0], w_base[0]
@@ -465,7 +481,7 @@ def _conv_forward(spec: ConvSpec, x, xn, w_base, w_basis, need_dgrad: bool = Tru
     """Returns (z_slabs [S,B,O,Ho,Wo], (bwd-data weight layout or None, position-major x or None), geom, basis, plan)."""
     lib = L.load()
     Ct = x.shape[1]
-    plan_key = _plan_key(spec, x.shape, w_basis[0].shape[0])
+    plan_key = _plan_key(spec, x.shape, _outputs(spec, w_basis) // spec.groups)
     geom, basis, plan = _plan_cached(*plan_key)
     basis = _with_table(_with_phases(basis, phases), spec, x.device)
     st = _stream(x)
@@ -552,15 +568,20 @@ def _conv_backward(spec: ConvSpec, x, xn, packed, dz, need_x: bool, need_xn: boo
             _launch(_sample("bwd_weight", geom, plan, x_pm is not None and dz_pm is not None, xn is not None), x,
                     lambda: lib.kan_conv_bwd_weight(_ptr(dz), _ptr(x), _ptr(xs), _ptr(dwp), C.byref(geom), C.byref(basis), _ptr(x_pm),
                                                     _ptr(dz_pm), st))
-        sb = _sink_for(wids[0], (Og, Cg, kh, kw), x.device) if (wids and G == 1 and spec.has_base) else None
-        ss = _sink_for(wids[1], (Og, Cg * spec.n_basis, kh, kw), x.device) if (wids and G == 1) else None
-        dwb = (sb.unsqueeze(0) if sb is not None else
-               torch.empty((G, Og, Cg, kh, kw), device=x.device, dtype=torch.float32)) if spec.has_base else None
-        dws = ss.unsqueeze(0) if ss is not None else torch.empty((G, Og, Cg * spec.n_basis, kh, kw), device=x.device, dtype=torch.float32)
-        L.check(lib.kan_unpack_wgrad(_ptr(dwp), _ptr(dwb), _ptr(dws), C.byref(geom), C.byref(basis), st), "kan_unpack_wgrad")
-        dw_basis = list(dws.unbind(0))
-        if spec.has_base:
-            dw_base = list(dwb.unbind(0))
+        if spec.w_layout == W_IOD:                      # the gradient lands in the coefficients' own [I, O, n] layout; no GRAD_SINKS write-through
+            dco = torch.empty((Cg, Og, spec.n_basis), device=x.device, dtype=torch.float32)
+            L.check(lib.kan_unpack_wgrad_iod(_ptr(dwp), _ptr(dco), C.byref(geom), C.byref(basis), st), "kan_unpack_wgrad_iod")
+            dw_basis = [dco]
+        else:
+            sb = _sink_for(wids[0], (Og, Cg, kh, kw), x.device) if (wids and G == 1 and spec.has_base) else None
+            ss = _sink_for(wids[1], (Og, Cg * spec.n_basis, kh, kw), x.device) if (wids and G == 1) else None
+            dwb = (sb.unsqueeze(0) if sb is not None else
+                   torch.empty((G, Og, Cg, kh, kw), device=x.device, dtype=torch.float32)) if spec.has_base else None
+            dws = ss.unsqueeze(0) if ss is not None else torch.empty((G, Og, Cg * spec.n_basis, kh, kw), device=x.device, dtype=torch.float32)
+            L.check(lib.kan_unpack_wgrad(_ptr(dwp), _ptr(dwb), _ptr(dws), C.byref(geom), C.byref(basis), st), "kan_unpack_wgrad")
+            dw_basis = list(dws.unbind(0))
+            if spec.has_base:
+                dw_base = list(dwb.unbind(0))
     dx = dxn = None
     if need_x or need_xn:
         S = plan.bwd_data_splits
@@ -623,6 +644,11 @@ class _KanConv(torch.autograd.Function):
         xn = _require(xn, "xn") if xn is not None else None
         weights = [_require(w, "weight") for w in weights]
         w_base, w_basis = _split_weights(spec, weights)
+        if spec.w_layout == W_IOD:
+            want = (x.shape[1], w_basis[0].shape[1] if w_basis[0].dim() == 3 else -1, spec.n_basis)
+            if len(weights) != 1 or tuple(w_basis[0].shape) != want or spec.groups != 1 or spec.kernel != (1, 1) or spec.has_base or phases is not None:
+                raise L.KanConvError(f"w_layout = W_IOD takes one [inputs, outputs, n_basis] coefficient tensor, a 1x1 kernel, one group and no base branch; "
+                                     f"got {[tuple(w.shape) for w in weights]} for input {tuple(x.shape)}, n_basis {spec.n_basis}")
         if phases is not None:
             phases = _require(phases, "phases")
             want = (x.shape[1] // spec.groups, 2, spec.n_basis) if spec.kind == L.BASIS_RELU else (spec.n_basis,)
@@ -932,13 +958,13 @@ def _image_runs(spec: ConvSpec, x: torch.Tensor, out_channels: int) -> Optional[
 
 def fits_one_launch(spec: ConvSpec, x: torch.Tensor, w_basis: Sequence[torch.Tensor]) -> bool:
     """The conv stage runs as one launch set, not once per run of images (what a fused BatchNorm tail needs)."""
-    return _image_runs(spec, x, sum(w.shape[0] for w in w_basis)) is None
+    return _image_runs(spec, x, _outputs(spec, w_basis)) is None
 
 
 def _apply(stage, spec: ConvSpec, x, xn, w_base, w_basis, extra=()) -> torch.Tensor:
     """Body of the public entry points: stage(x, xn, *flattened weight lists, *extra), once, or once per run of whole images."""
     ws = (list(w_base) if spec.has_base else []) + list(w_basis) + list(extra)
-    n = _image_runs(spec, x, sum(w.shape[0] for w in w_basis))
+    n = _image_runs(spec, x, _outputs(spec, w_basis))
     if n is None:
         return stage(x, xn, *ws)
     xs = x.split(n)

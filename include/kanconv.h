@@ -172,6 +172,16 @@ int kan_tile_orders(const KanGeom* geom, const KanBasis* basis);
 int kan_pack_weights(const float* w_base, const float* w_basis, float* wp, float* wd,
                      const KanGeom* geom, const KanBasis* basis, void* stream);
 
+/* kan_pack_weights for the MLP KAN heads whose one parameter is stored input-major: coeffs[C][O][n_basis] -- the `cheby_coeffs` /
+ * `bessel_coeffs` / `fib_coeffs` / `gegenbauer_coeffs` / `hermite_coeffs` / `laguerre_coeffs` / `lucas_coeffs` parameter that the layer's
+ * einsum('bid,iod->bo', basis, coeffs) contracts (cheby_kan_layers.py:16,34-36; bessel_kan_layers.py:19,35; fibonacci_kan_layers.py:16,37;
+ * gegenbauer_kan_layers.py:16,32; hermite_kan_layers.py:15,27; laguerre_kan_layers.py:15,35; lucas_kan_layers.py:16,37).  That contraction is
+ * the conv stage on [B, C, 1, 1] with a 1x1 kernel, and this call fills wp and wd (NULL to skip) with exactly what kan_pack_weights writes
+ * for the tensor permuted to [O][C*n_basis][1][1] -- padding included, so the conv launchers cannot tell which packer ran -- without that
+ * permuted copy ever existing.  Scope: kh = kw = 1, one group, act == KAN_ACT_NONE, any basis the planner accepts; anything else fails
+ * before a launch.  Replaces nothing in the reference (layout only). */
+int kan_pack_weights_iod(const float* coeffs, float* wp, float* wd, const KanGeom* geom, const KanBasis* basis, void* stream);
+
 /* The same with the packed layouts kept by the caller between calls (single-group geometries for which kan_pack_cacheable
  * returns 1; 16-byte aligned weight tensors).  Every call fingerprints the reference-layout weights on the device -- the two 32-bit sums
  * sum_i bits_i * (2 i + 1) and sum_i rotl(bits_i, i mod 32), over all elements or over every sample_stride-th group of
@@ -242,6 +252,11 @@ int kan_conv_bwd_weight_expanded(const float* dz_pm, const float* e_pm, float* d
  * first folded into slab 0 in place. */
 int kan_unpack_wgrad(const float* dwp, float* dw_base, float* dw_basis,
                      const KanGeom* geom, const KanBasis* basis, void* stream);
+
+/* kan_unpack_wgrad for the same heads: dcoeffs[C][O][n_basis], the gradient of the `..._coeffs` parameter through the einsum lines listed at
+ * kan_pack_weights_iod (autograd of cheby_kan_layers.py:34-36 and its six siblings), bit for bit the permuted result of kan_unpack_wgrad:
+ * the plan.bwd_weight_splits slabs are added in the same order (dwp is scratch in the same way).  Same scope as kan_pack_weights_iod. */
+int kan_unpack_wgrad_iod(const float* dwp, float* dcoeffs, const KanGeom* geom, const KanBasis* basis, void* stream);
 
 /* out = sum_s slabs[s]  over an NCHW block (B, Cn channels, HW pixels, batch stride bstride). */
 int kan_slab_reduce(const float* slabs, int n_slabs, long long slab_elems, float* out,
