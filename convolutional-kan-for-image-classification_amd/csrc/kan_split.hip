@@ -1,4 +1,4 @@
-// libkanconv, OPT-IN split-precision forward (round 3).  NOT on any default path: `dtype` f32 stays exact; this mode is reached only
+// libkanconv, OPT-IN split-precision forward (round 3) and input gradient (k_split_bwd_data, further down).  NOT on any default path: `dtype` f32 stays exact; this mode is reached only
 // through its own entry points (kan_split_*), carries its own tolerance in the tests and is reported under `other_workloads` by bench.py.
 //
 // Every fp32 operand (expanded plane value, weight) is cut into three bf16 pieces hi + mid + lo (24 mantissa bits); each 16-deep k-block runs six
@@ -67,6 +67,17 @@ __device__ inline void split3(float v, __bf16& h, __bf16& m, __bf16& l) {
     h = (__bf16)v; const float r1 = v - (float)h;
     m = (__bf16)r1; const float r2 = r1 - (float)m;
     l = (__bf16)r2;
+}
+
+// two values -> three packed bf16 pairs (v_cvt_pk_bf16_f32 rounds to nearest even; a bf16 widens to fp32 by a shift / mask)
+__device__ __forceinline__ void split_pair(float v0, float v1, unsigned& h, unsigned& m, unsigned& l) {
+    typedef float f32x2 __attribute__((ext_vector_type(2)));
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    auto pk = [](float a, float b) { f32x2 f = {a, b}; return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2)); };
+    h = pk(v0, v1);
+    const float r0 = v0 - __builtin_bit_cast(float, h << 16), r1 = v1 - __builtin_bit_cast(float, h & 0xffff0000u);
+    m = pk(r0, r1);
+    l = pk(r0 - __builtin_bit_cast(float, m << 16), r1 - __builtin_bit_cast(float, m & 0xffff0000u));
 }
 
 // ---- weights: reference layout (base [O][C][3][3], spline [O][C*8][3][3], channel c*8+k) -> wc[cg][step][piece][k-half][o][8 bf16]
@@ -158,16 +169,6 @@ __global__ __launch_bounds__(512, 1) void k_split_fwd(const float* __restrict__ 
     // PRODUCER waves (4 .. 7, one per SIMD next to an MFMA wave): the hardware issues their vector work in the MFMA waves' gaps.  They compute the
     // next channel group's pieces into registers while the current group is contracted, and write them once the halo tile is free.
     struct Pieces { uint2 h[NP], m[NP], l[NP]; };          // per plane: the 4 channels' pieces, packed bf16 pairs (ch0 ch1 | ch2 ch3)
-    // two values -> three packed bf16 pairs (v_cvt_pk_bf16_f32 rounds to nearest even; a bf16 widens to fp32 by a shift / mask)
-    auto split_pair = [&](float v0, float v1, unsigned& h, unsigned& m, unsigned& l) {
-        typedef float f32x2 __attribute__((ext_vector_type(2)));
-        typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-        auto pk = [](float a, float b) { f32x2 f = {a, b}; return __builtin_bit_cast(unsigned, __builtin_convertvector(f, bf16x2)); };
-        h = pk(v0, v1);
-        const float r0 = v0 - __builtin_bit_cast(float, h << 16), r1 = v1 - __builtin_bit_cast(float, h & 0xffff0000u);
-        m = pk(r0, r1);
-        l = pk(r0 - __builtin_bit_cast(float, m << 16), r1 - __builtin_bit_cast(float, m & 0xffff0000u));
-    };
     auto compute = [&](int cg, Pieces& pc, const float* xsrc) {
         float v[4][NP];
 #pragma unroll
@@ -314,6 +315,238 @@ __global__ __launch_bounds__(512, 1) void k_split_fwd(const float* __restrict__ 
             for (int r = 0; r < 16; ++r) zi[(size_t)(i * 32 + mfma_row(r, lane)) * HW + j * 32 + m] = acc[i][j][r];
 }
 
+// ---- the input gradient (k_split_bwd_data): what kan_conv_bwd_data computes for a layer in scope, G = dgrad(dz, W_p) per plane, dx = sum_p plane_p'(x) G_p,
+// into ONE slab, every element written once.  The forward's loop turned round:
+//   tile    128 rows x 128 pixels per workgroup, 512 threads = 4 MFMA waves (64 x 64 each) + 4 producer waves.  Rows = two 64-row halves of 7 channels x 9
+//           planes (+ one zero row): the `wd` tile of the exact kernel, each MFMA wave row owns whole channels for the epilogue.  Pixels: as the forward (two
+//           8x8 images or eight rows of a 16x16 image), but ordered so that 16 consecutive columns are ONE lane group of a ds_read_b128: on 8x8 planes column
+//           n = 16 row + 8 image + col (the same row of both images), on 16x16 planes one image row;
+//   depth   per group of 16 output channels 9 steps of 16: step = tap, k-half = o-octet.  No zero padding; both k-halves of a step share the tap shift;
+//   B side  raw dz: the producers load the group's 16 x 128 fp32 values (8 per thread), cut them (split_pair) and write a zero-bordered halo tile per piece and
+//           o-octet, ONE 16-byte chunk per cell (the 8 consecutive o of a lane's operand share).  Every tap reads the same tile through a shifted address,
+//           shift = -(r - 1) rows - (t - 1) cells (the forward's with the sign turned).  Row pitch: 16x16 planes 17 chunks (the 16 cells of a lane group are
+//           consecutive: all sixteen 16-byte slots; the right border cell overlaps the next row's left one); 8x8 planes 9 chunks per image with the second
+//           image 104 = 8 mod 16 chunks behind the first (its 8 cells take the other 8 slots).  The tile is small (16 / 18 KB for all six planes), so there
+//           are TWO: group g + 1 is written while group g is contracted, and no step waits for a halo write;
+//   A side  weights pre-cut (kan_split_pack_weights_bwd_data) into wcd[row tile][step][piece][k-half][row][8 bf16 of consecutive o], streamed by 16-byte
+//           LDS-DMA into the forward's ring of six one-step buffers, under the same counted waits; one barrier per two steps.  18 steps (two groups) are
+//           unrolled, so ring slot, halo buffer and tap shift of every step are compile-time;
+//   loop    the forward's explicit-ISA step: 24 MFMAs, smallest products first, the 12 ds_read_b128 of the next step one per MFMA gap;
+//   end     accumulators -> LDS (the ring's space), all 512 threads contract the 9 planes of their (channel, pixel) pairs with stage_unit_grad (the exact
+//           kernel's derivative values) and store dx; the x values are requested before the LDS round trip.  Rows of padding channels are never stored.
+constexpr int BD_CH = 7, BD_TCH = 2 * BD_CH, BD_TP = 132;            // channels per 64-row half / per row tile; pitch (floats) of the G tile in the epilogue
+template <int PW> struct BwdGeo {
+    static constexpr int PITCH = PW == 8 ? 9 : 17, IMG1 = 104;       // chunks per halo row; PW = 8: chunk offset of the second image
+    static constexpr int TILEC = PW == 8 ? 196 : 172;                // chunks of one (piece, o-octet) tile: 10 halo rows (+ the overhang of the last border cell)
+    static constexpr int TILEB = TILEC * 16, HALOB = 6 * TILEB, HWP = PW * PW;
+    __device__ static constexpr int cell(int n) {                    // chunk of tile column n (0..127)
+        return PW == 8 ? ((n >> 3) & 1) * IMG1 + ((n >> 4) + 1) * PITCH + (n & 7) + 1 : ((n >> 4) + 1) * PITCH + (n & 15) + 1;
+    }
+};
+template <int PW> constexpr int lds_bytes_bwd() { return NBUF * WSLOT + 2 * BwdGeo<PW>::HALOB + 64; }
+static_assert(128 * BD_TP * 4 <= NBUF * WSLOT, "the G tile of the epilogue fits the weight ring");
+inline int bwd_row_tiles(int C) { return (C + BD_TCH - 1) / BD_TCH; }
+
+// ---- weights: reference layout -> wcd[row tile][step = (o / 16) * 9 + tap][piece][k-half][row][8 bf16: o = 16 (o / 16) + 8 k-half + j];
+// row = 64 half + 9 channel + plane, channel c = 14 tile + 7 half + channel; rows 63 / 127 and rows of channels >= C are zero
+__global__ void k_cut_weights_bwd_data(const float* __restrict__ wb, const float* __restrict__ ws, __bf16* __restrict__ wcd, int NC, int NO, int c_tiles) {
+    const int steps = (NO / 16) * 9;
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;             // (row tile, step, kh, row)
+    if (idx >= c_tiles * steps * 2 * 128) return;
+    const int row = idx & 127, kh = (idx >> 7) & 1, st = (idx >> 8) % steps, ct = (idx >> 8) / steps;
+    const int tap = st % 9, o0 = (st / 9) * 16 + kh * 8, rr = row & 63, c = ct * BD_TCH + (row >> 6) * BD_CH + rr / NP, p = rr % NP;
+    bf16x8 h, m, l;
+    for (int j = 0; j < 8; ++j) {
+        float v = 0.f;
+        if (rr < BD_CH * NP && c < NC) {
+            const int o = o0 + j;
+            v = p == 0 ? wb[((size_t)o * NC + c) * 9 + tap] : ws[((size_t)o * NC * 8 + c * 8 + (p - 1)) * 9 + tap];
+        }
+        __bf16 a, b, d; split3(v, a, b, d); h[j] = a; m[j] = b; l[j] = d;
+    }
+    const size_t step = (size_t)ct * steps + st;
+    bf16x8* dst = (bf16x8*)wcd;
+    dst[((step * 3 + 0) * 2 + kh) * 128 + row] = h;
+    dst[((step * 3 + 1) * 2 + kh) * 128 + row] = m;
+    dst[((step * 3 + 2) * 2 + kh) * 128 + row] = l;
+}
+
+template <int PW>
+__global__ __launch_bounds__(512, 1) void k_split_bwd_data(const float* __restrict__ dz, const float* __restrict__ x, const __bf16* __restrict__ wcd, float* __restrict__ dx, DevBasis bs, int NC, int NO, int c_tiles) {
+    using Gm = BwdGeo<PW>;
+    constexpr int PITCH = Gm::PITCH, TILEB = Gm::TILEB, HALOB = Gm::HALOB, HW = Gm::HWP, RINGB = NBUF * WSLOT;
+    const int NOG = NO / 16, TOTAL_STEPS = NOG * 9;                        // groups of 16 output channels (even: O % 128 == 0), 16-deep steps
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned char* sW = smem;                                              // weight ring; the G tile of the epilogue afterwards
+    unsigned char* sH = smem + RINGB;                                      // two halo buffers of [piece][o-octet] tiles
+    float* sTab = (float*)(smem + RINGB + 2 * HALOB);
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int w_o = wave & 1, w_p = (wave >> 1) & 1, kh = lane >> 5, m = lane & 31;
+    const int ct = blockIdx.x % c_tiles, ptile = blockIdx.x / c_tiles;
+    const int b0 = PW == 8 ? ptile * 2 : ptile >> 1, half_img = PW == 8 ? 0 : (ptile & 1);      // PW = 16: image b0, rows [8 half_img, 8 half_img + 8)
+
+    for (int i = tid; i < 2 * HALOB / 16; i += 512) ((uint4*)sH)[i] = uint4{0u, 0u, 0u, 0u};
+    if (tid < 16) sTab[tid] = bs.tab[tid];
+
+    // weight stream: 3 chunks of 16 B per producer thread and step (a step of a row tile is 12 KB contiguous)
+    const __amdgpu_buffer_rsrc_t w_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(wcd), 0, (int)((long long)c_tiles * TOTAL_STEPS * WSLOT), 0x00020000);
+    auto issue2 = [&](int t, int slot) {
+        unsigned char* dst = sW + (slot % NBUF) * WSLOT + (wave & 3) * 1024;
+        const int so = __builtin_amdgcn_readfirstlane((ct * TOTAL_STEPS + t) * WSLOT);
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rs, (__attribute__((address_space(3))) void*)(dst + j * 4096), 16, (int)(((tid & 255) + 256 * j) * 16), so, 0, 0);
+    };
+
+    // epilogue units: thread = (tile column en, channel slot tid >> 7 of four), channels slot, slot + 4, ...
+    const int en = tid & 127;
+    const size_t epix = PW == 8 ? (size_t)(b0 + ((en >> 3) & 1)) * NC * HW + (en >> 4) * 8 + (en & 7) : (size_t)b0 * NC * HW + half_img * 128 + en;
+
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+
+    if (tid >= 256) {
+        // PRODUCER waves: thread = (tile column q, o-octet hh); per group 8 dz values -> three 16-byte chunks.  They also stream the weights, exactly as
+        // the forward's: steps t+6, t+7 go out after the barrier of pair t, which is entered only when all but the six newest copies have landed.  The dz
+        // loads of a group are issued BEFORE the copies of their pair, so the counted wait of the next barrier covers them too.
+        const int q = en, hh = (tid >> 7) & 1;
+        const unsigned cellB = (unsigned)(hh * TILEB + Gm::cell(q) * 16);
+        const float* dzq = PW == 8 ? dz + ((size_t)(b0 + ((q >> 3) & 1)) * NO + hh * 8) * HW + (q >> 4) * 8 + (q & 7) : dz + ((size_t)b0 * NO + hh * 8) * HW + half_img * 128 + q;
+        // PW = 16: the ninth real row of the tile (image row 8 below the upper half: halo row 9; row 7 above the lower half: halo row 0), lanes q < 16
+        const bool extra = PW == 16 && q < 16;
+        const unsigned cellX = (unsigned)(hh * TILEB + ((half_img ? 0 : 9) * PITCH + (q & 15) + 1) * 16);
+        const float* dzx = dz + ((size_t)b0 * NO + hh * 8) * HW + (half_img ? 7 : 8) * 16 + (q & 15);
+        auto load = [&](int og, float (&v)[8], const float* src) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) v[j] = src[(size_t)(og * 16 + j) * HW];
+        };
+        auto cutwrite = [&](const float (&v)[8], int buf, unsigned cellb) {
+            uint4 h, md, l;
+            split_pair(v[0], v[1], h.x, md.x, l.x); split_pair(v[2], v[3], h.y, md.y, l.y);
+            split_pair(v[4], v[5], h.z, md.z, l.z); split_pair(v[6], v[7], h.w, md.w, l.w);
+            unsigned char* d = sH + buf * HALOB + cellb;
+            *(uint4*)d = h; *(uint4*)(d + 2 * TILEB) = md; *(uint4*)(d + 4 * TILEB) = l;
+        };
+        float dv[8], dxv[8];
+        for (int i = 0; i < NBUF; ++i) issue2(i, i);
+        __syncthreads();                                   // B1: zero fill, tables
+        load(0, dv, dzq); cutwrite(dv, 0, cellB);
+        if (extra) { load(0, dxv, dzx); cutwrite(dxv, 0, cellX); }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                                   // B2
+        int t = 0;
+#pragma unroll 1
+        for (int gg = 0; gg < NOG / 2; ++gg) {             // groups 2 gg (halo buffer 0) and 2 gg + 1 (buffer 1)
+            const bool more = gg + 1 < NOG / 2;
+#pragma unroll
+            for (int pr = 0; pr < 9; ++pr) {
+                if (t + 4 < TOTAL_STEPS) asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+                // buffer 1 is read from the step before barrier 4 on and free since barrier 8 of the previous round; buffer 0 is read until barrier 4
+                // and again after barrier 8: written after barriers 1 and 6, complete (lgkmcnt(0) above) at barriers 2 and 7
+                if (pr == 1) { cutwrite(dv, 1, cellB); if (extra) cutwrite(dxv, 1, cellX); }
+                if (pr == 6 && more) { cutwrite(dv, 0, cellB); if (extra) cutwrite(dxv, 0, cellX); }
+                if (pr == 0) { load(2 * gg + 1, dv, dzq); if (extra) load(2 * gg + 1, dxv, dzx); }
+                if (pr == 5 && more) { load(2 * gg + 2, dv, dzq); if (extra) load(2 * gg + 2, dxv, dzx); }
+                if (t + 6 < TOTAL_STEPS) { issue2(t + 6, 2 * pr); issue2(t + 7, 2 * pr + 1); }
+                t += 2;
+            }
+        }
+    } else {
+        // operand addresses (bytes from smem): the tap shift and the halo buffer are added per step (compile-time)
+        unsigned bBase[2];
+#pragma unroll
+        for (int bj = 0; bj < 2; ++bj) bBase[bj] = (unsigned)(RINGB + kh * TILEB + Gm::cell(w_p * 64 + bj * 32 + m) * 16);
+        const unsigned aLane = (unsigned)((kh * 128 + w_o * 64 + m) * 16);
+        struct Frag { f32x4 a[3][2], b[3][2]; };
+        // step s of the 18 of a round: ring slot s % 6, halo buffer s / 9, tap s % 9
+        auto b_off = [](int s) { const int tap = s % 9; return (s / 9) * HALOB - ((tap / 3 - 1) * PITCH + (tap % 3 - 1)) * 16; };
+        auto loadF = [&](Frag& f, int s) {
+            const unsigned ao = aLane + (unsigned)((s % NBUF) * WSLOT);
+            const unsigned p0 = bBase[0] + (unsigned)b_off(s), p1 = bBase[1] + (unsigned)b_off(s);
+            DSR(f.a[0][0], ao, 0);    DSR(f.a[0][1], ao, 512);
+            DSR(f.b[0][0], p0, 0);    DSR(f.b[0][1], p1, 0);
+            DSR(f.a[1][0], ao, 4096); DSR(f.a[1][1], ao, 4608);
+            DSR(f.b[1][0], p0, 2 * TILEB); DSR(f.b[1][1], p1, 2 * TILEB);
+            DSR(f.a[2][0], ao, 8192); DSR(f.a[2][1], ao, 8704);
+            DSR(f.b[2][0], p0, 4 * TILEB); DSR(f.b[2][1], p1, 4 * TILEB);
+        };
+        // the 24 MFMAs of the step held in c, the 12 operand reads of step s_next into n, one per MFMA gap
+        auto step = [&](Frag& c, Frag& n, int s_next) {
+            const unsigned ao = aLane + (unsigned)((s_next % NBUF) * WSLOT);
+            const unsigned p0 = bBase[0] + (unsigned)b_off(s_next), p1 = bBase[1] + (unsigned)b_off(s_next);
+            int gap = 0;
+            auto G = [&]() {
+                switch (gap) {
+                    case 0: DSR(n.a[0][0], ao, 0); break;            case 1: DSR(n.a[0][1], ao, 512); break;
+                    case 2: DSR(n.b[0][0], p0, 0); break;            case 3: DSR(n.b[0][1], p1, 0); break;
+                    case 4: DSR(n.a[1][0], ao, 4096); break;         case 5: DSR(n.a[1][1], ao, 4608); break;
+                    case 6: DSR(n.b[1][0], p0, 2 * TILEB); break;    case 7: DSR(n.b[1][1], p1, 2 * TILEB); break;
+                    case 8: DSR(n.a[2][0], ao, 8192); break;         case 9: DSR(n.a[2][1], ao, 8704); break;
+                    case 10: DSR(n.b[2][0], p0, 4 * TILEB); break;   case 11: DSR(n.b[2][1], p1, 4 * TILEB); break;
+                    default: break;
+                }
+                ++gap;
+            };
+            asm volatile("s_waitcnt lgkmcnt(0)" : FRAG_REGS(c) :: "memory");
+            MF4(c.a[2][0], c.a[2][1], c.b[0][0], c.b[0][1]);
+            MF4(c.a[0][0], c.a[0][1], c.b[2][0], c.b[2][1]);
+            MF4(c.a[1][0], c.a[1][1], c.b[1][0], c.b[1][1]);
+            MF4(c.a[1][0], c.a[1][1], c.b[0][0], c.b[0][1]);
+            MF4(c.a[0][0], c.a[0][1], c.b[1][0], c.b[1][1]);
+            MF4(c.a[0][0], c.a[0][1], c.b[0][0], c.b[0][1]);
+        };
+        __builtin_amdgcn_s_setprio(3);
+        Frag F0, F1;
+        __syncthreads();                                   // B1
+        __syncthreads();                                   // B2: halo tile of group 0 written, steps 0..5 landed
+        loadF(F0, 0);
+#pragma unroll 1
+        for (int gg = 0; gg < NOG / 2; ++gg) {
+#pragma unroll
+            for (int pr = 0; pr < 9; ++pr) {
+                step(F0, F1, 2 * pr + 1);
+                asm volatile("s_waitcnt lgkmcnt(0)" : FRAG_REGS(F1) :: "memory");
+                BAR_PLAIN();                               // steps t+2, t+3 have landed; every MFMA wave holds steps t, t+1 in registers: their ring slots are free
+                step(F1, F0, (2 * pr + 2) % 18);           // (after the last step of all: a read of stale, in-bounds LDS that nobody uses)
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)" : FRAG_REGS(F0) :: "memory");
+        __builtin_amdgcn_s_setprio(0);
+    }
+
+    // ---- epilogue: G -> LDS, contract the 9 planes of each channel with plane'(x)
+    float xv[4];
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+        const int cl = (tid >> 7) + 4 * it, c = ct * BD_TCH + cl;
+        xv[it] = (cl < BD_TCH && c < NC) ? x[epix + (size_t)c * HW] : 0.f;
+    }
+    float* sG = (float*)sW;
+    __syncthreads();                                       // every wave is done with the ring
+    if (tid < 256) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) sG[(w_o * 64 + i * 32 + mfma_row(r, lane)) * BD_TP + w_p * 64 + j * 32 + m] = acc[i][j][r];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < 4; ++it) {
+        const int cl = (tid >> 7) + 4 * it, c = ct * BD_TCH + cl;
+        if (cl >= BD_TCH || c >= NC) continue;
+        const int row0 = (cl / BD_CH) * 64 + (cl % BD_CH) * NP;
+        dx[epix + (size_t)c * HW] = stage_unit_grad<KAN_BASIS_BSPLINE, FAST_BSPLINE_SILU>(bs, sTab, xv[it], xv[it], sG + row0 * BD_TP + en, BD_TP).dx;
+    }
+}
+
 
 const char* split_reject(const KanGeom* g, const KanBasis* b) {
     if (!g || !b) return "null geometry / basis";
@@ -323,6 +556,13 @@ const char* split_reject(const KanGeom* g, const KanBasis* b) {
     if (g->groups > 1 || g->C % CG || g->O % 128 || (g->H == 8 && g->B % 2) || g->C < CG) return "split-precision forward: one group, C % 8 == 0, O % 128 == 0, even batch on 8x8 planes";
     if (g->x_bstride != (long long)g->C * g->H * g->W || g->y_bstride != (long long)g->O * g->H * g->W) return "split-precision forward: dense NCHW tensors";
     if ((long long)(g->C / CG) * NSTEP * 3 * 2 * g->O * 16 >= (1ll << 31)) return "split-precision forward: cut weights must stay under 2 GiB";
+    return nullptr;
+}
+
+// the bwd-data launch: the scope of split_reject, and its own cut-weight buffer under 2 GiB
+const char* split_bwd_reject(const KanGeom* g, const KanBasis* b) {
+    if (const char* why = split_reject(g, b)) return why;
+    if ((long long)bwd_row_tiles(g->C) * (g->O / 16) * 9 * WSLOT >= (1ll << 31)) return "split-precision bwd-data: cut weights must stay under 2 GiB";
     return nullptr;
 }
 
@@ -359,6 +599,35 @@ int kan_conv_fwd_split(const float* x, const void* wc, float* z, const KanGeom* 
     else
         hipLaunchKernelGGL(k_split_fwd<16>, dim3((unsigned)(g->B * 2 * o_tiles)), dim3(512), lds_bytes<16>(), (hipStream_t)stream, x, (const __bf16*)wc, z, db, g->C, g->O, o_tiles);
     return hipGetLastError() == hipSuccess ? 0 : kan_fail_msg("kan_conv_fwd_split: launch failed%s", "");
+}
+
+long long kan_split_bwd_data_weight_bytes(const KanGeom* g, const KanBasis* b) {
+    if (split_bwd_reject(g, b)) return 0;
+    return (long long)bwd_row_tiles(g->C) * (g->O / 16) * 9 * WSLOT;
+}
+
+int kan_split_pack_weights_bwd_data(const float* w_base, const float* w_basis, void* wcd, const KanGeom* g, const KanBasis* b, void* stream) {
+    const char* why = split_bwd_reject(g, b);
+    if (why) return kan_fail_msg("%s", why);
+    if (!w_base || !w_basis || !wcd) return kan_fail_msg("kan_split_pack_weights_bwd_data: null pointer%s", "");
+    const int c_tiles = bwd_row_tiles(g->C), n = c_tiles * (g->O / 16) * 9 * 2 * 128;
+    hipLaunchKernelGGL(k_cut_weights_bwd_data, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, w_base, w_basis, (__bf16*)wcd, g->C, g->O, c_tiles);
+    return hipGetLastError() == hipSuccess ? 0 : kan_fail_msg("kan_split_pack_weights_bwd_data: launch failed%s", "");
+}
+
+int kan_conv_bwd_data_split(const float* dz, const float* x, const void* wcd, float* dx, const KanGeom* g, const KanBasis* b, void* stream) {
+    const char* why = split_bwd_reject(g, b);
+    if (why) return kan_fail_msg("%s", why);
+    if (!dz || !x || !wcd || !dx) return kan_fail_msg("kan_conv_bwd_data_split: null pointer%s", "");
+    if (kan_raise_lds_limit((const void*)k_split_bwd_data<8>, lds_bytes_bwd<8>()) || kan_raise_lds_limit((const void*)k_split_bwd_data<16>, lds_bytes_bwd<16>()))
+        return kan_fail_msg("kan_conv_bwd_data_split: cannot reserve %s of LDS", "109 KB");
+    const DevBasis db = dev_basis(b);
+    const int c_tiles = bwd_row_tiles(g->C);
+    if (g->H == 8)
+        hipLaunchKernelGGL(k_split_bwd_data<8>, dim3((unsigned)((g->B / 2) * c_tiles)), dim3(512), lds_bytes_bwd<8>(), (hipStream_t)stream, dz, x, (const __bf16*)wcd, dx, db, g->C, g->O, c_tiles);
+    else
+        hipLaunchKernelGGL(k_split_bwd_data<16>, dim3((unsigned)(g->B * 2 * c_tiles)), dim3(512), lds_bytes_bwd<16>(), (hipStream_t)stream, dz, x, (const __bf16*)wcd, dx, db, g->C, g->O, c_tiles);
+    return hipGetLastError() == hipSuccess ? 0 : kan_fail_msg("kan_conv_bwd_data_split: launch failed%s", "");
 }
 
 }  // extern "C"

@@ -378,6 +378,62 @@ def _split_stage(spec: ConvSpec, x: torch.Tensor, w_base, w_basis):
     return z.unsqueeze(0)
 
 
+_SPLIT_BWD_DATA = False
+_SPLIT_BWD_CACHE: "OrderedDict" = OrderedDict()         # (weight addresses) -> (version stamps, epoch, cut weights of the bwd-data launch)
+
+
+@contextlib.contextmanager
+def split_precision_backward_data():
+    """OPT-IN, training: a conv autograd Function whose FORWARD runs inside with grad mode on (the decision is taken there, as autocast takes it), whose
+    input needs a gradient and whose stage is in scope of `kan_conv_bwd_data_split` (one group, base branch, no second input, no phases, no plane
+    windows, `kan_split_supported`: default B-spline spec on 8x8 / 16x16 planes, 3x3 / stride 1 / pad 1, C % 8 == 0, O % 128 == 0, even batch on 8x8)
+    computes its INPUT gradient in split precision (3 x bf16 pieces, six bf16 MFMA products).  The forward, the weight gradient and every other layer
+    stay on exact fp32 MFMA.  Never on by default."""
+    global _SPLIT_BWD_DATA
+    prev, _SPLIT_BWD_DATA = _SPLIT_BWD_DATA, True
+    try:
+        yield
+    finally:
+        _SPLIT_BWD_DATA = prev
+
+
+def _split_bwd_weights(spec: ConvSpec, x: torch.Tensor, xn, phases, w_base, w_basis, need_dgrad: bool):
+    """The cut weights `wcd` a backward hands to kan_conv_bwd_data_split, or None: outside `split_precision_backward_data`, without an input gradient to
+    compute (grad mode off, or an input that needs none), or for a stage out of scope.  Cached per weight pair: ONE buffer, re-cut in place when a
+    version stamp moved and, under `always_pack` (a recorded step), unconditionally -- a replay cuts the weights as they are then, into the address it
+    was recorded with."""
+    if not (_SPLIT_BWD_DATA and need_dgrad):            # need_dgrad comes from ctx.needs_input_grad: False whenever the caller's grad mode is off
+        return None
+    if spec.groups != 1 or not spec.has_base or xn is not None or phases is not None or x.dim() != 4 or spec.first or spec.w_layout == W_IOD:
+        return None
+    wb, ws = w_base[0], w_basis[0]
+    geom, basis, _ = _plan_cached(*_plan_key(spec, x.shape, ws.shape[0]))
+    nbytes = L.load().kan_split_bwd_data_weight_bytes(C.byref(geom), C.byref(basis))
+    if not nbytes:
+        return None
+    key = (wb.data_ptr(), ws.data_ptr(), x.device.index)
+    stamps = (_owner(wb)._version, _owner(ws)._version, _EPOCH)
+    ent = _SPLIT_BWD_CACHE.get(key)
+    wcd = ent[1] if ent is not None and ent[1].numel() == nbytes else None
+    if wcd is None or ent[0] != stamps or _ALWAYS_PACK:
+        wcd = _cut_weights_bwd_data(geom, basis, wb, ws, wcd)
+    _SPLIT_BWD_CACHE[key] = (stamps, wcd)
+    _SPLIT_BWD_CACHE.move_to_end(key)
+    while len(_SPLIT_BWD_CACHE) > 16:
+        _SPLIT_BWD_CACHE.popitem(last=False)
+    return wcd
+
+
+def _cut_weights_bwd_data(geom, basis, w_base: torch.Tensor, w_basis: torch.Tensor, wcd: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """kan_split_pack_weights_bwd_data into `wcd` (allocated when None)."""
+    lib = L.load()
+    if wcd is None:
+        wcd = torch.empty(lib.kan_split_bwd_data_weight_bytes(C.byref(geom), C.byref(basis)), device=w_base.device, dtype=torch.uint8)
+    L.check(lib.kan_split_pack_weights_bwd_data(_ptr(w_base), _ptr(w_basis), C.c_void_p(wcd.data_ptr()), C.byref(geom), C.byref(basis), _stream(w_base)),
+            "kan_split_pack_weights_bwd_data")
+    return wcd
+
+
 def weights_changed() -> None:
     """Tell the packed-weight cache that weights may have been written through a path the version counters cannot see (`.data` ops,
     `dist.broadcast(p.data)`, raw-pointer kernels): every layer fingerprints its weights on its next call."""
@@ -539,9 +595,10 @@ def _sink_for(wid, shape, device):
     return t
 
 
-def _conv_backward(spec: ConvSpec, x, xn, packed, dz, need_x: bool, need_xn: bool, need_w: bool, phases=None, mode: int = 0, wids=None, dparams=None):
+def _conv_backward(spec: ConvSpec, x, xn, packed, dz, need_x: bool, need_xn: bool, need_w: bool, phases=None, mode: int = 0, wids=None, dparams=None, wcd=None):
     """dz: [B,O,Ho,Wo] contiguous.  Returns (dx, dxn, dw_base list, dw_basis list) -- per-group views of stacked gradients.
-    `wids`: ids of the (base, basis) weight Parameters of a single-group layer, for GRAD_SINKS."""
+    `wids`: ids of the (base, basis) weight Parameters of a single-group layer, for GRAD_SINKS.
+    `wcd`: cut weights handed over by a forward under `split_precision_backward_data`: dx comes from kan_conv_bwd_data_split iff it is given."""
     lib = L.load()
     B, Ct, H, W = x.shape
     G = spec.groups
@@ -583,7 +640,9 @@ def _conv_backward(spec: ConvSpec, x, xn, packed, dz, need_x: bool, need_xn: boo
             if spec.has_base:
                 dw_base = list(dwb.unbind(0))
     dx = dxn = None
-    if need_x or need_xn:
+    if need_x and wcd is not None:                       # opt-in split-precision input gradient: one slab, no reduce
+        dx, _ = kan_conv_bwd_data_split(spec, x, dz, None, None, wcd)
+    elif need_x or need_xn:
         S = plan.bwd_data_splits
         separate = xn is not None
         dxs = torch.empty((S, B, Ct, H, W), device=x.device, dtype=torch.float32)
@@ -658,16 +717,17 @@ class _KanConv(torch.autograd.Function):
         with torch.cuda.device(x.device):
             z, (wd, x_pm), geom, _, plan = _conv_forward(spec, x, xn, w_base, w_basis, need_dgrad, phases)
             z = _sum_slabs(z, geom.B, z.shape[2], geom.Ho * geom.Wo)
+            wcd = _split_bwd_weights(spec, x, xn, phases, w_base, w_basis, need_dgrad)
         ctx.spec = spec
         # the basis weights are kept only for the parameter gradient (their version counters are then checked in the backward)
         kept_w = {f"w_basis{g}": w for g, w in enumerate(w_basis)} if phases is not None else {}
-        _save(ctx, x=x, xn=xn, phases=phases, wd=wd, x_pm=x_pm, **kept_w)
+        _save(ctx, x=x, xn=xn, phases=phases, wd=wd, x_pm=x_pm, wcd=wcd, **kept_w)
         return z
 
     @staticmethod
     def backward(ctx, dz):
         spec, G = ctx.spec, ctx.spec.groups
-        x, xn, phases, wd, x_pm, *w_basis = _saved(ctx, "x", "xn", "phases", "wd", "x_pm", *(f"w_basis{g}" for g in range(G)))
+        x, xn, phases, wd, x_pm, wcd, *w_basis = _saved(ctx, "x", "xn", "phases", "wd", "x_pm", "wcd", *(f"w_basis{g}" for g in range(G)))
         packed = (wd, x_pm)
         need_x, need_xn = ctx.needs_input_grad[1], xn is not None and ctx.needs_input_grad[2]
         need_p, need_w = ctx.needs_input_grad[3], any(ctx.needs_input_grad[4:])
@@ -680,7 +740,7 @@ class _KanConv(torch.autograd.Function):
             dpar = None
             if in_epilogue:                                    # ReLU-KAN: [Cg, 2, n] directly; Gram: 64 slot rows of partial sums
                 dpar = torch.zeros_like(phases) if spec.kind == L.BASIS_RELU else phases.new_zeros((64, spec.n_basis))
-            dx, dxn, dwb, dws = _conv_backward(spec, x, xn, packed, dz, need_x, need_xn, need_w, phases, dparams=dpar)
+            dx, dxn, dwb, dws = _conv_backward(spec, x, xn, packed, dz, need_x, need_xn, need_w, phases, dparams=dpar, wcd=wcd)
             if in_epilogue:
                 dph = dpar if spec.kind == L.BASIS_RELU else dpar.sum(dim=0)
             if need_p and not in_epilogue:
@@ -837,24 +897,25 @@ class _KanConvInPrelu(torch.autograd.Function):
                 plan = _plan_cached(*_plan_key(spec, x.shape, zs.shape[2] // G))[2]
             else:
                 zs, (wd, x_pm), _, _, plan = _conv_forward(spec, x, None, w_base, w_basis, bool(ctx.needs_input_grad[7]))
+            wcd = _split_bwd_weights(spec, x, None, None, w_base, w_basis, bool(ctx.needs_input_grad[7]))
             # all groups in one launch: per-channel gamma/beta concatenated, one PReLU slope per Og channels
             gamma, beta, slope = _cat(gammas), _cat(betas), _cat(prelus)
             y, z, mean, rstd, pidx = _norm_fwd(zs, plan.fwd_slab_elems, gamma, beta, slope, eps, G, pool, bn=bn)
         ctx.spec, ctx.pool, ctx.bn = spec, pool, bn
         ctx.wids = (id(w_base[0]) if spec.has_base else None, id(w_basis[0])) if G == 1 else None
-        _save(ctx, x=x, z=z, mean=mean, rstd=rstd, wd=wd, x_pm=x_pm, gamma=gamma, beta=beta, slope=slope, pidx=pidx)
+        _save(ctx, x=x, z=z, mean=mean, rstd=rstd, wd=wd, x_pm=x_pm, gamma=gamma, beta=beta, slope=slope, pidx=pidx, wcd=wcd)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         spec, G = ctx.spec, ctx.spec.groups
-        x, z, mean, rstd, wd, x_pm, gamma, beta, slope, pidx = _saved(ctx, "x", "z", "mean", "rstd", "wd", "x_pm", "gamma", "beta", "slope", "pidx")
+        x, z, mean, rstd, wd, x_pm, gamma, beta, slope, pidx, wcd = _saved(ctx, "x", "z", "mean", "rstd", "wd", "x_pm", "gamma", "beta", "slope", "pidx", "wcd")
         with torch.cuda.device(x.device):
             dz, dgam, dbet, dpre = _norm_bwd(dy, z, mean, rstd, gamma, beta, slope, pidx, G, ctx.pool, bn=ctx.bn)
             nw = G * (2 if spec.has_base else 1)
             need_x = ctx.needs_input_grad[7]
             need_w = any(ctx.needs_input_grad[8:8 + nw])
-            dx, _, dwb, dws = _conv_backward(spec, x, None, (wd, x_pm), dz, need_x, False, need_w, wids=ctx.wids)
+            dx, _, dwb, dws = _conv_backward(spec, x, None, (wd, x_pm), dz, need_x, False, need_w, wids=ctx.wids, wcd=wcd)
         grads = _flat_grads(spec, dwb, dws)
         if gamma is not None:
             grads += tuple(dgam.view(G, -1).unbind(0)) + tuple(dbet.view(G, -1).unbind(0))
@@ -1041,6 +1102,34 @@ def kan_conv_fwd_split(spec: ConvSpec, x: torch.Tensor, w_base: torch.Tensor, w_
         z = torch.empty((B, Ot, H, W), device=x.device, dtype=torch.float32)
         L.check(lib.kan_conv_fwd_split(_ptr(x), C.c_void_p(wc.data_ptr()), _ptr(z), C.byref(geom), C.byref(basis), _stream(x)), "kan_conv_fwd_split")
     return z, wc
+
+
+def kan_conv_bwd_data_split(spec: ConvSpec, x: torch.Tensor, dz: torch.Tensor, w_base: Optional[torch.Tensor], w_basis: Optional[torch.Tensor],
+                            wcd: Optional[torch.Tensor] = None):
+    """OPT-IN split-precision input gradient of the conv stage (no autograd; kanconv.h `kan_conv_bwd_data_split`): what the backward of `kan_conv` returns for
+    x, through 3 x bf16 pieces of dz and the weights and six bf16 MFMA products per k-block; the derivative planes are the exact kernel's.  Scope: that of
+    `kan_conv_fwd_split` (raises KanConvError otherwise).  Returns (dx, wcd): pass `wcd` back while the weights are unchanged to skip the cut (the
+    weights may then be None)."""
+    lib = L.load()
+    x, dz = _require(x, "x"), _require(dz, "dz")
+    if x.dim() != 4 or dz.dim() != 4:
+        raise L.KanConvError(f"split-precision bwd-data: NCHW x and dz, got {tuple(x.shape)} and {tuple(dz.shape)}")
+    Ot = dz.shape[1]
+    geom, basis, _ = _plan_cached(*_plan_key(spec, x.shape, Ot))
+    nbytes = lib.kan_split_bwd_data_weight_bytes(C.byref(geom), C.byref(basis)) if spec.groups == 1 and spec.has_base and not spec.first else 0
+    if not nbytes:
+        raise L.KanConvError("split-precision bwd-data: default B-spline spec (grid 5, order 3, SiLU base branch), 8x8 or 16x16 planes, 3x3 / stride 1 / pad 1, one group, C % 8 == 0, "
+                             "O % 128 == 0, even batch only")
+    if tuple(dz.shape) != (geom.B, Ot, geom.Ho, geom.Wo):
+        raise L.KanConvError(f"split-precision bwd-data: dz {tuple(dz.shape)} != {(geom.B, Ot, geom.Ho, geom.Wo)}")
+    with torch.cuda.device(x.device):
+        if wcd is None:
+            wcd = _cut_weights_bwd_data(geom, basis, _require(w_base, "w_base"), _require(w_basis, "w_basis"))
+        elif wcd.numel() != nbytes or wcd.dtype != torch.uint8 or wcd.device != x.device:
+            raise L.KanConvError(f"split-precision bwd-data: wcd must hold {nbytes} bytes on {x.device}")
+        dx = torch.empty_like(x)
+        L.check(lib.kan_conv_bwd_data_split(_ptr(dz), _ptr(x), C.c_void_p(wcd.data_ptr()), _ptr(dx), C.byref(geom), C.byref(basis), _stream(x)), "kan_conv_bwd_data_split")
+    return dx, wcd
 
 
 def instance_norm(x: torch.Tensor, gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None, eps: float = 1e-5):

@@ -375,6 +375,20 @@ long long kan_split_weight_bytes(const KanGeom* geom, const KanBasis* basis);
 int kan_split_pack_weights(const float* w_base, const float* w_basis, void* wc, const KanGeom* geom, const KanBasis* basis, void* stream);
 int kan_conv_fwd_split(const float* x, const void* wc, float* z, const KanGeom* geom, const KanBasis* basis, void* stream);
 
+/* OPT-IN split-precision input gradient: NOT reached from kan_conv_bwd_data, never the default.  The arithmetic and the scope of the
+ * split forward above (kan_split_supported serves both directions): dz and the weights are cut into three bf16 pieces, six bf16 MFMA products per 16-deep
+ * block, fp32 accumulation; the derivative planes of the epilogue are the exact kernel's.  Computes what kan_conv_bwd_data computes for such a layer -- the
+ * autograd of kan_layers.py:199-200, 203-239 w.r.t. the layer input -- into ONE slab dx[B][C][H][W], every element written exactly once (no atomics, no
+ * slab reduce).
+ *   kan_split_bwd_data_weight_bytes   size of the cut-weight buffer `wcd` (0 if out of scope):
+ *                                     wcd[ceil(C / 14) row tiles][(O / 16) * 9 steps][3 pieces][2 k-halves][128 rows][8 bf16 of consecutive o]
+ *   kan_split_pack_weights_bwd_data   reference-layout weights (as kan_split_pack_weights takes them: kan_layers.py:159-166, 170-177) -> wcd; once per weight update
+ *   kan_conv_bwd_data_split           dx = sum_p plane_p'(x) * dgrad(dz, W_p)
+ * Out-of-scope geometry and null pointers are refused by host arithmetic before any launch. */
+long long kan_split_bwd_data_weight_bytes(const KanGeom* geom, const KanBasis* basis);
+int kan_split_pack_weights_bwd_data(const float* w_base, const float* w_basis, void* wcd, const KanGeom* geom, const KanBasis* basis, void* stream);
+int kan_conv_bwd_data_split(const float* dz, const float* x, const void* wcd, float* dx, const KanGeom* geom, const KanBasis* basis, void* stream);
+
 /* One AdamW step over a flat fp32 block of n elements, in place (p, m = exp_avg, v = exp_avg_sq; g is read only and
  * multiplied by grad_scale first).  Replaces the per-tensor update loop of torch.optim.AdamW as the reference builds it
  * (generic_train.py:24 `optim.AdamW(model.parameters(), lr, weight_decay)`, stepped once per batch: evaluations.py train()),
