@@ -104,6 +104,8 @@ SIGNATURES = {
     "kan_split_bwd_data_weight_bytes": (_LL, [C.POINTER(KanGeom), C.POINTER(KanBasis)]),
     "kan_split_pack_weights_bwd_data": (_I, [_P, _P, _P, C.POINTER(KanGeom), C.POINTER(KanBasis), _P]),
     "kan_conv_bwd_data_split": (_I, [_P, _P, _P, _P, C.POINTER(KanGeom), C.POINTER(KanBasis), _P]),
+    "kan_split_bwd_weight_workspace_bytes": (_LL, [C.POINTER(KanGeom), C.POINTER(KanBasis)]),
+    "kan_conv_bwd_weight_split": (_I, [_P, _P, _P, _P, _P, C.POINTER(KanGeom), C.POINTER(KanBasis), _P]),
     "kan_wav_fwd": (_I, [_P, _P, _P, _P, _P, C.POINTER(KanWavGeom), _P]),
     "kan_wav_bwd_input": (_I, [_P, _P, _P, _P, _P, _P, C.POINTER(KanWavGeom), _P]),
     "kan_wav_param_workspace": (_LL, [C.POINTER(KanWavGeom)]),

@@ -1,4 +1,4 @@
-// libkanconv, OPT-IN split-precision forward (round 3) and input gradient (k_split_bwd_data, further down).  NOT on any default path: `dtype` f32 stays exact; this mode is reached only
+// libkanconv, OPT-IN split-precision forward (round 3), input gradient (k_split_bwd_data, further down) and weight gradient (k_split_bwd_weight, after it).  NOT on any default path: `dtype` f32 stays exact; this mode is reached only
 // through its own entry points (kan_split_*), carries its own tolerance in the tests and is reported under `other_workloads` by bench.py.
 //
 // Every fp32 operand (expanded plane value, weight) is cut into three bf16 pieces hi + mid + lo (24 mantissa bits); each 16-deep k-block runs six
@@ -566,6 +566,241 @@ const char* split_bwd_reject(const KanGeom* g, const KanBasis* b) {
     return nullptr;
 }
 
+// ---- the weight gradient (k_split_bwd_weight): what kan_conv_bwd_weight + kan_unpack_wgrad compute for a layer in scope,
+//   dW[o][c][plane][tap] = sum_{b,h,w} dz[b,o,h,w] * plane(x[b,c,h+r-1,w+t-1]),   tap = 3 r + t,
+// straight into the reference layouts.  The GEMM depth is now the pixel axis (b, h, w); a lane of the 32x32x16 MFMA wants 8 depth-consecutive bf16 values
+// in one 16-byte fragment, and a tap's column shift of one pixel would misalign a pixel-contiguous chunk by 2 bytes.  Way out taken here: IMAGES are the
+// inner depth index.  A 16-byte chunk holds the 8 images of an octet at the same (channel, plane, cell), so every tap is a whole-cell shift of one
+// zero-bordered halo tile, read with ds_read_b128 exactly as the forward reads its tile; nothing is transposed, EXEC stays full, and a batch tail is just
+// zero images.  (The hardware-transposed reads, ds_read_b64_tr_b16 on a cell-major tile, would keep the forward's tile but need two reads per fragment under
+// their alignment rules and give nothing back: the expansion is per (image, pixel) either way.)  The price is paid at small batches only: an octet with
+// fewer than 8 images multiplies zeros.
+//   tile    128 outputs x 96 columns per workgroup: the 81 (plane, tap) columns of ONE input channel (column n = 9 plane + tap: the reference order of both
+//           gradient tensors) + 15 padding columns that are computed and never stored.  512 threads = 8 waves, two per SIMD: wave = (32-output block,
+//           depth half), each 32 outputs x 96 columns (3 blocks) over its half of every block's steps -- one wave's operand reads hide behind the other's
+//           MFMAs; the halves are added through LDS at the end, in a fixed order;
+//   depth   units of 64 pixels x 8 images: an octet of whole 8x8 images, or four image rows of an octet of 16x16 images.  A step of 16 = two neighbouring
+//           pixels of a row (the k-halves) x 8 images; a unit is 8 blocks of 8 pixels (4 steps).  The units of a layer are dealt to KS workgroups per
+//           (channel, output tile) in contiguous runs; every workgroup stores its 128 x 81 partial sums once and k_wgrad_reduce adds the KS partials in
+//           ascending order into dw_base / dw_basis (every element written once, no atomics: two runs are bit-identical);
+//   B side  per unit all threads expand the channel's values (stage_unit, the exact kernels' own plane values: SiLU + 8 B-spline planes), cut image PAIRS with split_pair and
+//           write 4 bytes per (plane, piece) into the halo tile [piece][cell][plane][8 images]; rows outside the image and images past the batch are
+//           written as zeros, the left / right border cells are zeroed once.  The x values of a unit are fetched one unit ahead.  The expanded tensor
+//           never exists in HBM;
+//   A side  dz is cut once per call (k_cut_dz) into dzc[octet][pixel][piece][o][8 images] in the caller's workspace and streamed by 16-byte LDS-DMA, one
+//           8-pixel block (48 KB) ahead of the block being contracted (across units too), two buffers, s_waitcnt vmcnt(0) + barrier per block (36 MFMAs per wave);
+//   loop    18 MFMAs per step and wave (3 column blocks x the six products, smallest first), operands of 3 + 9 ds_read_b128, through the MFMA builtin: the
+//           compiler's schedule (it sinks the block's barrier between a wave's two steps, so the two waves of a SIMD drift half a block apart) measured
+//           1.42 - 1.48 x the exact kernels; pinning MFMAs and barrier in source order with volatile asm measured 7 % slower on all three shapes.
+// First version: one role for every wave, not the producer / MFMA wave split, the counted vmcnt + bare s_barrier ring and the explicit-ISA step of the two
+// kernels above.  The producer split itself was NOT tried here: the only alternative measured is the pinned order above.  The rate of issued bf16 products
+// (~1.3 PFLOP/s at 256 -> 256) is in the range of the forward's; what this kernel gives away against the 1.7 - 1.9 x of the other two launches is the 15
+// padding columns of 96, the expansion and the dz copy wait sitting on every wave's critical path, and the pre-pass and reduce launches.
+constexpr int WG_NB = 3, WG_COLS = NP * 9;                           // column blocks of 32; live columns
+constexpr int WG_PXB = 3 * 128 * 16, WG_DZBUF = 8 * WG_PXB;          // bytes of one pixel / one 8-pixel block of a 128-output tile of dzc
+template <int PW> struct WgGeo {
+    static constexpr int TR = PW == 8 ? 8 : 4, UPO = PW / TR;        // image rows per unit; units per image octet
+    static constexpr int PITCH = PW + 2, CELLS = (TR + 2) * PITCH, PIECEB = CELLS * CELLC * 16, EB = 3 * PIECEB, HWP = PW * PW;
+    static constexpr int NROWS = PW == 8 ? TR : TR + 2, HR0 = PW == 8 ? 1 : 0;     // halo rows a unit writes (8x8: the outer two are always outside the image)
+};
+template <int PW> constexpr int lds_bytes_wg() { return WgGeo<PW>::EB + 2 * WG_DZBUF + 64; }
+
+inline int wg_octets(const KanGeom* g) { return (g->B + 7) / 8; }
+inline int wg_units(const KanGeom* g) { return wg_octets(g) * (g->H == 8 ? 1 : 4); }
+// depth splits: enough workgroups for two rounds of 256 CUs, at most 32 and at most one per unit -- a function of the geometry alone
+inline int wg_ksplit(const KanGeom* g) {
+    const int tiles = g->C * (g->O / 128), units = wg_units(g);
+    int ks = (512 + tiles - 1) / tiles;
+    ks = ks > 32 ? 32 : ks;
+    return ks > units ? units : ks;
+}
+inline long long wg_dz_bytes(const KanGeom* g) { return (long long)wg_octets(g) * g->H * g->W * 3 * g->O * 16; }
+inline long long wg_part_bytes(const KanGeom* g) { return (long long)wg_ksplit(g) * g->O * g->C * WG_COLS * 4; }
+
+const char* split_bww_reject(const KanGeom* g, const KanBasis* b) {
+    if (const char* why = split_reject(g, b)) return why;
+    if (wg_dz_bytes(g) >= (1ll << 31)) return "split-precision bwd-weight: cut dz must stay under 2 GiB";
+    return nullptr;
+}
+
+// ---- dz [B][O][HW] -> dzc[octet][pixel][piece][o][8 bf16: images 8 octet .. 8 octet + 7, zero past the batch].  A workgroup cuts a tile of 16 outputs x 16
+// pixels of one octet: it reads pixel-fastest (64 contiguous bytes per output and image), turns the tile round in LDS (pitch 17 chunks: conflict-free both
+// ways) and stores output-fastest (256 contiguous bytes per pixel and piece)
+__global__ __launch_bounds__(256) void k_cut_dz(const float* __restrict__ dz, __bf16* __restrict__ dzc, int NB, int NO, int HW) {
+    __shared__ uint4 sT[3 * 16 * 17];
+    const int t = threadIdx.x, o_tiles = NO / 16, p_tiles = HW / 16;
+    const int o0 = (blockIdx.x % o_tiles) * 16, px0 = ((blockIdx.x / o_tiles) % p_tiles) * 16, q = blockIdx.x / (o_tiles * p_tiles);
+    {
+        const int ol = t >> 4, pl = t & 15;
+        float v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { const int b = q * 8 + i; v[i] = b < NB ? dz[((size_t)b * NO + o0 + ol) * HW + px0 + pl] : 0.f; }
+        uint4 h, md, l;
+        split_pair(v[0], v[1], h.x, md.x, l.x); split_pair(v[2], v[3], h.y, md.y, l.y);
+        split_pair(v[4], v[5], h.z, md.z, l.z); split_pair(v[6], v[7], h.w, md.w, l.w);
+        sT[pl * 17 + ol] = h; sT[272 + pl * 17 + ol] = md; sT[544 + pl * 17 + ol] = l;
+    }
+    __syncthreads();
+    const int pl = t >> 4, ol = t & 15;
+    uint4* dst = (uint4*)dzc + ((size_t)(q * HW + px0 + pl) * 3) * NO + o0 + ol;
+#pragma unroll
+    for (int pc = 0; pc < 3; ++pc) dst[(size_t)pc * NO] = sT[pc * 272 + pl * 17 + ol];
+}
+
+template <int PW>
+__global__ __launch_bounds__(512, 1) void k_split_bwd_weight(const float* __restrict__ x, const __bf16* __restrict__ dzc, float* __restrict__ part, DevBasis bs,
+                                                             int NB, int NC, int NO, int o_tiles, int KS, int dzc_bytes) {
+    using Gm = WgGeo<PW>;
+    constexpr int PITCH = Gm::PITCH, PIECEB = Gm::PIECEB, EB = Gm::EB, HW = Gm::HWP, TR = Gm::TR, UPO = Gm::UPO, NCELL = Gm::NROWS * PW;
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    unsigned char* sE = smem;                                              // halo tile of the expanded channel
+    unsigned char* sD = smem + EB;                                         // two 8-pixel blocks of cut dz
+    float* sTab = (float*)(smem + EB + 2 * WG_DZBUF);
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), kh = lane >> 5, m = lane & 31;
+    const int wo = wave & 3, dh = wave >> 2;                               // 32-output block; depth half: steps 2 dh, 2 dh + 1 of every block
+    const int c = blockIdx.x % NC, ot = (blockIdx.x / NC) % o_tiles, ks = blockIdx.x / (NC * o_tiles);
+    const int units = ((NB + 7) / 8) * UPO, u0 = (int)((long long)ks * units / KS), u1 = (int)((long long)(ks + 1) * units / KS);
+
+    for (int i = tid; i < EB / 16; i += 512) ((uint4*)sE)[i] = uint4{0u, 0u, 0u, 0u};
+    if (tid < 16) sTab[tid] = bs.tab[tid];
+
+    // dz stream: 6 chunks of 16 B per thread and block; chunk (pixel, piece, o) of the block at ((pixel * 3 + piece) * 128 + o) * 16
+    const __amdgpu_buffer_rsrc_t d_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(dzc), 0, dzc_bytes, 0x00020000);
+    const int voff0 = ((tid >> 7) * NO + ot * 128 + (tid & 127)) * 16;
+    auto issue = [&](int q, int px0, int buf) {
+        unsigned char* dst = sD + buf * WG_DZBUF + wave * 1024;
+        const int so = __builtin_amdgcn_readfirstlane((q * HW + px0) * 3 * NO * 16);
+#pragma unroll
+        for (int j = 0; j < 6; ++j)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(d_rs, (__attribute__((address_space(3))) void*)(dst + j * 8192), 16, voff0 + j * 4 * NO * 16, so, 0, 0);
+    };
+    // first pixel of block blk of the unit whose first image row is r0
+    auto block_px = [&](int r0, int blk) { return PW == 8 ? blk * 8 : (r0 + (blk >> 1)) * 16 + (blk & 1) * 8; };
+
+    // operand addresses (bytes): A = dz rows of this wave, B = the lane's column (plane, tap) of each block, both at the k-half's pixel
+    const unsigned aLane = (unsigned)(EB + (4 * dh + kh) * WG_PXB + (wo * 32 + m) * 16);
+    unsigned bLane[WG_NB];
+#pragma unroll
+    for (int j = 0; j < WG_NB; ++j) {
+        const int n = j * 32 + m, p = n < WG_COLS ? n / 9 : 0, tap = n < WG_COLS ? n % 9 : 4;      // padding columns: centre tap of plane 0 (never stored)
+        bLane[j] = (unsigned)((((tap / 3 - 1) * PITCH + (tap % 3 - 1) + 4 * dh + kh) * CELLC + p) * 16);
+    }
+
+    f32x16 acc[WG_NB];
+#pragma unroll
+    for (int j = 0; j < WG_NB; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+
+    // expansion item of this thread: (cell, image pair); NCELL * 4 <= 512 items, one per thread.  Its two x values are fetched one unit ahead.
+    static_assert(NCELL * 4 <= 512, "one expansion item per thread");
+    const bool has_item = tid < NCELL * 4;
+    const int pair = tid / NCELL, cl = tid % NCELL, hr = Gm::HR0 + cl / PW, col = cl % PW;
+    auto fetch = [&](int u, float (&xr)[2]) {
+        const int q = u / UPO, row = (u % UPO) * TR + hr - 1;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int b = q * 8 + pair * 2 + i;
+            xr[i] = (has_item && row >= 0 && row < PW && b < NB) ? x[((size_t)b * NC + c) * HW + row * PW + col] : 0.f;
+        }
+    };
+    float xr[2];
+    fetch(u0, xr);
+    __syncthreads();
+    issue(u0 / UPO, block_px((u0 % UPO) * TR, 0), 0);
+#pragma unroll 1
+    for (int u = u0; u < u1; ++u) {
+        const int q = u / UPO, r0 = (u % UPO) * TR;
+        // (every wave is past the barrier of the previous unit's last block: the tile and dz buffer 1 are free; block 0 of this unit is on its way to buffer 0)
+        if (has_item) {
+            float* colS = (float*)(sD + WG_DZBUF) + tid;                   // this thread's stage_unit column (+ dump slot), pitch 512, in dz buffer 1
+            const int row = r0 + hr - 1;
+            float v[2][NP];
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                const bool inb = row >= 0 && row < PW && q * 8 + pair * 2 + i < NB;      // outside: all nine planes zero
+                stage_unit<KAN_BASIS_BSPLINE, FAST_BSPLINE_SILU>(bs, sTab, inb, xr[i], xr[i], colS, 512, colS + NP * 512);
+#pragma unroll
+                for (int p = 0; p < NP; ++p) v[i][p] = colS[p * 512];
+            }
+            unsigned char* d = sE + ((hr * PITCH + col + 1) * CELLC) * 16 + pair * 4;
+#pragma unroll
+            for (int p = 0; p < NP; ++p) {
+                unsigned h, md, l;
+                split_pair(v[0][p], v[1][p], h, md, l);
+                *(unsigned*)(d + p * 16) = h; *(unsigned*)(d + PIECEB + p * 16) = md; *(unsigned*)(d + 2 * PIECEB + p * 16) = l;
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        const bool more = u + 1 < u1;
+        if (more) fetch(u + 1, xr);                                         // lands behind block 0's MFMAs
+#pragma unroll 1
+        for (int blk = 0; blk < 8; ++blk) {
+            if (blk + 1 < 8) issue(q, block_px(r0, blk + 1), (blk + 1) & 1);
+            else if (more) issue((u + 1) / UPO, block_px(((u + 1) % UPO) * TR, 0), 0);      // the next unit's block 0: buffer 0 is free since block 6's barrier
+            const int lrow = PW == 8 ? blk : (blk >> 1), col0 = PW == 8 ? 0 : (blk & 1) * 8;
+            const unsigned char* pa = smem + aLane + (blk & 1) * WG_DZBUF;
+            const unsigned char* pb = sE + ((lrow + 1) * PITCH + col0 + 1) * CELLC * 16;
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                bf16x8 a[3], b[WG_NB][3];
+#pragma unroll
+                for (int pc = 0; pc < 3; ++pc) {
+                    a[pc] = *(const bf16x8*)(pa + s * 2 * WG_PXB + pc * 2048);
+#pragma unroll
+                    for (int j = 0; j < WG_NB; ++j) b[j][pc] = *(const bf16x8*)(pb + s * 2 * CELLC * 16 + bLane[j] + pc * PIECEB);
+                }
+                // smallest products first: lo*hi, hi*lo, mid*mid, mid*hi, hi*mid, hi*hi (A = dz, B = plane value)
+#pragma unroll
+                for (int j = 0; j < WG_NB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[j][0], acc[j], 0, 0, 0);
+#pragma unroll
+                for (int j = 0; j < WG_NB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[j][2], acc[j], 0, 0, 0);
+#pragma unroll
+                for (int j = 0; j < WG_NB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[j][1], acc[j], 0, 0, 0);
+#pragma unroll
+                for (int j = 0; j < WG_NB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[j][0], acc[j], 0, 0, 0);
+#pragma unroll
+                for (int j = 0; j < WG_NB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[j][1], acc[j], 0, 0, 0);
+#pragma unroll
+                for (int j = 0; j < WG_NB; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[j][0], acc[j], 0, 0, 0);
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+        }
+    }
+    // ---- the two depth halves meet in LDS (the dz buffers are free after the last barrier), added in a fixed order; then the partial sums:
+    // part[ks][o][c][n], live columns only
+    float* sR = (float*)sD;
+    if (dh) {
+#pragma unroll
+        for (int j = 0; j < WG_NB; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) sR[((wo * WG_NB + j) * 16 + r) * 64 + lane] = acc[j][r];
+    }
+    __syncthreads();
+    if (dh) return;
+    float* po = part + ((size_t)ks * NO + ot * 128 + wo * 32) * NC * WG_COLS + (size_t)c * WG_COLS;
+#pragma unroll
+    for (int j = 0; j < WG_NB; ++j) {
+        const int n = j * 32 + m;
+        if (n >= WG_COLS) continue;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) po[(size_t)mfma_row(r, lane) * NC * WG_COLS + n] = acc[j][r] + sR[((wo * WG_NB + j) * 16 + r) * 64 + lane];
+    }
+}
+
+// ---- part[KS][O][C][81] -> dw_base[O][C][9], dw_basis[O][C * 8][9], the KS partials added in ascending order
+__global__ void k_wgrad_reduce(const float* __restrict__ part, float* __restrict__ dwb, float* __restrict__ dws, int n_oc, int KS) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;             // (o, c, column)
+    if (idx >= n_oc * WG_COLS) return;
+    float s = part[idx];
+    for (int k = 1; k < KS; ++k) s += part[(size_t)k * n_oc * WG_COLS + idx];
+    const int oc = idx / WG_COLS, n = idx % WG_COLS;
+    if (n < 9) dwb[(size_t)oc * 9 + n] = s;
+    else dws[(size_t)oc * 72 + (n - 9)] = s;
+}
+
 }  // namespace
 
 extern "C" {
@@ -628,6 +863,33 @@ int kan_conv_bwd_data_split(const float* dz, const float* x, const void* wcd, fl
     else
         hipLaunchKernelGGL(k_split_bwd_data<16>, dim3((unsigned)(g->B * 2 * c_tiles)), dim3(512), lds_bytes_bwd<16>(), (hipStream_t)stream, dz, x, (const __bf16*)wcd, dx, db, g->C, g->O, c_tiles);
     return hipGetLastError() == hipSuccess ? 0 : kan_fail_msg("kan_conv_bwd_data_split: launch failed%s", "");
+}
+
+long long kan_split_bwd_weight_workspace_bytes(const KanGeom* g, const KanBasis* b) {
+    if (split_bww_reject(g, b)) return 0;
+    return wg_dz_bytes(g) + wg_part_bytes(g);
+}
+
+int kan_conv_bwd_weight_split(const float* dz, const float* x, float* dw_base, float* dw_basis, void* workspace, const KanGeom* g, const KanBasis* b, void* stream) {
+    const char* why = split_bww_reject(g, b);
+    if (why) return kan_fail_msg("%s", why);
+    if (!dz || !x || !dw_base || !dw_basis || !workspace) return kan_fail_msg("kan_conv_bwd_weight_split: null pointer%s", "");
+    if ((uintptr_t)workspace & 15) return kan_fail_msg("kan_conv_bwd_weight_split: workspace must be 16-byte aligned%s", "");
+    if (kan_raise_lds_limit((const void*)k_split_bwd_weight<8>, lds_bytes_wg<8>()) || kan_raise_lds_limit((const void*)k_split_bwd_weight<16>, lds_bytes_wg<16>()))
+        return kan_fail_msg("kan_conv_bwd_weight_split: cannot reserve %s of LDS", "142 KB");
+    const DevBasis db = dev_basis(b);
+    const hipStream_t st = (hipStream_t)stream;
+    const int o_tiles = g->O / 128, KS = wg_ksplit(g), HW = g->H * g->W, n_cut = wg_octets(g) * (HW / 16) * (g->O / 16), n_oc = g->O * g->C;
+    __bf16* dzc = (__bf16*)workspace;
+    float* part = (float*)((char*)workspace + wg_dz_bytes(g));
+    hipLaunchKernelGGL(k_cut_dz, dim3((unsigned)n_cut), dim3(256), 0, st, dz, dzc, g->B, g->O, HW);      // one workgroup per (octet, 16 pixels, 16 outputs)
+    const dim3 grid((unsigned)(g->C * o_tiles * KS));
+    if (g->H == 8)
+        hipLaunchKernelGGL(k_split_bwd_weight<8>, grid, dim3(512), lds_bytes_wg<8>(), st, x, (const __bf16*)dzc, part, db, g->B, g->C, g->O, o_tiles, KS, (int)wg_dz_bytes(g));
+    else
+        hipLaunchKernelGGL(k_split_bwd_weight<16>, grid, dim3(512), lds_bytes_wg<16>(), st, x, (const __bf16*)dzc, part, db, g->B, g->C, g->O, o_tiles, KS, (int)wg_dz_bytes(g));
+    hipLaunchKernelGGL(k_wgrad_reduce, dim3((n_oc * WG_COLS + 255) / 256), dim3(256), 0, st, (const float*)part, dw_base, dw_basis, n_oc, KS);
+    return hipGetLastError() == hipSuccess ? 0 : kan_fail_msg("kan_conv_bwd_weight_split: launch failed%s", "");
 }
 
 }  // extern "C"

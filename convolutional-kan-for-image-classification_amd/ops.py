@@ -414,6 +414,9 @@ def _split_bwd_weights(spec: ConvSpec, x: torch.Tensor, xn, phases, w_base, w_ba
     key = (wb.data_ptr(), ws.data_ptr(), x.device.index)
     stamps = (_owner(wb)._version, _owner(ws)._version, _EPOCH)
     ent = _SPLIT_BWD_CACHE.get(key)
+    if ent is None:                                     # drop the entry when a weight tensor dies: another model's weights may get the same addresses and stamps
+        for o in (_owner(wb), _owner(ws)):
+            weakref.finalize(o, _SPLIT_BWD_CACHE.pop, key, None)
     wcd = ent[1] if ent is not None and ent[1].numel() == nbytes else None
     if wcd is None or ent[0] != stamps or _ALWAYS_PACK:
         wcd = _cut_weights_bwd_data(geom, basis, wb, ws, wcd)
@@ -432,6 +435,42 @@ def _cut_weights_bwd_data(geom, basis, w_base: torch.Tensor, w_basis: torch.Tens
     L.check(lib.kan_split_pack_weights_bwd_data(_ptr(w_base), _ptr(w_basis), C.c_void_p(wcd.data_ptr()), C.byref(geom), C.byref(basis), _stream(w_base)),
             "kan_split_pack_weights_bwd_data")
     return wcd
+
+
+_SPLIT_BWD_WEIGHT = False
+
+
+@contextlib.contextmanager
+def split_precision_backward_weight():
+    """OPT-IN, training: a conv autograd Function whose FORWARD runs inside (the decision is taken there and carried on the autograd node, so a backward
+    run outside still takes it), whose weights need a gradient and whose stage is in scope of `kan_conv_bwd_weight_split` (one group, base branch, no
+    second input, no phases, no plane windows, `kan_split_supported`: default B-spline spec on 8x8 / 16x16 planes, 3x3 / stride 1 / pad 1, C % 8 == 0,
+    O % 128 == 0, even batch on 8x8) computes its WEIGHT gradient in split precision (3 x bf16 pieces, six bf16 MFMA products), straight into the tensors
+    the exact path would fill (GRAD_SINKS included).  The forward, the input gradient and every other layer stay on exact fp32 MFMA.  Never on by default."""
+    global _SPLIT_BWD_WEIGHT
+    prev, _SPLIT_BWD_WEIGHT = _SPLIT_BWD_WEIGHT, True
+    try:
+        yield
+    finally:
+        _SPLIT_BWD_WEIGHT = prev
+
+
+@contextlib.contextmanager
+def split_precision_backward():
+    """`split_precision_backward_data` and `split_precision_backward_weight` at once: the whole backward of the layers in scope."""
+    with split_precision_backward_data(), split_precision_backward_weight():
+        yield
+
+
+def _split_bwd_weight_stage(spec: ConvSpec, x: torch.Tensor, xn, phases, w_basis, need_w: bool) -> bool:
+    """Whether this stage's backward takes kan_conv_bwd_weight_split: inside `split_precision_backward_weight`, with a weight gradient to compute, under
+    the host conditions of `_split_bwd_weights` and with a workspace size from the library (0 = out of scope)."""
+    if not (_SPLIT_BWD_WEIGHT and need_w):
+        return False
+    if spec.groups != 1 or not spec.has_base or xn is not None or phases is not None or x.dim() != 4 or spec.first or spec.w_layout == W_IOD:
+        return False
+    geom, basis, _ = _plan_cached(*_plan_key(spec, x.shape, w_basis[0].shape[0]))
+    return L.load().kan_split_bwd_weight_workspace_bytes(C.byref(geom), C.byref(basis)) > 0
 
 
 def weights_changed() -> None:
@@ -595,10 +634,11 @@ def _sink_for(wid, shape, device):
     return t
 
 
-def _conv_backward(spec: ConvSpec, x, xn, packed, dz, need_x: bool, need_xn: bool, need_w: bool, phases=None, mode: int = 0, wids=None, dparams=None, wcd=None):
+def _conv_backward(spec: ConvSpec, x, xn, packed, dz, need_x: bool, need_xn: bool, need_w: bool, phases=None, mode: int = 0, wids=None, dparams=None, wcd=None, wsplit: bool = False):
     """dz: [B,O,Ho,Wo] contiguous.  Returns (dx, dxn, dw_base list, dw_basis list) -- per-group views of stacked gradients.
     `wids`: ids of the (base, basis) weight Parameters of a single-group layer, for GRAD_SINKS.
-    `wcd`: cut weights handed over by a forward under `split_precision_backward_data`: dx comes from kan_conv_bwd_data_split iff it is given."""
+    `wcd`: cut weights handed over by a forward under `split_precision_backward_data`: dx comes from kan_conv_bwd_data_split iff it is given.
+    `wsplit`: decided by a forward under `split_precision_backward_weight`: the weight gradients come from kan_conv_bwd_weight_split."""
     lib = L.load()
     B, Ct, H, W = x.shape
     G = spec.groups
@@ -613,8 +653,15 @@ def _conv_backward(spec: ConvSpec, x, xn, packed, dz, need_x: bool, need_xn: boo
     wd, x_pm = packed
     dw_base: List[Optional[torch.Tensor]] = [None] * G
     dw_basis: List[Optional[torch.Tensor]] = [None] * G
-    dz_pm = _position_major(dz, 0, Ot) if (plan.dz_pm_wanted and xn is None) else None
-    if need_w:
+    exact_w, exact_x = need_w and not wsplit, (need_x or need_xn) and not (need_x and wcd is not None)      # the launches that read dz_pm
+    dz_pm = _position_major(dz, 0, Ot) if (plan.dz_pm_wanted and xn is None and (exact_w or exact_x)) else None
+    if need_w and wsplit:                                # opt-in split-precision weight gradient: no packed slabs, no unpack; same tensors, same sinks
+        sb, ss = (_sink_for(wids[0], (Og, Cg, kh, kw), x.device), _sink_for(wids[1], (Og, Cg * spec.n_basis, kh, kw), x.device)) if wids else (None, None)
+        dwb = sb if sb is not None else torch.empty((Og, Cg, kh, kw), device=x.device, dtype=torch.float32)
+        dws = ss if ss is not None else torch.empty((Og, Cg * spec.n_basis, kh, kw), device=x.device, dtype=torch.float32)
+        kan_conv_bwd_weight_split(spec, x, dz, out=(dwb, dws))
+        dw_base, dw_basis = list(dwb.unsqueeze(0).unbind(0)), list(dws.unsqueeze(0).unbind(0))       # views, as the exact path returns them
+    elif need_w:
         dwp = torch.empty(plan.bwd_weight_splits * plan.bwd_weight_slab_elems, device=x.device, dtype=torch.float32)
         if plan.bwd_weight_expanded and xn is None and dz_pm is not None:
             # small padded planes: expanded position-major operand, DMA + MFMA weight gradient (kanconv.h)
@@ -718,6 +765,7 @@ class _KanConv(torch.autograd.Function):
             z, (wd, x_pm), geom, _, plan = _conv_forward(spec, x, xn, w_base, w_basis, need_dgrad, phases)
             z = _sum_slabs(z, geom.B, z.shape[2], geom.Ho * geom.Wo)
             wcd = _split_bwd_weights(spec, x, xn, phases, w_base, w_basis, need_dgrad)
+            ctx.wsplit = _split_bwd_weight_stage(spec, x, xn, phases, w_basis, any(ctx.needs_input_grad[4:]))
         ctx.spec = spec
         # the basis weights are kept only for the parameter gradient (their version counters are then checked in the backward)
         kept_w = {f"w_basis{g}": w for g, w in enumerate(w_basis)} if phases is not None else {}
@@ -740,7 +788,7 @@ class _KanConv(torch.autograd.Function):
             dpar = None
             if in_epilogue:                                    # ReLU-KAN: [Cg, 2, n] directly; Gram: 64 slot rows of partial sums
                 dpar = torch.zeros_like(phases) if spec.kind == L.BASIS_RELU else phases.new_zeros((64, spec.n_basis))
-            dx, dxn, dwb, dws = _conv_backward(spec, x, xn, packed, dz, need_x, need_xn, need_w, phases, dparams=dpar, wcd=wcd)
+            dx, dxn, dwb, dws = _conv_backward(spec, x, xn, packed, dz, need_x, need_xn, need_w, phases, dparams=dpar, wcd=wcd, wsplit=ctx.wsplit)
             if in_epilogue:
                 dph = dpar if spec.kind == L.BASIS_RELU else dpar.sum(dim=0)
             if need_p and not in_epilogue:
@@ -898,6 +946,7 @@ class _KanConvInPrelu(torch.autograd.Function):
             else:
                 zs, (wd, x_pm), _, _, plan = _conv_forward(spec, x, None, w_base, w_basis, bool(ctx.needs_input_grad[7]))
             wcd = _split_bwd_weights(spec, x, None, None, w_base, w_basis, bool(ctx.needs_input_grad[7]))
+            ctx.wsplit = _split_bwd_weight_stage(spec, x, None, None, w_basis, any(ctx.needs_input_grad[8:8 + nw]))
             # all groups in one launch: per-channel gamma/beta concatenated, one PReLU slope per Og channels
             gamma, beta, slope = _cat(gammas), _cat(betas), _cat(prelus)
             y, z, mean, rstd, pidx = _norm_fwd(zs, plan.fwd_slab_elems, gamma, beta, slope, eps, G, pool, bn=bn)
@@ -915,7 +964,7 @@ class _KanConvInPrelu(torch.autograd.Function):
             nw = G * (2 if spec.has_base else 1)
             need_x = ctx.needs_input_grad[7]
             need_w = any(ctx.needs_input_grad[8:8 + nw])
-            dx, _, dwb, dws = _conv_backward(spec, x, None, (wd, x_pm), dz, need_x, False, need_w, wids=ctx.wids, wcd=wcd)
+            dx, _, dwb, dws = _conv_backward(spec, x, None, (wd, x_pm), dz, need_x, False, need_w, wids=ctx.wids, wcd=wcd, wsplit=ctx.wsplit)
         grads = _flat_grads(spec, dwb, dws)
         if gamma is not None:
             grads += tuple(dgam.view(G, -1).unbind(0)) + tuple(dbet.view(G, -1).unbind(0))
@@ -1130,6 +1179,35 @@ def kan_conv_bwd_data_split(spec: ConvSpec, x: torch.Tensor, dz: torch.Tensor, w
         dx = torch.empty_like(x)
         L.check(lib.kan_conv_bwd_data_split(_ptr(dz), _ptr(x), C.c_void_p(wcd.data_ptr()), _ptr(dx), C.byref(geom), C.byref(basis), _stream(x)), "kan_conv_bwd_data_split")
     return dx, wcd
+
+
+def kan_conv_bwd_weight_split(spec: ConvSpec, x: torch.Tensor, dz: torch.Tensor, out=None):
+    """OPT-IN split-precision weight gradient of the conv stage (no autograd; kanconv.h `kan_conv_bwd_weight_split`): what the backward of `kan_conv` returns
+    for the base / spline weights, through 3 x bf16 pieces of the plane values (the exact kernel's) and of dz and six bf16 MFMA products per k-block.  Scope:
+    that of `kan_conv_fwd_split` (raises KanConvError otherwise).  Returns (dw_base [O, C, 3, 3], dw_basis [O, C * 8, 3, 3]); `out`: a pair of contiguous
+    fp32 tensors of those shapes to write into.  The workspace (cut dz + depth-split partial sums) comes from torch's allocator on the current stream."""
+    lib = L.load()
+    x, dz = _require(x, "x"), _require(dz, "dz")
+    if x.dim() != 4 or dz.dim() != 4:
+        raise L.KanConvError(f"split-precision bwd-weight: NCHW x and dz, got {tuple(x.shape)} and {tuple(dz.shape)}")
+    Ot, Ct = dz.shape[1], x.shape[1]
+    geom, basis, _ = _plan_cached(*_plan_key(spec, x.shape, Ot))
+    nbytes = lib.kan_split_bwd_weight_workspace_bytes(C.byref(geom), C.byref(basis)) if spec.groups == 1 and spec.has_base and not spec.first else 0
+    if not nbytes:
+        raise L.KanConvError("split-precision bwd-weight: default B-spline spec (grid 5, order 3, SiLU base branch), 8x8 or 16x16 planes, 3x3 / stride 1 / pad 1, one group, "
+                             "C % 8 == 0, O % 128 == 0, even batch on 8x8 planes only")
+    if tuple(dz.shape) != (geom.B, Ot, geom.Ho, geom.Wo):
+        raise L.KanConvError(f"split-precision bwd-weight: dz {tuple(dz.shape)} != {(geom.B, Ot, geom.Ho, geom.Wo)}")
+    shapes = ((Ot, Ct, 3, 3), (Ot, Ct * spec.n_basis, 3, 3))
+    with torch.cuda.device(x.device):
+        if out is None:
+            out = tuple(torch.empty(sh, device=x.device, dtype=torch.float32) for sh in shapes)
+        elif any(tuple(t.shape) != sh or t.dtype != torch.float32 or t.device != x.device or not t.is_contiguous() for t, sh in zip(out, shapes)):
+            raise L.KanConvError(f"split-precision bwd-weight: out must be contiguous fp32 tensors {shapes} on {x.device}")
+        ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+        L.check(lib.kan_conv_bwd_weight_split(_ptr(dz), _ptr(x), _ptr(out[0]), _ptr(out[1]), C.c_void_p(ws.data_ptr()), C.byref(geom), C.byref(basis), _stream(x)),
+                "kan_conv_bwd_weight_split")
+    return out[0], out[1]
 
 
 def instance_norm(x: torch.Tensor, gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None, eps: float = 1e-5):

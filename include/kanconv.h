@@ -389,6 +389,22 @@ long long kan_split_bwd_data_weight_bytes(const KanGeom* geom, const KanBasis* b
 int kan_split_pack_weights_bwd_data(const float* w_base, const float* w_basis, void* wcd, const KanGeom* geom, const KanBasis* basis, void* stream);
 int kan_conv_bwd_data_split(const float* dz, const float* x, const void* wcd, float* dx, const KanGeom* geom, const KanBasis* basis, void* stream);
 
+/* OPT-IN split-precision weight gradient: NOT reached from kan_conv_bwd_weight, never the default.  The arithmetic and the scope of
+ * the two split launches above (kan_split_supported serves all three): the expanded plane values (the exact kernels' own) and dz are cut into three bf16
+ * pieces, six bf16 MFMA products per 16-deep block, fp32 accumulation.  Computes what kan_conv_bwd_weight + kan_unpack_wgrad compute for such a layer -- the
+ * autograd of kan_layers.py:199-200, 203-239 w.r.t. the base_conv / spline_conv weights -- straight into the reference layouts dw_base[O][C][3][3] and
+ * dw_basis[O][C * 8][3][3] (channel c * 8 + k), every element written exactly once, nothing else written, no float atomics: two calls give the same bits.
+ * Any batch the scope admits, batch tails included (images are the inner depth index, in octets; missing images are zeros).
+ *   kan_split_bwd_weight_workspace_bytes   size of `workspace` (0 = out of scope; in scope always > 0): the cut dz, then the depth-split partial sums,
+ *                                          dzc [ceil(B / 8) octets][H * W pixels][3 pieces][O][8 bf16 of consecutive images]
+ *                                          part[KS][O][C][81 floats: 9 planes x 9 taps],   KS = min(32, ceil(512 / (C * O / 128)), units),
+ *                                          units = ceil(B / 8) on 8x8 planes, 4 ceil(B / 8) on 16x16 planes (depth units of 64 pixels x 8 images)
+ *   kan_conv_bwd_weight_split              cuts dz, contracts, adds the KS partials in ascending order; `workspace` is scratch (16-byte aligned)
+ * Out-of-scope geometry, null pointers and a workspace that is not 16-byte aligned are refused by host arithmetic before any launch. */
+long long kan_split_bwd_weight_workspace_bytes(const KanGeom* geom, const KanBasis* basis);
+int kan_conv_bwd_weight_split(const float* dz, const float* x, float* dw_base, float* dw_basis, void* workspace,
+                              const KanGeom* geom, const KanBasis* basis, void* stream);
+
 /* One AdamW step over a flat fp32 block of n elements, in place (p, m = exp_avg, v = exp_avg_sq; g is read only and
  * multiplied by grad_scale first).  Replaces the per-tensor update loop of torch.optim.AdamW as the reference builds it
  * (generic_train.py:24 `optim.AdamW(model.parameters(), lr, weight_decay)`, stepped once per batch: evaluations.py train()),
