@@ -18,7 +18,7 @@ KAN_MAX_TABLE = 32
 KAN_FP_WORDS = 192
 BASIS_BSPLINE, BASIS_RBF, BASIS_CHEBY, BASIS_POLY, BASIS_FOURIER, BASIS_RELU, BASIS_GRAM = 0, 1, 2, 3, 4, 5, 6
 ACT_NONE, ACT_IDENTITY, ACT_GELU, ACT_SILU, ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_GELU_TANH = -1, 0, 1, 2, 3, 4, 5, 6
-ORDER_QUAD_FWD, ORDER_ROWBLK8_FWD, ORDER_QUAD_BWD_DATA = 1, 2, 4          # kan_tile_orders bits (KAN_ORDER_*)
+ORDER_QUAD_FWD, ORDER_ROWBLK8_FWD, ORDER_QUAD_BWD_DATA, ORDER_FWD_WEIGHT_SIDE = 1, 2, 4, 8        # kan_tile_orders bits (KAN_ORDER_*)
 
 
 class KanGeom(C.Structure):
@@ -83,6 +83,7 @@ SIGNATURES = {
     "kan_conv_bwd_weight": (_I, [_P, _P, _P, _P, _GP, _BP, _P, _P, _P]),
     "kan_position_major_expanded": (_I, [_P, _P, _GP, _BP, _P]),
     "kan_conv_fwd_expanded": (_I, [_P, _P, _P, _GP, _BP, _P]),
+    "kan_conv_fwd_expanded_order": (_I, [_P, _P, _P, _GP, _BP, _P, _I]),
     "kan_conv_bwd_weight_expanded": (_I, [_P, _P, _P, _GP, _BP, _P]),
     "kan_unpack_wgrad": (_I, [_P, _P, _P, _GP, _BP, _P]),
     "kan_unpack_wgrad_iod": (_I, [_P, _P, _GP, _BP, _P]),

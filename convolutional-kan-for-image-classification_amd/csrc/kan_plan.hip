@@ -432,6 +432,11 @@ int plan_conv(const KanGeom* g, const KanBasis* b, ConvPlan* cp) {
     // 8x8 planes: row blocks on half-plane tiles of 4 images (k_conv_fwd_halo<4, 8, 4, 4>) instead of whole planes of 2: the same B / 2 tiles, splits
     // and slabs, again invisible in KanPlan (row_blocks stays 0 for these geometries)
     c.rowblk8_fwd = halo && g->H == 8 && g->W == 8 && c.fc.TO == 256 && g->B % 4 == 0 && !tuning_off("KAN_ROWBLK8_FWD");
+    // 2x2 planes under 3x3 / s1 / p1 / d1: the expanded forward puts the four output positions on the weight side of its tiles (32 outputs x 4
+    // positions x 128 images: the same 32 tiles per split) and stores whole 16-byte groups z[b][o][0..3]; same steps per split, same slabs
+    // bit for bit (0.212 -> 0.153 ms per launch on 512 -> 512); -DKAN_TUNING_KNOBS + KAN_PMDMA_FWD_WQ=0 runs the other order
+    c.fwd_wq = c.fwd == Route::EXPANDED && g->H == 2 && g->W == 2 && g->Ho == 2 && g->Wo == 2 && g->kh == 3 && g->kw == 3 && g->sh == 1 && g->sw == 1 &&
+               g->ph == 1 && g->pw == 1 && g->dh == 1 && g->dw == 1 && pl->P == 9 && pl->KC == 18 && g->y_bstride % 4 == 0 && !tuning_off("KAN_PMDMA_FWD_WQ");
     if (dw) {                                   // direct depthwise kernels: no split-K on the data path, no position-major copies
         pl->fwd_splits = pl->bwd_data_splits = 1;
         pl->bwd_weight_splits = dw_weight_chunks(g);

@@ -199,39 +199,80 @@ __global__ __launch_bounds__(256) void k_pack(const float* __restrict__ src_base
     }
 }
 
+// Sum of the weight-gradient slabs, transposed back to the reference layout.  A tile is UNPACK_TO = 64 outputs x UNPACK_TJ = 32 source
+// columns j: a thread owns one 16-byte group of four outputs in two rows (j, j + 16) of the packed slabs -- the rows are contiguous in o
+// and Opad is a multiple of 64, so a tile reads whole 128-byte lines -- and the tile leaves through LDS as rows of 32 consecutive j.
+// Loads are unconditional on a clamped row (pack_row once per row, not per element and slab) and all loads of a slab group are issued
+// before the first add (the branchy 4-byte version kept 2 - 3 loads in flight per element); what lies outside O x J is dropped at the store.
+// Per element the sum is the fixed sequence the 4-byte kernel used (and k_unpack_iod uses): eight running sums over slabs s, s + 8, ...,
+// the remainder into the first, then the tree ((s0+s1)+(s2+s3))+((s4+s5)+(s6+s7)) -- the same bits.
+constexpr int UNPACK_TO = 64, UNPACK_TJ = 32;
+__device__ __forceinline__ float4 f4_add(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }
+// s0 (of both rows) += slabs 0 .. N - 1 at a0 / a1, in slab order; the 2 N loads go out first
+template <int N>
+__device__ __forceinline__ void unpack_tail(float4& r0, float4& r1, const float* a0, const float* a1, long long slab_elems) {
+    float4 v0[N], v1[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        v0[i] = *reinterpret_cast<const float4*>(a0 + (size_t)i * slab_elems);
+        v1[i] = *reinterpret_cast<const float4*>(a1 + (size_t)i * slab_elems);
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) { r0 = f4_add(r0, v0[i]); r1 = f4_add(r1, v1[i]); }
+}
 __global__ __launch_bounds__(256) void k_unpack(const float* __restrict__ dwp, float* __restrict__ dst_base, float* __restrict__ dst_basis,
                                                 PackGeo q, int nb_base, int n_slabs, long long slab_elems, long long dwp_gstride) {
-    __shared__ float tile[32][33];
+    __shared__ float tile[UNPACK_TO][UNPACK_TJ + 1];
     const int src_kind = (int)blockIdx.x < nb_base ? 0 : 1;           // block-uniform: base gradient first, then basis
     const int bx = src_kind == 0 ? blockIdx.x : blockIdx.x - nb_base;
     const int J = src_kind == 0 ? q.C * q.T : q.C * q.nb * q.T;
     dwp += (size_t)blockIdx.z * dwp_gstride;
     float* dst = (src_kind == 0 ? dst_base : dst_basis) + (size_t)blockIdx.z * q.O * J;
-    const int j0 = bx * 32, o0 = blockIdx.y * 32;
-    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
+    const int j0 = bx * UNPACK_TJ, o0 = blockIdx.y * UNPACK_TO;       // o0 + 64 <= Opad: no clamp along o
+    const int ol = 4 * (threadIdx.x & 15), jl = threadIdx.x >> 4;     // outputs o0 + ol .. + 3 of rows j0 + jl and j0 + jl + 16
+    const float* a0 = dwp + (size_t)pack_row(q, src_kind, min(j0 + jl, J - 1)) * q.Opad + o0 + ol;
+    const float* a1 = dwp + (size_t)pack_row(q, src_kind, min(j0 + jl + 16, J - 1)) * q.Opad + o0 + ol;
+    const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 s[2][8];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        int j = j0 + ty + 8 * i, o = o0 + tx;
-        float s = 0.f;
-        if (j < J && o < q.O) {
-            const float* a = dwp + (size_t)pack_row(q, src_kind, j) * q.Opad + o;
-            float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f, s4 = 0.f, s5 = 0.f, s6 = 0.f, s7 = 0.f;
-            int sl = 0;
-            for (; sl + 8 <= n_slabs; sl += 8) {               // 8 loads in flight; fixed summation order => deterministic
-                const float* b = a + (size_t)sl * slab_elems;
-                s0 += b[0]; s1 += b[slab_elems]; s2 += b[2 * slab_elems]; s3 += b[3 * slab_elems];
-                s4 += b[4 * slab_elems]; s5 += b[5 * slab_elems]; s6 += b[6 * slab_elems]; s7 += b[7 * slab_elems];
-            }
-            for (; sl < n_slabs; ++sl) s0 += a[(size_t)sl * slab_elems];
-            s = ((s0 + s1) + (s2 + s3)) + ((s4 + s5) + (s6 + s7));
+    for (int i = 0; i < 8; ++i) s[0][i] = s[1][i] = zero;
+    int sl = 0;
+    for (; sl + 8 <= n_slabs; sl += 8) {                              // 16 loads in flight; fixed summation order => deterministic
+        float4 v[2][8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            v[0][i] = *reinterpret_cast<const float4*>(a0 + (size_t)(sl + i) * slab_elems);
+            v[1][i] = *reinterpret_cast<const float4*>(a1 + (size_t)(sl + i) * slab_elems);
         }
-        tile[ty + 8 * i][tx] = s;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) { s[0][i] = f4_add(s[0][i], v[0][i]); s[1][i] = f4_add(s[1][i], v[1][i]); }
+    }
+    {
+        const float* b0 = a0 + (size_t)sl * slab_elems;
+        const float* b1 = a1 + (size_t)sl * slab_elems;
+        switch (n_slabs - sl) {                                       // (uniform) the remaining 0 - 7 slabs go into s0, in order
+            case 1: unpack_tail<1>(s[0][0], s[1][0], b0, b1, slab_elems); break;
+            case 2: unpack_tail<2>(s[0][0], s[1][0], b0, b1, slab_elems); break;
+            case 3: unpack_tail<3>(s[0][0], s[1][0], b0, b1, slab_elems); break;
+            case 4: unpack_tail<4>(s[0][0], s[1][0], b0, b1, slab_elems); break;
+            case 5: unpack_tail<5>(s[0][0], s[1][0], b0, b1, slab_elems); break;
+            case 6: unpack_tail<6>(s[0][0], s[1][0], b0, b1, slab_elems); break;
+            case 7: unpack_tail<7>(s[0][0], s[1][0], b0, b1, slab_elems); break;
+            default: break;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        const float4 t = f4_add(f4_add(f4_add(s[r][0], s[r][1]), f4_add(s[r][2], s[r][3])), f4_add(f4_add(s[r][4], s[r][5]), f4_add(s[r][6], s[r][7])));
+        const int j = jl + 16 * r;
+        tile[ol][j] = t.x; tile[ol + 1][j] = t.y; tile[ol + 2][j] = t.z; tile[ol + 3][j] = t.w;
     }
     __syncthreads();
+    const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        int o = o0 + ty + 8 * i, j = j0 + tx;
-        if (o < q.O && j < J) dst[(size_t)o * J + j] = tile[tx][ty + 8 * i];
+    for (int i = 0; i < UNPACK_TO / 8; ++i) {
+        const int o = o0 + ty + 8 * i, j = j0 + tx;
+        if (o < q.O && j < J) dst[(size_t)o * J + j] = tile[ty + 8 * i][tx];
     }
 }
 
@@ -1823,6 +1864,114 @@ __global__ __launch_bounds__(256, 4) void k_conv_fwd_pmdma(
     }
 }
 
+// The same forward on 2x2 planes under 3x3 / stride 1 / pad 1 / dilation 1, the four output positions on the A (weight) side.  There every
+// (output position q, input position p) pair is live under exactly one tap, tap(q, p) = (p_r - q_r + 1) * 3 + (p_c - q_c + 1) =
+// tap(q, 0) + 3 p_r + p_c: a dense GEMM.  A tile is 32 outputs x 4 positions (128 A rows) x 128 images; a step is (input position p,
+// channel pair) in (p, pair) order: B = the 18 e_pm rows of the pair at p (as above), A = sW[18][128] with column
+// (o_l >> 4) * 64 + q * 16 + (o_l & 15), each 16-byte DMA chunk four consecutive outputs of step (tap(q, p), pair) of wp.  The per-lane
+// part of the source is tap(q, 0)'s step, the row and the chunk; p and the pair only move the wave-uniform part, so the loop holds no
+// vector address arithmetic.  For a fixed q ascending p is ascending live tap, and split z takes steps [z n / S, (z + 1) n / S) of the
+// n = 4 C / 2, which is where live_step_pos cuts the kernel above: slab z holds the same partial sums, accumulated in the same order
+// (bit-identical slabs).  Wave w_o owns outputs 16 w_o .. + 15 under all four q, MFMA block mi the positions 2 mi and 2 mi + 1, so by the
+// 32x32 accumulator layout a lane holds the four positions of one (b, o) in acc[0][ni][r], acc[0][ni][r + 8], acc[1][ni][r],
+// acc[1][ni][r + 8] (r < 8) and stores them as ONE 16-byte group z[b][o][0..3]: 16 stores per lane instead of 64, registers r & 3 and the
+// lane halves completing a 128-byte line within four store instructions (the kernel above leaves each group to four workgroups).
+// tools/probe/fwd_wq_emul.py restates this index arithmetic in numpy.
+template <int KC>
+__global__ __launch_bounds__(256, 4) void k_conv_fwd_pmdma_wq(
+    const float* __restrict__ e_pm, const float* __restrict__ wp, float* __restrict__ z, DevGeom g, int Opad, int n_chunks,
+    int chunks_per_split, long long slab_elems, unsigned e_bytes, unsigned w_bytes, int tiles_o, int xcd) {
+    constexpr int TO = 128, TP = 128, NQ = KC / 2, P = KC / 2, HW = 4;     // NQ 1-KiB wave copies per operand and step
+    __shared__ __attribute__((aligned(16))) float sW[2 * KC * TO];
+    __shared__ __attribute__((aligned(16))) float sE[2 * KC * TP];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int w_o = wave >> 1, w_p = wave & 1, kh2 = lane >> 5;
+    const BlockId blk = xcd_block_order(xcd != 0);
+    const int grp = blk.y / tiles_o, tiles_b = g.B / TP;                   // grid.x = 4 output sub-tiles x image tiles (the tile count of the kernel above)
+    const int sub = blk.x / tiles_b, b0 = (blk.x - sub * tiles_b) * TP;
+    const int o_tile0 = ((blk.y - grp * tiles_o) * 4 + sub) * 32;          // the tile: outputs o_tile0 .. + 31 at all four positions, images b0 .. + 127
+    const int pairs = g.C >> 1;
+    e_pm += (size_t)grp * g.C * HW * P * g.B;
+    z += (size_t)grp * g.O * HW;
+    wp += (size_t)grp * n_chunks * KC * Opad;
+    const kan_rsrc e_rs = make_rsrc(e_pm, e_bytes), w_rs = make_rsrc(wp, w_bytes);
+
+    // per-lane parts of the DMA sources (wave w issues copies w, w + 4, w + 8 of each operand: two rows per copy)
+    unsigned eoff[(NQ + 3) / 4];
+#pragma unroll
+    for (int j = 0; j < (NQ + 3) / 4; ++j) {
+        const int r = min(2 * (j * 4 + wave) + (lane >> 5), KC - 1), cl = r / P, pp = r - cl * P;
+        eoff[j] = (unsigned)(((cl * HW) * P + pp) * g.B + (lane & 31) * 4) * 4u;
+    }
+    unsigned woff;
+    {
+        const int col = (lane & 31) * 4, q = (col >> 4) & 3, o_l = (col >> 6) * 16 + (col & 15);
+        const int tap0 = (1 - (q >> 1)) * 3 + (1 - (q & 1));               // tap(q, p = 0)
+        woff = (unsigned)((tap0 * pairs * KC + (lane >> 5)) * Opad + o_l) * 4u;
+    }
+    auto issue = [&](int p, int pair, int buf) {
+        const int se = __builtin_amdgcn_readfirstlane((((2 * pair * HW + p) * P) * g.B + b0) * 4);
+        const int sw = __builtin_amdgcn_readfirstlane(((((3 * (p >> 1) + (p & 1)) * pairs + pair) * KC) * Opad + o_tile0) * 4);
+        float* dE = sE + buf * (KC * TP);
+        float* dW = sW + buf * (KC * TO);
+#pragma unroll
+        for (int j = 0; j < (NQ + 3) / 4; ++j) {
+            const int q = j * 4 + wave;
+            if (q < NQ) {
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(e_rs, (__attribute__((address_space(3))) void*)(dE + q * 256), 16, (int)eoff[j], se, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rs, (__attribute__((address_space(3))) void*)(dW + q * 256), 16, (int)woff,
+                                                         sw + q * 2 * Opad * 4, 0, 0);
+            }
+        }
+    };
+
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[a][b][r] = 0.f;
+
+    int ch0, ch1;                                                          // steps [ch0, ch1) of the n = 4 * pairs, all live
+    {
+        const int L = HW * pairs;
+        const int S = min((int)gridDim.z, max(1, (L + chunks_per_split - 1) / chunks_per_split));
+        if (blk.z >= S) { ch0 = ch1 = L; }
+        else {
+            ch0 = (int)((long long)L * blk.z / S);
+            ch1 = blk.z == S - 1 ? L : (int)((long long)L * (blk.z + 1) / S);
+        }
+    }
+    int p = ch0 / pairs, pair = ch0 - p * pairs;                           // of the step to issue next
+    int ch = ch0;
+    if (ch < ch1) issue(p, pair, 0);
+    const int ao = w_o * 64 + (lane & 31), bp = w_p * 64 + (lane & 31);
+    for (int cur = 0; ch < ch1; cur ^= 1) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        ++ch;
+        if (++pair == pairs) { pair = 0; ++p; }
+        if (ch < ch1) issue(p, pair, cur ^ 1);
+        const unsigned aw = lds_addr(sW + cur * (KC * TO) + kh2 * TO + ao), ae = lds_addr(sE + cur * (KC * TP) + kh2 * TP + bp);
+        KAN_MFMA_STEP(KC / 2, aw, TO, ae, TP);
+    }
+
+    float* zs = z + (size_t)blk.z * slab_elems;
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) {
+        const int b = b0 + w_p * 64 + ni * 32 + (lane & 31);
+        if (b >= g.B) continue;
+        float* zb = zs + (size_t)b * g.ybs;
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int o = o_tile0 + w_o * 16 + mfma_row(r, lane);          // rows 0 .. 15 of the block: (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+            if (o < g.O) *reinterpret_cast<float4*>(zb + (size_t)o * 4) = make_float4(acc[0][ni][r], acc[0][ni][r + 8], acc[1][ni][r], acc[1][ni][r + 8]);
+        }
+    }
+}
+
 // dW tile = 128 rows of the tap-major flat K axis (one tap: C*P % 128 == 0 is required) x 128 outputs; a step = 16 images of one
 // output position; steps whose (position, tap) pair reads padding are skipped, split ranges are cut over live steps
 // (as k_conv_bwd_weight).  No staging code at all.  Round 3: both operands are [row][16 images] with the images contiguous in HBM and in LDS,
@@ -2929,7 +3078,8 @@ int kan_tile_orders(const KanGeom* g, const KanBasis* b) {
     ConvPlan cp;
     if (plan_conv(g, b, &cp)) return 0;
     const bool halo = cp.fwd == Route::HALO;
-    return (halo && cp.quad_fwd ? KAN_ORDER_QUAD_FWD : 0) | (halo && cp.rowblk8_fwd ? KAN_ORDER_ROWBLK8_FWD : 0) | (cp.quad_bd ? KAN_ORDER_QUAD_BWD_DATA : 0);
+    return (halo && cp.quad_fwd ? KAN_ORDER_QUAD_FWD : 0) | (halo && cp.rowblk8_fwd ? KAN_ORDER_ROWBLK8_FWD : 0) | (cp.quad_bd ? KAN_ORDER_QUAD_BWD_DATA : 0) |
+           (cp.fwd_wq ? KAN_ORDER_FWD_WEIGHT_SIDE : 0);
 }
 
 int kan_pack_cacheable(const KanGeom* g, const KanBasis* b) {
@@ -2974,8 +3124,8 @@ static int unpack_wgrad_impl(const float* dwp, float* dw_base, float* dw_basis, 
                            pl.bwd_weight_slab_elems, pl.bwd_weight_slab_elems);
         n_slabs = 1;
     }
-    const int nb_base = hb ? ceil_div(g->C * T, 32) : 0;
-    dim3 grid(nb_base + ceil_div(g->C * b->n_basis * T, 32), ceil_div(g->O, 32), G);
+    const int nb_base = hb ? ceil_div(g->C * T, UNPACK_TJ) : 0;
+    dim3 grid(nb_base + ceil_div(g->C * b->n_basis * T, UNPACK_TJ), ceil_div(g->O, UNPACK_TO), G);
     if (iod) {
         const IodLaunch l = iod_launch(g, pl);
         hipLaunchKernelGGL(k_unpack_iod, dim3(l.blocks), dim3(256), 0, st, dwp, dw_basis, q, l.o_tiles, l.n_tiles, n_slabs, pl.bwd_weight_slab_elems,
@@ -3252,26 +3402,46 @@ int kan_position_major_expanded(const float* x, float* e_pm, const KanGeom* g, c
     return launch_ok("position_major_expanded");
 }
 
-int kan_conv_fwd_expanded(const float* e_pm, const float* wp, float* z, const KanGeom* g, const KanBasis* b, void* stream) {
+// order < 0: the planner's; 0 / KAN_ORDER_FWD_WEIGHT_SIDE: forced (kan_conv_fwd_expanded_order)
+static int conv_fwd_expanded_impl(const float* e_pm, const float* wp, float* z, const KanGeom* g, const KanBasis* b, void* stream, int order) {
     ConvPlan cp;
     if (int rc = plan_conv(g, b, &cp)) return rc;
     const KanPlan& pl = cp.pub;
     if (!e_pm || !wp || !z) return fail("null tensor pointer");
     if (cp.fwd != Route::EXPANDED) return fail("the forward of this geometry / basis does not read the expanded position-major copy (plan.fwd_expanded)");
+    if (order >= 0 && order != 0 && order != KAN_ORDER_FWD_WEIGHT_SIDE) return fail("order must be 0 or KAN_ORDER_FWD_WEIGHT_SIDE");
+    if (order == KAN_ORDER_FWD_WEIGHT_SIDE && !cp.fwd_wq) return fail("this geometry does not offer the weight-side order (kan_tile_orders)");
     const FwdCfg& c = cp.fc;                                // (128 x 128 tiles, 18-row steps of channel pairs: the planner's pmdma shape)
     DevGeom dg = dev_geom(g);
     dg.pix_major = 1;
+    if ((long long)c.tiles_o * ngroups(g) > 65535) return fail("groups * output tiles exceed the grid limit");
+    if (order < 0 ? cp.fwd_wq : order != 0) {               // same grid: 4 output sub-tiles x image tiles in x
+        if ((size_t)z & 15) return fail("the weight-side forward stores 16-byte groups: z must be 16-byte aligned");
+        dim3 grid(c.tiles_p, c.tiles_o * ngroups(g), pl.fwd_splits);
+        hipLaunchKernelGGL((k_conv_fwd_pmdma_wq<18>), grid, dim3(256), 0, (hipStream_t)stream, e_pm, wp, z, dg, pl.Opad, c.chunks, pl.fwd_target,
+                           pl.fwd_slab_elems, (unsigned)(((long long)pl.e_pm_elems - 256) * 4), (unsigned)((long long)pl.Kpad * pl.Opad * 4), c.tiles_o,
+                           cp.pmdma_xcd ? 1 : 0);
+        return launch_ok("conv_fwd_expanded");
+    }
     TilePerm perm; perm.n = 0;
     if (!cp.pmdma_xcd) {                                    // weight of a pixel tile = its live work (as kan_conv_fwd)
         const int tpp = ceil_div(g->B, c.TP), cpt = ceil_div(g->C, pl.IPC);
         perm = tile_perm(c.tiles_p, [&](int t) { return live_taps_out(g, t / tpp) * cpt; });
     }
-    if ((long long)c.tiles_o * ngroups(g) > 65535) return fail("groups * output tiles exceed the grid limit");
     dim3 grid(c.tiles_p, c.tiles_o * ngroups(g), pl.fwd_splits);
     hipLaunchKernelGGL((k_conv_fwd_pmdma<18>), grid, dim3(256), 0, (hipStream_t)stream, e_pm, wp, z, dg, pl.P, make_fastdiv(pl.P), pl.Opad, c.chunks,
                        pl.fwd_target, pl.fwd_slab_elems, (unsigned)(((long long)pl.e_pm_elems - 256) * 4),
                        (unsigned)((long long)pl.Kpad * pl.Opad * 4), perm, c.tiles_o, cp.pmdma_xcd ? 1 : 0);
     return launch_ok("conv_fwd_expanded");
+}
+
+int kan_conv_fwd_expanded(const float* e_pm, const float* wp, float* z, const KanGeom* g, const KanBasis* b, void* stream) {
+    return conv_fwd_expanded_impl(e_pm, wp, z, g, b, stream, -1);
+}
+
+int kan_conv_fwd_expanded_order(const float* e_pm, const float* wp, float* z, const KanGeom* g, const KanBasis* b, void* stream, int order) {
+    if (order < 0) return fail("order must be 0 or KAN_ORDER_FWD_WEIGHT_SIDE");
+    return conv_fwd_expanded_impl(e_pm, wp, z, g, b, stream, order);
 }
 
 int kan_conv_bwd_weight_expanded(const float* dz_pm, const float* e_pm, float* dwp, const KanGeom* g, const KanBasis* b, void* stream) {

@@ -145,10 +145,14 @@ int kan_plan(const KanGeom* geom, const KanBasis* basis, KanPlan* plan);
  *                          the block of the plane's first / last row under the tap row that leaves the plane (11/12 issued)
  *   KAN_ORDER_QUAD_BWD_DATA 4x4 planes, B % 32 == 0, O % 16 == 0: bwd-data runs quadrant tiles (25/36 issued) when it is given dz_pm and one input tensor;
  *                          otherwise it keeps the row blocks of KanPlan.row_blocks bit 1
+ *   KAN_ORDER_FWD_WEIGHT_SIDE 2x2 planes, 3x3 / stride 1 / pad 1 / dilation 1, y_bstride % 4 == 0: the expanded forward (plan.fwd_expanded) runs tiles of
+ *                          32 outputs x the 4 output positions x 128 images instead of 128 outputs x 1 position x 128 images and stores z[b][o][0..3] as one
+ *                          16-byte group; the slabs are bit for bit those of the other order
  * 0 for a geometry the planner rejects. */
 #define KAN_ORDER_QUAD_FWD 1
 #define KAN_ORDER_ROWBLK8_FWD 2
 #define KAN_ORDER_QUAD_BWD_DATA 4
+#define KAN_ORDER_FWD_WEIGHT_SIDE 8
 int kan_tile_orders(const KanGeom* geom, const KanBasis* basis);
 
 /* Pack the reference-layout weights of one group into the GEMM layouts of the kernels:
@@ -244,6 +248,9 @@ int kan_conv_bwd_weight(const float* dz, const float* x, const float* xn, float*
  * count as kan_conv_bwd_weight.  dz_pm = kan_position_major(dz).  Replaces the same reference lines as kan_conv_bwd_weight. */
 int kan_position_major_expanded(const float* x, float* e_pm, const KanGeom* geom, const KanBasis* basis, void* stream);
 int kan_conv_fwd_expanded(const float* e_pm, const float* wp, float* z, const KanGeom* geom, const KanBasis* basis, void* stream);   /* plan.fwd_expanded; z slabs as kan_conv_fwd */
+/* The same launch with the tile order forced, for A/B tests and profiling tools: order = 0 (one output position per tile) or KAN_ORDER_FWD_WEIGHT_SIDE
+ * (only where kan_tile_orders reports it; z 16-byte aligned).  Both orders write the same bits. */
+int kan_conv_fwd_expanded_order(const float* e_pm, const float* wp, float* z, const KanGeom* geom, const KanBasis* basis, void* stream, int order);
 int kan_conv_bwd_weight_expanded(const float* dz_pm, const float* e_pm, float* dwp,
                                  const KanGeom* geom, const KanBasis* basis, void* stream);
 
