@@ -340,7 +340,7 @@ def always_pack():
 
 
 _SPLIT_INFERENCE = False
-_SPLIT_CACHE: "OrderedDict" = OrderedDict()             # (weight addresses) -> (version stamps, epoch, cut weights)
+_SPLIT_CACHE: "OrderedDict" = OrderedDict()             # (weight addresses) -> (version stamps, epoch, cut weights of the forward launch)
 
 
 @contextlib.contextmanager
@@ -357,25 +357,67 @@ def split_precision_inference():
         _SPLIT_INFERENCE = prev
 
 
-def _split_stage(spec: ConvSpec, x: torch.Tensor, w_base, w_basis):
-    """[1, B, O, H, W] pre-norm slab through kan_conv_fwd_split, or None when the stage is out of its scope.  Cut weights are cached per weight pair."""
-    if spec.groups != 1 or not spec.has_base or x.dim() != 4:
+_SPLIT_FWD = False
+
+
+@contextlib.contextmanager
+def split_precision_forward():
+    """OPT-IN, training and inference: inside, a conv stage (`kan_conv`, `kan_conv_in_prelu`) in scope of `kan_conv_fwd_split` (one group, base branch, no
+    second input, no phases, no plane windows, `kan_split_supported`: default B-spline spec on 8x8 / 16x16 planes, 3x3 / stride 1 / pad 1, C % 8 == 0,
+    O % 128 == 0, even batch on 8x8) runs its FORWARD in split precision (3 x bf16 pieces, six bf16 MFMA products), with grad mode on or off.  Its backward
+    stays the exact one -- the forward hands it what it needs -- unless the backward contexts are entered too (`split_precision_training`).  Every other
+    layer stays on exact fp32 MFMA.  Never on by default."""
+    global _SPLIT_FWD
+    prev, _SPLIT_FWD = _SPLIT_FWD, True
+    try:
+        yield
+    finally:
+        _SPLIT_FWD = prev
+
+
+def _split_stage(spec: ConvSpec, x: torch.Tensor, xn, phases, w_base, w_basis):
+    """[B, O, H, W] pre-norm values through kan_conv_fwd_split, or None when the stage is out of its scope (the host conditions of `_split_bwd_weights`,
+    then `kan_split_supported`).  The cut weights are cached per weight pair on the scheme of `_SPLIT_BWD_CACHE`: ONE buffer, re-cut in place when a version
+    stamp or the epoch moved and, under `always_pack` (a recorded step), unconditionally; the entry goes when a weight tensor dies."""
+    if spec.groups != 1 or not spec.has_base or xn is not None or phases is not None or x.dim() != 4 or spec.first or spec.w_layout == W_IOD:
         return None
     lib = L.load()
     wb, ws = w_base[0], w_basis[0]
     geom, basis, _ = _plan_cached(*_plan_key(spec, x.shape, ws.shape[0]))
-    if not lib.kan_split_supported(C.byref(geom), C.byref(basis)):
+    nbytes = lib.kan_split_weight_bytes(C.byref(geom), C.byref(basis)) if lib.kan_split_supported(C.byref(geom), C.byref(basis)) else 0
+    if not nbytes:
         return None
     key = (wb.data_ptr(), ws.data_ptr(), x.device.index)
     stamps = (_owner(wb)._version, _owner(ws)._version, _EPOCH)
     ent = _SPLIT_CACHE.get(key)
-    wc = ent[1] if ent is not None and ent[0] == stamps else None
-    z, wc = kan_conv_fwd_split(spec, x, wb, ws, wc)
+    if ent is None:                                     # drop the entry when a weight tensor dies: another model's weights may get the same addresses and stamps
+        for o in (_owner(wb), _owner(ws)):
+            weakref.finalize(o, _SPLIT_CACHE.pop, key, None)
+    wc = ent[1] if ent is not None and ent[1].numel() == nbytes else None
+    if wc is None or ent[0] != stamps or _ALWAYS_PACK:
+        with torch.cuda.device(x.device):
+            if wc is None:
+                wc = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+            L.check(lib.kan_split_pack_weights(_ptr(wb), _ptr(ws), C.c_void_p(wc.data_ptr()), C.byref(geom), C.byref(basis), _stream(x)), "kan_split_pack_weights")
     _SPLIT_CACHE[key] = (stamps, wc)
     _SPLIT_CACHE.move_to_end(key)
     while len(_SPLIT_CACHE) > 16:
         _SPLIT_CACHE.popitem(last=False)
-    return z.unsqueeze(0)
+    return kan_conv_fwd_split(spec, x, wb, ws, wc)[0]
+
+
+def _split_fwd_keeps(spec: ConvSpec, x: torch.Tensor, w_base, w_basis, exact_x: bool, exact_w: bool):
+    """(wd, x_pm, plan): what a split-precision forward hands an EXACT backward, without the exact forward launch -- the bwd-data weight layout from `_pack`
+    when an exact input gradient will run, the position-major x where the plan wants it when an exact weight gradient will.  With both gradients split
+    (or not needed) nothing is packed."""
+    plan_key = _plan_key(spec, x.shape, w_basis[0].shape[0])
+    geom, basis, plan = _plan_cached(*plan_key)
+    wd = x_pm = None
+    if exact_x:
+        _, wd = _pack(L.load(), spec, geom, basis, plan, plan_key, w_base, w_basis, True, None, x.device, _stream(x))      # (B-spline: no device table)
+    if exact_w and plan.x_pm_wanted:
+        x_pm = _position_major(x, 0, x.shape[1])
+    return wd, x_pm, plan
 
 
 _SPLIT_BWD_DATA = False
@@ -459,6 +501,14 @@ def split_precision_backward_weight():
 def split_precision_backward():
     """`split_precision_backward_data` and `split_precision_backward_weight` at once: the whole backward of the layers in scope."""
     with split_precision_backward_data(), split_precision_backward_weight():
+        yield
+
+
+@contextlib.contextmanager
+def split_precision_training():
+    """`split_precision_forward`, `split_precision_backward_data` and `split_precision_backward_weight` at once: all three conv launches of the layers in
+    scope, for a training step run inside (`train.train_step(..., split_precision=True)`).  `split_precision_inference` is a switch of its own."""
+    with split_precision_forward(), split_precision_backward_data(), split_precision_backward_weight():
         yield
 
 
@@ -735,8 +785,9 @@ def _is_depthwise(spec: ConvSpec, x, w_basis) -> bool:
 
 
 class _KanConv(torch.autograd.Function):
-    """z = conv stage.  args: spec, x, xn (or None: the basis reads x), phases (or None), *[w_base_g...], *[w_basis_g...]
+    """z = conv stage.  args: spec, split, x, xn (or None: the basis reads x), phases (or None), *[w_base_g...], *[w_basis_g...]
 
+    `split`: run the forward in split precision where `kan_conv_fwd_split` takes it (`split_precision_forward`); the backward gets what an exact one needs.
     `xn`: a second input -- x feeds the base branch (a host-applied base activation: x = act(input)), xn the basis.
     `phases`: the parameter table of a basis with trainable per-channel parameters, [Cg, 2, n] (phase_low, phase_high per channel) for ReLU-KAN
     (relu_kan_layers.py:118-136), [n] recurrence coefficients for Gram.
@@ -745,7 +796,7 @@ class _KanConv(torch.autograd.Function):
     i.e. the weight-gradient kernel run on the parameter-derivative planes, contracted with the weights."""
 
     @staticmethod
-    def forward(ctx, spec: ConvSpec, x, xn, phases, *weights):
+    def forward(ctx, spec: ConvSpec, split: bool, x, xn, phases, *weights):
         x = _require(x, "x")
         xn = _require(xn, "xn") if xn is not None else None
         weights = [_require(w, "weight") for w in weights]
@@ -760,12 +811,17 @@ class _KanConv(torch.autograd.Function):
             want = (x.shape[1] // spec.groups, 2, spec.n_basis) if spec.kind == L.BASIS_RELU else (spec.n_basis,)
             if tuple(phases.shape) != want:
                 raise L.KanConvError(f"parameter table {tuple(phases.shape)} != {want} for basis kind {spec.kind}")
-        need_dgrad = bool(ctx.needs_input_grad[1] or (xn is not None and ctx.needs_input_grad[2]))
+        need_dgrad = bool(ctx.needs_input_grad[2] or (xn is not None and ctx.needs_input_grad[3]))         # (0: spec, 1: split, 2: x, 3: xn, 4: phases, 5...: weights)
+        need_w = any(ctx.needs_input_grad[5:])
         with torch.cuda.device(x.device):
-            z, (wd, x_pm), geom, _, plan = _conv_forward(spec, x, xn, w_base, w_basis, need_dgrad, phases)
-            z = _sum_slabs(z, geom.B, z.shape[2], geom.Ho * geom.Wo)
             wcd = _split_bwd_weights(spec, x, xn, phases, w_base, w_basis, need_dgrad)
-            ctx.wsplit = _split_bwd_weight_stage(spec, x, xn, phases, w_basis, any(ctx.needs_input_grad[4:]))
+            ctx.wsplit = _split_bwd_weight_stage(spec, x, xn, phases, w_basis, need_w)
+            z = _split_stage(spec, x, xn, phases, w_base, w_basis) if split else None
+            if z is not None:                            # opt-in split-precision forward: one slab; the backward is exact unless its contexts are on too
+                wd, x_pm, _ = _split_fwd_keeps(spec, x, w_base, w_basis, need_dgrad and wcd is None, need_w and not ctx.wsplit)
+            else:
+                z, (wd, x_pm), geom, _, plan = _conv_forward(spec, x, xn, w_base, w_basis, need_dgrad, phases)
+                z = _sum_slabs(z, geom.B, z.shape[2], geom.Ho * geom.Wo)
         ctx.spec = spec
         # the basis weights are kept only for the parameter gradient (their version counters are then checked in the backward)
         kept_w = {f"w_basis{g}": w for g, w in enumerate(w_basis)} if phases is not None else {}
@@ -777,8 +833,8 @@ class _KanConv(torch.autograd.Function):
         spec, G = ctx.spec, ctx.spec.groups
         x, xn, phases, wd, x_pm, wcd, *w_basis = _saved(ctx, "x", "xn", "phases", "wd", "x_pm", "wcd", *(f"w_basis{g}" for g in range(G)))
         packed = (wd, x_pm)
-        need_x, need_xn = ctx.needs_input_grad[1], xn is not None and ctx.needs_input_grad[2]
-        need_p, need_w = ctx.needs_input_grad[3], any(ctx.needs_input_grad[4:])
+        need_x, need_xn = ctx.needs_input_grad[2], xn is not None and ctx.needs_input_grad[3]
+        need_p, need_w = ctx.needs_input_grad[4], any(ctx.needs_input_grad[5:])
         dz = dz.contiguous()
         dph = None
         with torch.cuda.device(x.device):
@@ -804,7 +860,7 @@ class _KanConv(torch.autograd.Function):
                     dph = torch.zeros_like(phases)
                     for mode in range(1, n - 1):
                         dph[mode + 1] = factor(mode).sum()
-        return (None, dx if need_x else None, dxn if need_xn else None, dph) + _flat_grads(spec, dwb, dws)
+        return (None, None, dx if need_x else None, dxn if need_xn else None, dph) + _flat_grads(spec, dwb, dws)
 
 
 def _cat(ts: Sequence[Optional[torch.Tensor]]) -> Optional[torch.Tensor]:
@@ -922,7 +978,8 @@ def _norm_bwd(dy, z, mean, rstd, gamma, beta, slope, pidx, groups: int = 1, pool
 class _KanConvInPrelu(torch.autograd.Function):
     """y = [MaxPool2d]([PReLU](InstanceNorm(conv stage))), or BatchNorm in its place.
     args: spec, eps, use_affine, use_prelu, pool, split, bn, x, *[w_base_g], *[w_basis_g], *[gamma_g], *[beta_g], *[prelu_g]
-    `split`: run the conv stage in split precision where `kan_conv_fwd_split` takes it (inference only: nothing is kept for a backward).
+    `split`: run the conv stage in split precision where `kan_conv_fwd_split` takes it (`split_precision_inference` under no_grad, `split_precision_forward`
+    in any grad mode); the backward gets what an exact one needs (`_split_fwd_keeps`).
     `bn`: None, or the BatchStats of a BatchNorm tail (running buffers of all groups concatenated)."""
 
     @staticmethod
@@ -939,14 +996,15 @@ class _KanConvInPrelu(torch.autograd.Function):
         if use_prelu and any(p.numel() != 1 for p in prelus):
             raise L.KanConvError("only scalar-slope PReLU (nn.PReLU()) is supported, as in kan_layers.py:182")
         with torch.cuda.device(x.device):
-            zs = _split_stage(spec, x, w_base, w_basis) if split else None
-            if zs is not None:                           # opt-in inference mode (split_precision_inference): one slab
-                wd = x_pm = None
-                plan = _plan_cached(*_plan_key(spec, x.shape, zs.shape[2] // G))[2]
+            need_x, need_w = bool(ctx.needs_input_grad[7]), any(ctx.needs_input_grad[8:8 + nw])
+            wcd = _split_bwd_weights(spec, x, None, None, w_base, w_basis, need_x)
+            ctx.wsplit = _split_bwd_weight_stage(spec, x, None, None, w_basis, need_w)
+            zs = _split_stage(spec, x, None, None, w_base, w_basis) if split else None
+            if zs is not None:                           # opt-in split-precision forward (split_precision_inference / split_precision_forward): one slab
+                zs = zs.unsqueeze(0)
+                wd, x_pm, plan = _split_fwd_keeps(spec, x, w_base, w_basis, need_x and wcd is None, need_w and not ctx.wsplit)
             else:
-                zs, (wd, x_pm), _, _, plan = _conv_forward(spec, x, None, w_base, w_basis, bool(ctx.needs_input_grad[7]))
-            wcd = _split_bwd_weights(spec, x, None, None, w_base, w_basis, bool(ctx.needs_input_grad[7]))
-            ctx.wsplit = _split_bwd_weight_stage(spec, x, None, None, w_basis, any(ctx.needs_input_grad[8:8 + nw]))
+                zs, (wd, x_pm), _, _, plan = _conv_forward(spec, x, None, w_base, w_basis, need_x)
             # all groups in one launch: per-channel gamma/beta concatenated, one PReLU slope per Og channels
             gamma, beta, slope = _cat(gammas), _cat(betas), _cat(prelus)
             y, z, mean, rstd, pidx = _norm_fwd(zs, plan.fwd_slab_elems, gamma, beta, slope, eps, G, pool, bn=bn)
@@ -1084,14 +1142,15 @@ def _apply(stage, spec: ConvSpec, x, xn, w_base, w_basis, extra=()) -> torch.Ten
 
 def kan_conv(spec: ConvSpec, x: torch.Tensor, xn: Optional[torch.Tensor], w_base: Sequence[torch.Tensor],
              w_basis: Sequence[torch.Tensor]) -> torch.Tensor:
-    return _apply(lambda a, b, *ws: _KanConv.apply(spec, a, b, None, *ws), spec, x, xn, w_base, w_basis)
+    split = _SPLIT_FWD                                  # opt-in split-precision forward: decided here, where the caller's flags are visible; each run of images decides its scope
+    return _apply(lambda a, b, *ws: _KanConv.apply(spec, split, a, b, None, *ws), spec, x, xn, w_base, w_basis)
 
 
 def kan_conv_phased(spec: ConvSpec, x: torch.Tensor, phases: torch.Tensor, w_base: Sequence[torch.Tensor],
                     w_basis: Sequence[torch.Tensor], xn: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Conv stage of a basis with trainable parameters held in device memory, differentiable in them: ReLU-KAN
     (`phases` = [channels per group, 2, n_basis]: low, high) or Gram (`phases` = [n_basis] recurrence coefficients c_k)."""
-    return _apply(lambda a, b, *ws: _KanConv.apply(spec, a, b, phases, *ws), spec, x, xn, w_base, w_basis)
+    return _apply(lambda a, b, *ws: _KanConv.apply(spec, False, a, b, phases, *ws), spec, x, xn, w_base, w_basis)
 
 
 def pool_fusable(pool, ho: int, wo: int, batchnorm: bool = False) -> bool:
@@ -1124,7 +1183,8 @@ def kan_conv_in_prelu(spec: ConvSpec, x: torch.Tensor, w_base: Sequence[torch.Te
     pool = _norm_pool(pool)
     if bn is not None and not fits_one_launch(spec, x, w_basis):
         raise L.KanConvError("a BatchNorm tail cannot be cut into runs of images: run kan_conv, then batch_norm")
-    split = _SPLIT_INFERENCE and not torch.is_grad_enabled()            # opt-in inference mode: decided where the caller's grad mode is visible
+    # opt-in split-precision forward, decided where the caller's grad mode and flags are visible: the inference switch under no_grad only, the forward switch always
+    split = _SPLIT_FWD or (_SPLIT_INFERENCE and not torch.is_grad_enabled())
     aff = gammas is not None
     extra = (list(gammas) + list(betas) if aff else []) + (list(prelus) if prelus is not None else [])
     return _apply(lambda a, _, *ps: _KanConvInPrelu.apply(spec, float(eps), aff, prelus is not None, pool, split, bn, a, *ps),
@@ -1133,7 +1193,7 @@ def kan_conv_in_prelu(spec: ConvSpec, x: torch.Tensor, w_base: Sequence[torch.Te
 
 def kan_conv_fwd_split(spec: ConvSpec, x: torch.Tensor, w_base: torch.Tensor, w_basis: torch.Tensor, wc: Optional[torch.Tensor] = None):
     """OPT-IN split-precision conv stage (forward only, no autograd; kanconv.h `kan_conv_fwd_split`): the fp32 result of `kan_conv` to ~4e-6 of its largest
-    element, through 3 x bf16 pieces and six bf16 MFMA products per k-block.  Never used by the layers; scope: default B-spline spec on 8x8 or 16x16 planes, 3x3 /
+    element, through 3 x bf16 pieces and six bf16 MFMA products per k-block.  The layers take it only inside `split_precision_inference` / `split_precision_forward`; scope: default B-spline spec on 8x8 or 16x16 planes, 3x3 /
     stride 1 / pad 1, one group, C % 8 == 0, O % 128 == 0, even batch on 8x8 (raises KanConvError otherwise).  Returns (z, wc): pass `wc` back while the
     weights are unchanged to skip the cut (0.05 ms at 256 -> 256)."""
     lib = L.load()

@@ -9,6 +9,7 @@ the launch stream: the only host synchronisation is the once-per-epoch read of t
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Iterable, List, Optional, Tuple
 
 import torch
@@ -18,16 +19,23 @@ from .optim import FusedAdamW
 
 
 def train_step(model: nn.Module, data: torch.Tensor, target: torch.Tensor, optimizer: torch.optim.Optimizer,
-               criterion: Optional[nn.Module] = None, reducer=None) -> torch.Tensor:
-    """One batch: returns the (detached, device-resident) loss."""
+               criterion: Optional[nn.Module] = None, reducer=None, split_precision: bool = False) -> torch.Tensor:
+    """One batch: returns the (detached, device-resident) loss.  ``split_precision``: OPT-IN, the forward and backward of this step run inside
+    ``ops.split_precision_training()`` (the conv launches of the layers in its scope in split precision; everything else exact)."""
     criterion = criterion if criterion is not None else nn.CrossEntropyLoss()
     optimizer.zero_grad()
-    loss = criterion(model(data), target)
-    loss.backward()
+    with _split_context(split_precision):
+        loss = criterion(model(data), target)
+        loss.backward()
     if reducer is not None:
         reducer.finish()
     optimizer.step()
     return loss.detach()
+
+
+def _split_context(on: bool):
+    from . import ops
+    return ops.split_precision_training() if on else contextlib.nullcontext()
 
 
 class GraphedStep:
@@ -37,7 +45,7 @@ class GraphedStep:
     torch's own; a replay costs one graph launch instead of the host's per-kernel work.  That pays where the step is launch-bound -- small models and
     single layers (BASELINE config 2: 0.23 ms replayed against 0.43-0.48 ms eager, bit-identical); KAN-VGG11 at bs 256 keeps the GPU busy either way.
     The weight packs are recorded unconditionally (``ops.always_pack``): the replay reads the weights as they are at replay time, so an optimizer may
-    update them in place between replays.  Keep the optimizer step OUTSIDE the graph (AdamW's bias correction takes the step count as a kernel
+    update them in place between replays.  ``split_precision=True`` (OPT-IN) warms up and records inside ``ops.split_precision_training()``.  Keep the optimizer step OUTSIDE the graph (AdamW's bias correction takes the step count as a kernel
     argument) and do not call ``zero_grad`` between replays: the recorded backward assigns ``p.grad`` (static tensors) rather than accumulating.
 
         step = GraphedStep(model, example_data, example_target)
@@ -47,7 +55,7 @@ class GraphedStep:
     """
 
     def __init__(self, model: nn.Module, example_data: torch.Tensor, example_target: torch.Tensor, criterion: Optional[nn.Module] = None,
-                 warmup: int = 3):
+                 warmup: int = 3, split_precision: bool = False):
         from . import ops
         if not example_data.is_cuda:
             raise ValueError("GraphedStep needs device tensors")
@@ -56,13 +64,13 @@ class GraphedStep:
         self.data, self.target = example_data.clone(), example_target.clone()
         side = torch.cuda.Stream(device=example_data.device)
         side.wait_stream(torch.cuda.current_stream(example_data.device))
-        with torch.cuda.stream(side):                      # warm-up off the capture stream: plans, workspaces, torch's lazy initialisations
+        with torch.cuda.stream(side), _split_context(split_precision):      # warm-up off the capture stream: plans, workspaces, torch's lazy initialisations
             for _ in range(max(1, warmup)):
                 self._eager()
         torch.cuda.current_stream(example_data.device).wait_stream(side)
         self.graph = torch.cuda.CUDAGraph()
         self.model.zero_grad(set_to_none=True)             # recorded backward then ASSIGNS the gradients (tensors of the graph's pool)
-        with ops.always_pack(), torch.cuda.graph(self.graph):
+        with _split_context(split_precision), ops.always_pack(), torch.cuda.graph(self.graph):
             self.loss = self._eager()
 
     def _eager(self) -> torch.Tensor:
@@ -82,9 +90,9 @@ class GraphedStep:
 
 def train_model_generic(model: nn.Module, train_batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], device="cuda",
                         learning_rate: float = 1e-3, weight_decay: float = 1e-4, gamma: float = 0.8, epochs: int = 15,
-                        reducer=None) -> List[float]:
+                        reducer=None, split_precision: bool = False) -> List[float]:
     """generic_train.py:19-30 without the dataset / metric / checkpoint plumbing; returns the average loss per epoch.
-    ``train_batches`` is re-iterated every epoch (a list of (data, target) pairs or a DataLoader)."""
+    ``train_batches`` is re-iterated every epoch (a list of (data, target) pairs or a DataLoader).  ``split_precision``: handed to every ``train_step``."""
     model.to(device).train()
     optimizer = FusedAdamW(model.parameters(), lr=learning_rate, weight_decay=weight_decay)
     scheduler = torch.optim.lr_scheduler.ExponentialLR(optimizer, gamma=gamma)
@@ -93,7 +101,7 @@ def train_model_generic(model: nn.Module, train_batches: Iterable[Tuple[torch.Te
     for _ in range(epochs):
         total, n = torch.zeros((), device=device), 0
         for data, target in train_batches:
-            total += train_step(model, data.to(device), target.to(device), optimizer, criterion, reducer)
+            total += train_step(model, data.to(device), target.to(device), optimizer, criterion, reducer, split_precision)
             n += 1
         history.append(float(total) / max(n, 1))
         scheduler.step()
