@@ -114,7 +114,12 @@ SIGNATURES = {
     "kan_wav_route": (_I, [C.POINTER(KanWavGeom), C.POINTER(KanWavRoute)]),
     "kan_adamw_step": (_I, [_P, _P, _P, _P, _LL, _D, _D, _D, _D, _D, _I, _F, _P]),
     "kan_adamw_step_segments": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _D, _D, _D, _D, _D, _I, _F, _P]),
+    "kan_xent_workspace_bytes": (_LL, [_I]),
+    "kan_xent_metrics_bytes": (_LL, [_I]),
+    "kan_xent_fwd": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "kan_xent_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _P]),
 }
+XENT_HEADER_WORDS = 8                                   # metrics buffer: [correct, samples, batches, bad_target, loss_sum (double), 3 unused], tp[C], pred[C], true[C]
 
 _lib: Optional[C.CDLL] = None
 

@@ -4,6 +4,7 @@
 //   kan_direct.hip  band kernels: layers of few input channels (first layers: 3 -> 64) and layers whose output count fills no 128-wide
 //                   tile (64 -> 192), any kernel size / stride / dilation / padding
 //   kan_split.hip   opt-in split-precision forward
+//   kan_loss.hip    cross-entropy loss, its gradient and the counters of the test metrics
 #pragma once
 #include <type_traits>
 #include "kanconv.h"

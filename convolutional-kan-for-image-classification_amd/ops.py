@@ -10,6 +10,8 @@ Two differentiable entry points, both launching only hand-written HIP kernels:
 * ``instance_norm``      -- InstanceNorm2d alone (fast_kan_layers.py:106, norm on the input).
 * ``batch_norm``         -- BatchNorm2d alone; ``kan_conv_in_prelu(..., bn=)`` is the fused tail of a layer built with
                             ``norm_layer=BatchNorm2d`` (train.py:67-68: the default of the reference's training script).
+* ``cross_entropy``      -- the criterion (generic_train.py:26) with the counters of the test metrics (evaluations.py:131-151)
+                            accumulated on the device.
 
 All tensors are fp32, NCHW, on a ROCm device.  Groups (kan_layers.py:249-258 loops over them in
 Python) run inside the SAME launches (KanGeom.groups; the group index is folded into the grid):
@@ -1280,3 +1282,48 @@ def batch_norm(x: torch.Tensor, gamma: Optional[torch.Tensor] = None, beta: Opti
     """BatchNorm2d over NCHW with this rank's batch statistics (F.batch_norm's semantics: the running buffers are updated in place when
     training, used when not; without them the batch statistics serve both modes).  Raises ValueError for one value per channel in training."""
     return _InstanceNorm.apply(x, gamma, beta, float(eps), BatchStats(running_mean, running_var, float(momentum), bool(training)))
+
+
+# --------------------------------------------------------------------------------------- cross-entropy loss and test metrics
+class _CrossEntropy(torch.autograd.Function):
+    """loss = mean_b (lse[b] - logits[b, target[b]]) on the kernels of csrc/kan_loss.hip (generic_train.py:26's criterion, mean reduction);
+    ``metrics``: None or the int64 counter buffer of ``ClassMetrics``, which the same launches add to.  The upstream gradient stays on the device."""
+
+    @staticmethod
+    def forward(ctx, logits, target, metrics):
+        lib = L.load()
+        logits = _require(logits, "logits")
+        if torch.cuda.is_current_stream_capturing():
+            raise L.KanConvError("cross_entropy is not recorded into a HIP graph (train.GraphedStep): keep torch's criterion inside a recorded step")
+        if logits.dim() != 2 or target.shape != logits.shape[:1]:
+            raise L.KanConvError(f"cross_entropy takes logits [B, C] and target [B], got {tuple(logits.shape)} and {tuple(target.shape)}")
+        if target.device != logits.device or target.dtype != torch.int64:
+            raise L.KanConvError(f"target must be int64 on {logits.device}, got {target.dtype} on {target.device}")
+        target = target.contiguous()
+        B, Cn = logits.shape
+        if metrics is not None and (metrics.device != logits.device or metrics.dtype != torch.int64 or not metrics.is_contiguous()
+                                    or metrics.numel() * 8 != lib.kan_xent_metrics_bytes(Cn)):
+            raise L.KanConvError(f"metrics buffer does not fit {Cn} classes on {logits.device}: build it with ClassMetrics({Cn}, device)")
+        loss = torch.empty((), device=logits.device, dtype=torch.float32)
+        lse = torch.empty((B,), device=logits.device, dtype=torch.float32)
+        ws = torch.empty((max(int(lib.kan_xent_workspace_bytes(B)), 4) // 4,), device=logits.device, dtype=torch.int32)
+        L.check(lib.kan_xent_fwd(_ptr(logits), _ptr(target), B, Cn, _ptr(loss), _ptr(lse), _ptr(metrics), _ptr(ws), _stream(logits)), "kan_xent_fwd")
+        ctx.save_for_backward(logits, target, lse)
+        return loss
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = L.load()
+        logits, target, lse = ctx.saved_tensors
+        g = _require(g, "grad of the loss").reshape(1)
+        dlogits = torch.empty_like(logits)
+        L.check(lib.kan_xent_bwd(_ptr(logits), _ptr(target), _ptr(lse), _ptr(g), _ptr(dlogits), logits.shape[0], logits.shape[1], _stream(logits)),
+                "kan_xent_bwd")
+        return dlogits, None, None
+
+
+def cross_entropy(logits: torch.Tensor, target: torch.Tensor, metrics=None) -> torch.Tensor:
+    """Mean cross-entropy of fp32 ``logits`` [B, C] against int64 ``target`` [B] (a device scalar).  ``metrics``: a ``ClassMetrics`` (or its
+    buffer); every call then adds this batch's loss, predictions (lowest index among the maxima, as torch.max) and per-class counts to it on
+    the device -- no host read.  A target outside [0, C) adds nothing, gets a zero gradient row and is reported by ``ClassMetrics.result()``."""
+    return _CrossEntropy.apply(logits, target, getattr(metrics, "buffer", metrics))

@@ -5,7 +5,10 @@ Mirrors the reference's loop: ``optim.AdamW(lr, weight_decay)`` + ``ExponentialL
 scheduler step per epoch (evaluations.py: train_and_test_models), with the optimizer replaced by ``FusedAdamW`` and, under
 ``torch.distributed``, the gradient mean taken by ``BucketedGradReducer`` between backward and step.  Everything stays on
 the launch stream: the only host synchronisation is the once-per-epoch read of the accumulated loss (the reference reads
-``loss.item()`` every batch).  Datasets, metrics, checkpoints and plots stay out of scope (section 8: control plane).
+``loss.item()`` every batch).  ``evaluate`` and ``train_and_test_models`` add the second half of that loop (evaluations.py:81-247: test loss,
+accuracy, macro precision / recall / F1 after every epoch) under the same rule: the loss and the counting run in the kernels of
+csrc/kan_loss.hip and the counters are read once per evaluation.  Datasets, checkpoints, early stopping and plots stay out of scope
+(section 8: control plane).
 """
 from __future__ import annotations
 
@@ -47,6 +50,8 @@ class GraphedStep:
     The weight packs are recorded unconditionally (``ops.always_pack``): the replay reads the weights as they are at replay time, so an optimizer may
     update them in place between replays.  ``split_precision=True`` (OPT-IN) warms up and records inside ``ops.split_precision_training()``.  Keep the optimizer step OUTSIDE the graph (AdamW's bias correction takes the step count as a kernel
     argument) and do not call ``zero_grad`` between replays: the recorded backward assigns ``p.grad`` (static tensors) rather than accumulating.
+    The criterion inside a recorded step is torch's: ``convkan_amd.CrossEntropyLoss`` (the device-side counters of ``ClassMetrics``) is refused here --
+    recording it is not supported yet; ``train_step`` takes it.
 
         step = GraphedStep(model, example_data, example_target)
         for data, target in batches:
@@ -57,6 +62,9 @@ class GraphedStep:
     def __init__(self, model: nn.Module, example_data: torch.Tensor, example_target: torch.Tensor, criterion: Optional[nn.Module] = None,
                  warmup: int = 3, split_precision: bool = False):
         from . import ops
+        from .loss import CrossEntropyLoss
+        if isinstance(criterion, CrossEntropyLoss):
+            raise NotImplementedError("GraphedStep does not record convkan_amd.CrossEntropyLoss yet: keep torch's criterion in a recorded step")
         if not example_data.is_cuda:
             raise ValueError("GraphedStep needs device tensors")
         self.model = model
@@ -106,3 +114,55 @@ def train_model_generic(model: nn.Module, train_batches: Iterable[Tuple[torch.Te
         history.append(float(total) / max(n, 1))
         scheduler.step()
     return history
+
+
+def evaluate(model: nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], device="cuda", metrics=None) -> dict:
+    """evaluations.py:81-153 (``test``) without its per-batch host reads: the model in ``eval()`` mode under ``no_grad``, one
+    ``ops.cross_entropy(model(data), target, metrics)`` per batch -- loss, torch.max's prediction and the per-class counts stay on the device --
+    and ONE read at the end.  Returns ``ClassMetrics.result()``: loss (the mean of the batch means, evaluations.py:150), accuracy, macro
+    precision / recall / f1 (scikit-learn's, ``zero_division=0``), samples, batches.  ``metrics``: a ``ClassMetrics`` to reuse (it is reset
+    first); by default one is made for the width of the first batch's logits.  The model's training mode is restored.  Inference timing is not
+    carried over."""
+    from . import ops
+    from .loss import ClassMetrics
+    was_training = model.training
+    model.eval()
+    if metrics is not None:
+        metrics.reset()
+    try:
+        with torch.no_grad():
+            for data, target in batches:
+                out = model(data.to(device))
+                if metrics is None:
+                    metrics = ClassMetrics(out.shape[1], out.device)
+                ops.cross_entropy(out, target.to(device), metrics)
+    finally:
+        model.train(was_training)
+    if metrics is None:
+        raise ValueError("evaluate: no batches")
+    return metrics.result()
+
+
+def train_and_test_models(model: nn.Module, train_batches: Iterable[Tuple[torch.Tensor, torch.Tensor]],
+                          test_batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], optimizer: torch.optim.Optimizer, scheduler=None,
+                          epochs: int = 15, reducer=None, split_precision: bool = False, criterion: Optional[nn.Module] = None):
+    """evaluations.py:156-247: per epoch the ``train_step`` loop (one read of the accumulated loss), then ``evaluate`` (one read of the
+    counters), then ``scheduler.step()``.  Runs on the device the model is on.  Returns the first seven lists of evaluations.py:247: train loss,
+    test loss, accuracy, precision, recall, F1 and the learning rate each epoch started with.  Checkpoints (``torch.save``), early stopping
+    (``patience``), plots and timing are not carried over."""
+    device = next(model.parameters()).device
+    train_loss, test_loss, accuracy, precision, recall, f1, rates = [], [], [], [], [], [], []
+    for _ in range(epochs):
+        rates.append(optimizer.param_groups[0]["lr"])
+        model.train()
+        total, n = torch.zeros((), device=device), 0
+        for data, target in train_batches:
+            total += train_step(model, data.to(device), target.to(device), optimizer, criterion, reducer, split_precision)
+            n += 1
+        train_loss.append(float(total) / max(n, 1))
+        r = evaluate(model, test_batches, device)
+        for history, key in ((test_loss, "loss"), (accuracy, "accuracy"), (precision, "precision"), (recall, "recall"), (f1, "f1")):
+            history.append(r[key])
+        if scheduler is not None:
+            scheduler.step()
+    return train_loss, test_loss, accuracy, precision, recall, f1, rates

@@ -437,6 +437,30 @@ int kan_adamw_step_segments(float* p, float* m, float* v, const unsigned long lo
                             const int* chunk_seg, const int* chunk_start, const float* seg_bias, int n_chunks, int chunk_elems, double lr,
                             double beta1, double beta2, double eps, double weight_decay, int step, float grad_scale, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- cross-entropy loss and test metrics
+ * The criterion of the training script (generic_train.py:26 `nn.CrossEntropyLoss()`, called at evaluations.py:61 and :131: mean reduction, no
+ * class weights, no ignore_index, no label smoothing) and what the evaluation loop collects per batch (evaluations.py:131-136: the batch loss,
+ * torch.max's prediction, the correct count; :139-140, :146-151: every target and prediction, for scikit-learn's macro precision / recall / F1)
+ * -- without the reference's host reads per batch.  logits: fp32 [B][C] row-major;  target: int64 [B].
+ *   forward    loss[0] = mean_b (lse[b] - logits[b][target[b]]),  lse[b] = log sum_c exp(logits[b][c]) (kept for the backward).  The batch mean is
+ *              summed in double in an order that depends on B alone, and a row's lse on that row alone: the same inputs give the same bits.
+ *   metrics    NULL, or a zero-initialised buffer of 8-byte words that every forward call adds to:
+ *                [0] correct  [1] samples  [2] batches  [3] bad_target (rows with a target outside [0, C); sticky)  [4] loss_sum, a DOUBLE: the sum
+ *                of the batch-mean losses (evaluations.py:132, :150 average batch means)  [5..7] unused
+ *                [8 ..) tp[C], pred[C], true[C]: per class, the rows predicted and labelled c / predicted c / labelled c
+ *              The prediction of a row is the LOWEST index among its maxima (torch.max).  Integer counters: exact whatever the order.
+ *   bad rows   a target outside [0, C) never indexes anything: the row adds 0 to the loss (the mean still divides by B), counts in no counter
+ *              but bad_target, and gets a zero gradient row.  The caller reads bad_target when it reads the counters, not per batch.
+ *   backward   dlogits[b][c] = grad_loss[0] * (exp(logits[b][c] - lse[b]) - [c == target[b]]) / B;  grad_loss is a DEVICE scalar.
+ *   workspace  scratch of the forward (the row losses and row states), 4-byte aligned.
+ * Null pointers (metrics excepted), B < 1 and C < 1 are refused by host arithmetic before any launch; the two size functions return 0 for them. */
+long long kan_xent_workspace_bytes(int B);
+long long kan_xent_metrics_bytes(int C);
+int kan_xent_fwd(const float* logits, const long long* target, int B, int C, float* loss, float* lse, void* metrics /* nullable */,
+                 void* workspace, void* stream);
+int kan_xent_bwd(const float* logits, const long long* target, const float* lse, const float* grad_loss /* device */, float* dlogits,
+                 int B, int C, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- Wav-KAN wavelet stage
  * u[b, o, ho, wo] = sum_{c, r, t} w[o, c, r, t] * psi((x[b, c, hi, wi] - trans[o, c]) / scale[o, c]),  zero padding applied to the
  * wavelet values.  Replaces WaveletConvND / WaveletConvNDFast / WaveletConvNDFastPlusOne .forward up to (not including) the 1x1
