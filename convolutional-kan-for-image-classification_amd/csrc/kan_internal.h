@@ -5,6 +5,7 @@
 //                   tile (64 -> 192), any kernel size / stride / dilation / padding
 //   kan_split.hip   opt-in split-precision forward
 //   kan_loss.hip    cross-entropy loss, its gradient and the counters of the test metrics
+//   kan_feed.hip    batches from a device-resident uint8 dataset: gather, crop, flip, convert, normalise
 #pragma once
 #include <type_traits>
 #include "kanconv.h"

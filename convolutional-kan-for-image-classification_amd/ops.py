@@ -12,6 +12,8 @@ Two differentiable entry points, both launching only hand-written HIP kernels:
                             ``norm_layer=BatchNorm2d`` (train.py:67-68: the default of the reference's training script).
 * ``cross_entropy``      -- the criterion (generic_train.py:26) with the counters of the test metrics (evaluations.py:131-151)
                             accumulated on the device.
+* ``prepare_batch``      -- one batch from a device-resident uint8 dataset: gather, crop with zero padding, flip, ToTensor, Normalize
+                            (utils/dataloader.py:56-90) and the labels, in one launch.
 
 All tensors are fp32, NCHW, on a ROCm device.  Groups (kan_layers.py:249-258 loops over them in
 Python) run inside the SAME launches (KanGeom.groups; the group index is folded into the grid):
@@ -1327,3 +1329,66 @@ def cross_entropy(logits: torch.Tensor, target: torch.Tensor, metrics=None) -> t
     buffer); every call then adds this batch's loss, predictions (lowest index among the maxima, as torch.max) and per-class counts to it on
     the device -- no host read.  A target outside [0, C) adds nothing, gets a zero gradient row and is reported by ``ClassMetrics.result()``."""
     return _CrossEntropy.apply(logits, target, getattr(metrics, "buffer", metrics))
+
+
+# --------------------------------------------------------------------------------------- batches from a device-resident uint8 dataset
+def prepare_batch(images: torch.Tensor, table: torch.Tensor, out_hw, mean, std, labels: Optional[torch.Tensor] = None,
+                  channels_last: bool = True, out=None):
+    """One batch of a uint8 dataset that lives on the device, in one launch of csrc/kan_feed.hip and with no host read: the transforms of
+    utils/dataloader.py:56-90 (``RandomCrop(S, padding=p)``, ``RandomHorizontalFlip``, ``ToTensor``, ``Normalize``) and the DataLoader's batching.
+
+    ``images``: uint8 [N, H, W, C] (``channels_last``, CIFAR's layout) or [N, C, H, W] (SVHN's; MNIST's [N, H, W] counts as C = 1 either way);
+    ``table``: int32 [B, 4], rows (index, top, left, flip) with top / left in unpadded source coordinates (negative: zero padding of the raw
+    bytes, so a padded pixel comes out as (0 - mean) / std); ``out_hw``: (Ho, Wo); ``mean`` / ``std``: C floats; ``labels``: int64 [N] or None.
+    Returns (data fp32 [B, C, Ho, Wo], target int64 [B] or None).  ``out=(data, target)`` writes into given tensors (``GraphedStep``'s
+    ``step.data`` / ``step.target``) and returns them.  A row whose index is outside [0, N) gets an all-zero image and target -1
+    (``ClassMetrics.result()`` reports it).  No autograd: images carry no gradient."""
+    lib = L.load()
+    if not (isinstance(images, torch.Tensor) and isinstance(table, torch.Tensor)):
+        raise L.KanConvError("prepare_batch takes tensors for images and table")
+    if images.dtype != torch.uint8 or not images.is_contiguous():
+        raise L.KanConvError(f"images must be contiguous uint8, got {images.dtype}{'' if images.is_contiguous() else ', not contiguous'}")
+    if images.dim() == 3:
+        N, H, W = images.shape
+        Cn = 1
+    elif images.dim() == 4:
+        N, H, W, Cn = images.shape if channels_last else (images.shape[0], images.shape[2], images.shape[3], images.shape[1])
+    else:
+        raise L.KanConvError(f"images must be [N, H, W, C], [N, C, H, W] or [N, H, W], got {tuple(images.shape)}")
+    if min(N, H, W, Cn) < 1:
+        raise L.KanConvError(f"images are empty: {tuple(images.shape)}")
+    if Cn > 4:
+        raise L.KanConvError(f"at most 4 channels, got {Cn} ({'channels_last' if channels_last else 'channels first'} {tuple(images.shape)})")
+    limit = int(lib.kan_feed_max_image_bytes())
+    if H * W * Cn > limit:
+        raise L.KanConvError(f"an image of {H} x {W} x {Cn} = {H * W * Cn} bytes is above the {limit} bytes this kernel stages")
+    if table.device != images.device or table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != 4 or table.shape[0] < 1 \
+            or not table.is_contiguous():
+        raise L.KanConvError(f"table must be contiguous int32 [B, 4] on {images.device}, got {table.dtype} {tuple(table.shape)} on {table.device}")
+    B = table.shape[0]
+    Ho, Wo = (int(v) for v in out_hw)
+    if Ho < 1 or Wo < 1:
+        raise L.KanConvError(f"out_hw must be positive, got {(Ho, Wo)}")
+    mean, std = [float(v) for v in mean], [float(v) for v in std]
+    if len(mean) != Cn or len(std) != Cn:
+        raise L.KanConvError(f"mean and std must hold {Cn} values, got {len(mean)} and {len(std)}")
+    if labels is not None and (labels.device != images.device or labels.dtype != torch.int64 or labels.shape != (N,) or not labels.is_contiguous()):
+        raise L.KanConvError(f"labels must be contiguous int64 [{N}] on {images.device}, got {labels.dtype} {tuple(labels.shape)} on {labels.device}")
+    if not images.is_cuda:                                   # after the checks that need no device, so those speak on any tensor
+        raise L.KanConvError(f"images are on {images.device}: this path runs only on a ROCm device (MI355X); there is no CPU fallback")
+    if out is not None:
+        data, target = out
+        if data.device != images.device or data.dtype != torch.float32 or tuple(data.shape) != (B, Cn, Ho, Wo) or not data.is_contiguous():
+            raise L.KanConvError(f"out data must be contiguous float32 {(B, Cn, Ho, Wo)} on {images.device}, got {data.dtype} {tuple(data.shape)}")
+        if (target is None) != (labels is None):
+            raise L.KanConvError("out target is given exactly when labels are")
+        if target is not None and (target.device != images.device or target.dtype != torch.int64 or tuple(target.shape) != (B,)
+                                   or not target.is_contiguous()):
+            raise L.KanConvError(f"out target must be contiguous int64 {(B,)} on {images.device}, got {target.dtype} {tuple(target.shape)}")
+    else:
+        data = torch.empty((B, Cn, Ho, Wo), device=images.device, dtype=torch.float32)
+        target = torch.empty((B,), device=images.device, dtype=torch.int64) if labels is not None else None
+    fl = C.c_float * Cn
+    L.check(lib.kan_feed_batch(_ptr(images), _ptr(labels), _ptr(table), N, B, Cn, H, W, Ho, Wo, 1 if channels_last else 0, fl(*mean), fl(*std),
+                               _ptr(data), _ptr(target), _stream(images)), "kan_feed_batch")
+    return data, target

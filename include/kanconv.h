@@ -461,6 +461,31 @@ int kan_xent_fwd(const float* logits, const long long* target, int B, int C, flo
 int kan_xent_bwd(const float* logits, const long long* target, const float* lse, const float* grad_loss /* device */, float* dlogits,
                  int B, int C, void* stream);
 
+/* ---------------------------------------------------------------------------------------------- batches from a device-resident uint8 dataset
+ * The per-sample transforms of the loader's non-ImageNet branch (utils/dataloader.py:56-90: `RandomCrop(S, padding=p)`, `RandomHorizontalFlip`,
+ * `ToTensor`, `Normalize`, or the last two alone) and the batching of its DataLoader (:111-112), for a dataset that lives on the device as uint8:
+ * one launch per batch, no host read.  Reading dataset files, Resize / RandomResizedCrop / Grayscale (:26-54) and the random draws themselves
+ * (the caller makes the table) are not here.
+ *   images   uint8, N images of H x W x C: [N][H][W][C] (channels_last != 0; CIFAR) or [N][C][H][W] (channels_last == 0; SVHN, MNIST with C = 1)
+ *   labels   int64 [N], or NULL together with target
+ *   table    DEVICE int32 [B][4], one row (index, top, left, flip) per batch row
+ *   mean/std HOST float [C], C <= 4 (they travel as kernel arguments)
+ *   data     fp32 [B][C][Ho][Wo] contiguous:  data[b][c][y][x] = (float(v) / 255.0f - mean[c]) / std[c]  -- three correctly rounded fp32 operations in
+ *            that order, ToTensor's div and Normalize's sub_ and div_ -- with v the byte at (c, top + y, left + (flip ? Wo - 1 - x : x)) of image
+ *            `index`, and v = 0 outside [0, H) x [0, W).  top and left are in UNPADDED source coordinates and may be negative: torchvision pads the
+ *            uint8 image with 0, crops, flips, then converts, so a padded pixel is (0 - mean[c]) / std[c], not 0.  RandomCrop(32, padding=4) on
+ *            32 x 32 is top, left in [-4, 4]; a centre crop is top = (H - Ho) / 2; no crop is 0.
+ *   target   int64 [B]:  labels[index]
+ *   bad rows an index outside [0, N) is compared against the range before it addresses anything: the row's image is all 0.0f and its target -1,
+ *            which the loss kernels leave out and count in bad_target.
+ * Every output element has one writer and depends on its own table row alone: the same inputs give the same bits.  Null pointers (labels and
+ * target excepted, as a pair), N, B, C, H, W, Ho, Wo < 1, C > 4 and H * W * C above the size helper's value are refused by host arithmetic
+ * before any launch. */
+long long kan_feed_max_image_bytes(void);
+int kan_feed_batch(const unsigned char* images, const long long* labels /* nullable */, const int* table, long long N, int B, int C, int H, int W,
+                   int Ho, int Wo, int channels_last, const float* mean /* host */, const float* std /* host */, float* data,
+                   long long* target /* nullable with labels */, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- Wav-KAN wavelet stage
  * u[b, o, ho, wo] = sum_{c, r, t} w[o, c, r, t] * psi((x[b, c, hi, wi] - trans[o, c]) / scale[o, c]),  zero padding applied to the
  * wavelet values.  Replaces WaveletConvND / WaveletConvNDFast / WaveletConvNDFastPlusOne .forward up to (not including) the 1x1
