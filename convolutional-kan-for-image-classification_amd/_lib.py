@@ -120,6 +120,8 @@ SIGNATURES = {
     "kan_xent_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _P]),
     "kan_feed_max_image_bytes": (_LL, []),
     "kan_feed_batch": (_I, [_P, _P, _P, _LL, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
+    "kan_feed_resize_max_ksize": (_I, []),
+    "kan_feed_resize_batch": (_I, [_P, _P, _P, _LL] + [_I] * 10 + [_P, _I] * 4 + [_P, _P, _P, _P, _P]),
 }
 XENT_HEADER_WORDS = 8                                   # metrics buffer: [correct, samples, batches, bad_target, loss_sum (double), 3 unused], tp[C], pred[C], true[C]
 

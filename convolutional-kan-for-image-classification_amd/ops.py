@@ -14,6 +14,8 @@ Two differentiable entry points, both launching only hand-written HIP kernels:
                             accumulated on the device.
 * ``prepare_batch``      -- one batch from a device-resident uint8 dataset: gather, crop with zero padding, flip, ToTensor, Normalize
                             (utils/dataloader.py:56-90) and the labels, in one launch.
+* ``prepare_resized_batch`` -- the same for the loader's ImageNet branch (:26-54): Resize, a crop box, Resize of the box (PIL's 8-bit bilinear
+                            bytes), flip, Grayscale(3), ToTensor, Normalize, in one launch.
 
 All tensors are fp32, NCHW, on a ROCm device.  Groups (kan_layers.py:249-258 loops over them in
 Python) run inside the SAME launches (KanGeom.groups; the group index is folded into the grid):
@@ -1391,4 +1393,85 @@ def prepare_batch(images: torch.Tensor, table: torch.Tensor, out_hw, mean, std, 
     fl = C.c_float * Cn
     L.check(lib.kan_feed_batch(_ptr(images), _ptr(labels), _ptr(table), N, B, Cn, H, W, Ho, Wo, 1 if channels_last else 0, fl(*mean), fl(*std),
                                _ptr(data), _ptr(target), _stream(images)), "kan_feed_batch")
+    return data, target
+
+
+def prepare_resized_batch(images: torch.Tensor, table: torch.Tensor, resize, out_hw, mean, std, labels: Optional[torch.Tensor] = None,
+                          channels_last: bool = True, out_channels: Optional[int] = None, coeffs=None, out=None):
+    """``prepare_batch`` for the loader's ImageNet branch (utils/dataloader.py:26-54), in one launch of csrc/kan_feed_resize.hip and with no
+    host read: ``Resize`` of the whole image to ``resize`` = (Rh, Rw) (an int follows ``Resize(int)``; None: the image's own size), the crop
+    box of each row, ``Resize`` of the box to ``out_hw``, flip, ``Grayscale(3)`` when ``out_channels`` is 3 on one-channel images, ``ToTensor``,
+    ``Normalize`` -- with the bytes of PIL's 8-bit bilinear resampling (``data.resample_coeffs``).
+
+    ``table``: int32 [B, 6], rows (index, top, left, h, w, flip), the box in stage-1 (Rh x Rw) coordinates; ``mean`` / ``std``: ``out_channels``
+    floats (default: the images' C); ``coeffs``: the ``data.ResizeTables`` of this geometry on the images' device (``data.resize_tables``; built
+    and uploaded here when None -- a loop passes its own, as ``ResizedDeviceBatches`` does).  Returns (data fp32 [B, out_channels, Ho, Wo],
+    target int64 [B] or None); ``out=(data, target)`` writes into given tensors.  A row whose index is outside [0, N) or whose box is not inside
+    the stage-1 image with h, w >= 1 gets an all-zero image and target -1.  No autograd: images carry no gradient."""
+    lib = L.load()
+    if not (isinstance(images, torch.Tensor) and isinstance(table, torch.Tensor)):
+        raise L.KanConvError("prepare_resized_batch takes tensors for images and table")
+    if images.dtype != torch.uint8 or not images.is_contiguous():
+        raise L.KanConvError(f"images must be contiguous uint8, got {images.dtype}{'' if images.is_contiguous() else ', not contiguous'}")
+    if images.dim() == 3:
+        N, H, W = images.shape
+        Cn = 1
+    elif images.dim() == 4:
+        N, H, W, Cn = images.shape if channels_last else (images.shape[0], images.shape[2], images.shape[3], images.shape[1])
+    else:
+        raise L.KanConvError(f"images must be [N, H, W, C], [N, C, H, W] or [N, H, W], got {tuple(images.shape)}")
+    if min(N, H, W, Cn) < 1:
+        raise L.KanConvError(f"images are empty: {tuple(images.shape)}")
+    if Cn > 4:
+        raise L.KanConvError(f"at most 4 channels, got {Cn} ({'channels_last' if channels_last else 'channels first'} {tuple(images.shape)})")
+    limit = int(lib.kan_feed_max_image_bytes())
+    if H * W * Cn > limit:
+        raise L.KanConvError(f"an image of {H} x {W} x {Cn} = {H * W * Cn} bytes is above the {limit} bytes this kernel stages")
+    if table.device != images.device or table.dtype != torch.int32 or table.dim() != 2 or table.shape[1] != 6 or table.shape[0] < 1 \
+            or not table.is_contiguous():
+        raise L.KanConvError(f"table must be contiguous int32 [B, 6] on {images.device}, got {table.dtype} {tuple(table.shape)} on {table.device}")
+    B = table.shape[0]
+    from . import data as D                                  # data imports this module
+    Rh, Rw = D.resized_hw(H, W, resize)
+    Ho, Wo = (int(v) for v in out_hw)
+    if Rh < 1 or Rw < 1:
+        raise L.KanConvError(f"resize must be positive, got {(Rh, Rw)}")
+    if Ho < 1 or Wo < 1:
+        raise L.KanConvError(f"out_hw must be positive, got {(Ho, Wo)}")
+    OC = Cn if out_channels is None else int(out_channels)
+    if OC != Cn and not (OC == 3 and Cn == 1):
+        raise L.KanConvError(f"out_channels is the images' {Cn}, or 3 for one-channel images, got {OC}")
+    mean, std = [float(v) for v in mean], [float(v) for v in std]
+    if len(mean) != OC or len(std) != OC:
+        raise L.KanConvError(f"mean and std must hold {OC} values, got {len(mean)} and {len(std)}")
+    if labels is not None and (labels.device != images.device or labels.dtype != torch.int64 or labels.shape != (N,) or not labels.is_contiguous()):
+        raise L.KanConvError(f"labels must be contiguous int64 [{N}] on {images.device}, got {labels.dtype} {tuple(labels.shape)} on {labels.device}")
+    if coeffs is not None:
+        if not isinstance(coeffs, D.ResizeTables) or coeffs.geometry != (H, W, Rh, Rw, Ho, Wo) or coeffs.device != images.device:
+            raise L.KanConvError(f"coeffs must be the data.ResizeTables of {(H, W, Rh, Rw, Ho, Wo)} on {images.device}, got "
+                                 f"{getattr(coeffs, 'geometry', type(coeffs).__name__)} on {getattr(coeffs, 'device', None)}")
+        kmax = int(lib.kan_feed_resize_max_ksize())
+        if max(coeffs.ksize) > kmax:
+            raise L.KanConvError(f"a resampling pass of {max(coeffs.ksize)} taps is above the {kmax} this kernel's tiles are sized for")
+    if not images.is_cuda:                                   # after the checks that need no device, so those speak on any tensor
+        raise L.KanConvError(f"images are on {images.device}: this path runs only on a ROCm device (MI355X); there is no CPU fallback")
+    if out is not None:
+        data, target = out
+        if data.device != images.device or data.dtype != torch.float32 or tuple(data.shape) != (B, OC, Ho, Wo) or not data.is_contiguous():
+            raise L.KanConvError(f"out data must be contiguous float32 {(B, OC, Ho, Wo)} on {images.device}, got {data.dtype} {tuple(data.shape)}")
+        if (target is None) != (labels is None):
+            raise L.KanConvError("out target is given exactly when labels are")
+        if target is not None and (target.device != images.device or target.dtype != torch.int64 or tuple(target.shape) != (B,)
+                                   or not target.is_contiguous()):
+            raise L.KanConvError(f"out target must be contiguous int64 {(B,)} on {images.device}, got {target.dtype} {tuple(target.shape)}")
+    else:
+        data = torch.empty((B, OC, Ho, Wo), device=images.device, dtype=torch.float32)
+        target = torch.empty((B,), device=images.device, dtype=torch.int64) if labels is not None else None
+    if coeffs is None:
+        coeffs = D.resize_tables(H, W, Rh, Rw, Ho, Wo, device=images.device)
+    fl = C.c_float * OC
+    (k1x, k1y, k2x, k2y), ks = coeffs.tables, coeffs.ksize
+    L.check(lib.kan_feed_resize_batch(_ptr(images), _ptr(labels), _ptr(table), N, B, Cn, H, W, Rh, Rw, Ho, Wo, 1 if channels_last else 0, OC,
+                                      _ptr(k1x), ks[0], _ptr(k1y), ks[1], _ptr(k2x), ks[2], _ptr(k2y), ks[3], fl(*mean), fl(*std), _ptr(data),
+                                      _ptr(target), _stream(images)), "kan_feed_resize_batch")
     return data, target

@@ -486,6 +486,34 @@ int kan_feed_batch(const unsigned char* images, const long long* labels /* nulla
                    int Ho, int Wo, int channels_last, const float* mean /* host */, const float* std /* host */, float* data,
                    long long* target /* nullable with labels */, void* stream);
 
+/* The loader's ImageNet branch (utils/dataloader.py:26-54: Resize + RandomResizedCrop / CenterCrop + RandomHorizontalFlip, or Resize +
+ * Grayscale(3); then ToTensor + Normalize) on the same device-resident uint8 dataset, one launch per batch, with PIL's 8-bit BILINEAR
+ * resampling reproduced byte for byte.  Per sample, torchvision's order on PIL images: stage 1 resizes the whole H x W source to Rh x Rw; the
+ * box (top, left, h, w) of that image is cropped; stage 2 resizes the box to Ho x Wo; flip; one channel may be replicated to three; then the
+ * value arithmetic of kan_feed_batch.  A resize is a horizontal pass into a uint8 image, then a vertical pass over it, so four uint8 roundings
+ * precede the float conversion.  One pass from n to m samples is integer arithmetic over HOST-computed coefficient rows
+ * (data.resample_coeffs: PIL's float64 operations in PIL's order; the kernel does no floating-point coefficient work):
+ *       out[xx] = clip((2^21 + sum_{t < count} in[xmin + t] * k[t]) >> 22, 0, 255),   a row = (xmin, count, k[0 .. ksize)) of ksize + 2 int32,
+ * k zero past count.
+ *   images, labels, mean / std, target, channels_last   as kan_feed_batch; mean / std hold out_channels values
+ *   table    DEVICE int32 [B][6], one row (index, top, left, h, w, flip) per batch row; the box is in stage-1 coordinates
+ *   k1x, k1y DEVICE stage-1 coefficient rows: [Rw] rows of ksize1x + 2 for W -> Rw, [Rh] rows of ksize1y + 2 for H -> Rh
+ *   k2x, k2y DEVICE stage-2 coefficient rows for EVERY source length: [Rw][Wo] rows of ksize2x + 2 (block w - 1 is the pass w -> Wo), and
+ *            [Rh][Ho] rows of ksize2y + 2; a block whose own ksize is smaller is zero-padded to the common one
+ *   out_channels   C, or 3 with C == 1 (Grayscale(num_output_channels=3) on a one-channel image: a plain copy)
+ *   data     fp32 [B][out_channels][Ho][Wo] contiguous
+ *   bad rows an index outside [0, N), or a box not inside [0, Rh) x [0, Rw) with h, w >= 1, is compared before it addresses anything: an
+ *            all-zero image and target -1.  Coefficient rows are used for values only: every window is clamped into the tile it reads.
+ * One writer per output element; the same inputs give the same bits.  Refused by host arithmetic before any launch: null pointers (labels and
+ * target excepted, as a pair), a size or ksize below 1, C > 4, out_channels other than the above, H * W * C above kan_feed_max_image_bytes(),
+ * a ksize above kan_feed_resize_max_ksize() (9: one pass downscales by at most 4 -- the kernel's tiles are sized for that), Rh, Rw, Ho or Wo
+ * above 4096, and a geometry of which one output row does not fit the 160 KB of LDS of a compute unit. */
+int kan_feed_resize_max_ksize(void);
+int kan_feed_resize_batch(const unsigned char* images, const long long* labels /* nullable */, const int* table, long long N, int B, int C, int H,
+                          int W, int Rh, int Rw, int Ho, int Wo, int channels_last, int out_channels, const int* k1x, int ksize1x, const int* k1y,
+                          int ksize1y, const int* k2x, int ksize2x, const int* k2y, int ksize2y, const float* mean /* host */,
+                          const float* std /* host */, float* data, long long* target /* nullable with labels */, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- Wav-KAN wavelet stage
  * u[b, o, ho, wo] = sum_{c, r, t} w[o, c, r, t] * psi((x[b, c, hi, wi] - trans[o, c]) / scale[o, c]),  zero padding applied to the
  * wavelet values.  Replaces WaveletConvND / WaveletConvNDFast / WaveletConvNDFastPlusOne .forward up to (not including) the 1x1

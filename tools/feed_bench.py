@@ -14,6 +14,14 @@
                 TensorDataset of that fp32 list with num_workers=0 (the reference's transfer cost without its transforms).  The condition to meet:
                 the DeviceBatches step is within the run-to-run spread of the resident step plus the kernel time of (b) -- otherwise the iteration
                 path hides a host read or an allocation.
+  --imagenet    the loader's ImageNet branch instead (csrc/kan_feed_resize.hip, ops.prepare_resized_batch, K.ResizedDeviceBatches), written to
+                profiles/feed_resize_bench.json with `--out`:
+                (d) kernel  one bs-128 launch of the CIFAR train transform (Resize(256) + RandomResizedCrop(224) + flip) over 50 000 resident
+                            images, and of the test transform (CenterCrop: stage 2 the identity), against a same-process `fill_` of the same 77 MB
+                            output (the write alone), alternated; bytes from the shapes, B * (H*W*C + 4*3*224*224 + 24 + 16), and the share of the
+                            achievable HBM rate.
+                (e) step    KAN-AlexNet (ChebyKAN degree 4) bs-128 ``train_step`` fed by K.ResizedDeviceBatches against the same step on resident
+                            pre-materialised fp32 batches, alternated step by step.
 Kernel windows are `--launches` launches between two HIP events on the launch stream; steps are one step between two events.  Every figure is given per
 run (`--runs` repeats of the whole schedule) with median and min .. max.  One JSON line on stdout; `--out` also writes it.  There is no CPU figure:
 without a GPU the tool fails."""
@@ -182,6 +190,90 @@ def step_under_feeds(args, kernel_ms):
     return res
 
 
+IMAGENET_BATCH = 128
+
+
+def resized_bytes(B, H, W, C, OC, Ho, Wo):
+    return B * (H * W * C + 4 * OC * Ho * Wo + 24 + 16)
+
+
+def resized_kernel(args):
+    """(d): one bs-128 launch of the ImageNet-branch transforms against a fill of the same output."""
+    import torch
+    import convkan_amd as K
+    from convkan_amd import ops
+    images, labels = _synthetic(50000, 13)
+    out = (torch.empty((IMAGENET_BATCH, 3, 224, 224), device="cuda"), torch.empty((IMAGENET_BATCH,), device="cuda", dtype=torch.int64))
+    feeds = {"train": K.imagenet_device_batches("CIFAR10", True, images, labels, IMAGENET_BATCH),
+             "test": K.imagenet_device_batches("CIFAR10", False, images, labels, IMAGENET_BATCH, shuffle=True)}
+    tables = {k: d.epoch_table(0)[:IMAGENET_BATCH].contiguous() for k, d in feeds.items()}
+
+    def launch(k):
+        d = feeds[k]
+        return lambda: ops.prepare_resized_batch(images, tables[k], d.resize, d.out_hw, d.mean, d.std, labels, True, d.out_channels, d.coeffs, out)
+    settings = {"train": launch("train"), "test": launch("test"), "fill": lambda: out[0].fill_(0.5)}
+
+    def window(fn):
+        for _ in range(args.launches):
+            fn()
+    for fn in settings.values():
+        for _ in range(args.warmup):
+            window(fn)
+    torch.cuda.synchronize()
+    nbytes = resized_bytes(IMAGENET_BATCH, 32, 32, 3, 3, 224, 224)
+    res = {"batch": IMAGENET_BATCH, "bytes_per_launch": nbytes, "output_bytes": out[0].numel() * 4, "launches_per_window": args.launches,
+           "hbm_achievable_bytes_per_s": HBM_ACHIEVABLE, "runs": []}
+    for _ in range(args.runs):
+        times = {k: [] for k in settings}
+        for _ in range(args.steps):                                      # alternated window by window
+            for k, fn in settings.items():
+                times[k].append(_timed(lambda: window(fn))[0] / args.launches)
+        run = {k: _summary(times[k], 5) for k in settings}
+        for k in ("train", "test"):
+            rate = nbytes / (run[k]["median_ms"] * 1e-3)
+            run[k].update(bytes_per_s=round(rate, -6), share_of_achievable_hbm=round(rate / HBM_ACHIEVABLE, 3),
+                          fill_over_kernel_median=round(run["fill"]["median_ms"] / run[k]["median_ms"], 3))
+        res["runs"].append(run)
+    return res
+
+
+def resized_step(args):
+    """(e): the KAN-AlexNet step under the resized feed and under resident fp32 batches."""
+    import torch
+    import convkan_amd as K
+    from convkan_amd.models import alexnet_kan
+    torch.manual_seed(0)
+    model = alexnet_kan(num_classes=10, kan_conv="ChebyKAN", degree=4).cuda().train()
+    opt = K.FusedAdamW(model.parameters(), lr=1e-3, weight_decay=1e-4)
+    images, labels = _synthetic(50000, 17)
+    db = K.imagenet_device_batches("CIFAR10", True, images, labels, IMAGENET_BATCH, drop_last=True)
+    resident = [(x.clone(), t.clone()) for x, t in itertools.islice(iter(db), 8)]
+
+    def forever(make):
+        while True:
+            yield from make()
+    feeds = {"resized_device_batches": forever(lambda: iter(db)), "resident_fp32": forever(lambda: iter(resident))}
+
+    def step(feed):
+        data, target = next(feed)
+        return K.train_step(model, data, target, opt)
+    for _ in range(args.warmup):
+        for feed in feeds.values():
+            step(feed)
+    torch.cuda.synchronize()
+    res = {"workload": "kan_alexnet ChebyKAN degree 4 train_step (FusedAdamW)", "batch": IMAGENET_BATCH, "runs": []}
+    for _ in range(args.runs):
+        times = {k: [] for k in feeds}
+        for _ in range(args.steps):                                      # alternated step by step
+            for k, feed in feeds.items():
+                times[k].append(_timed(lambda: step(feed))[0])
+        run = {k: _summary(times[k]) for k in feeds}
+        run["resized_minus_resident_ms"] = round(run["resized_device_batches"]["median_ms"] - run["resident_fp32"]["median_ms"], 4)
+        run["images_per_s_resized"] = round(IMAGENET_BATCH / (run["resized_device_batches"]["median_ms"] * 1e-3), 1)
+        res["runs"].append(run)
+    return res
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--warmup", type=int, default=5)
@@ -190,10 +282,15 @@ if __name__ == "__main__":
     ap.add_argument("--runs", type=int, default=2)
     ap.add_argument("--only", default="abc", help="which of a, b, c to run")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--imagenet", action="store_true", help="measure the ImageNet-branch feed (d, e) instead of a, b, c")
     a = ap.parse_args()
     import torch
     assert torch.cuda.is_available(), "this tool measures on the GPU: there is no CPU figure"
     res = {"tool": "tools/feed_bench.py", "device": torch.cuda.get_device_name(0)}
+    if a.imagenet:
+        res["d_resized_kernel"] = resized_kernel(a)
+        res["e_step_under_resized_feed"] = resized_step(a)
+        a.only = ""
     if "a" in a.only:
         res["a_kernel_rate"] = kernel_rate(a)
     kernel_ms = 0.0
