@@ -28,9 +28,9 @@ import ctypes as C
 import os
 import weakref
 from collections import OrderedDict
-from dataclasses import dataclass
-from functools import lru_cache
-from typing import List, Optional, Sequence, Tuple
+from dataclasses import dataclass, replace
+from functools import lru_cache, partial
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -345,71 +345,161 @@ def always_pack():
         _ALWAYS_PACK = prev
 
 
-_SPLIT_INFERENCE = False
-_SPLIT_CACHE: "OrderedDict" = OrderedDict()             # (weight addresses) -> (version stamps, epoch, cut weights of the forward launch)
+# --------------------------------------------------------------------------------------- opt-in split precision
+# Three conv launches have a split-precision twin in csrc/kan_split.hip: the forward, the input gradient, the weight gradient.  Everything the host adds
+# to them is in this section: ONE switch record and the six public contexts that set its fields, ONE scope rule, ONE cut-weight cache class (an
+# instance per launch that reads cut weights), the three public entry points, and ONE per-stage decision that both autograd Functions take.
+@dataclass(frozen=True)
+class SplitMode:
+    """Which launches of the layers in scope run in split precision.  Immutable: a context swaps the whole record and puts back the one it found."""
+    inference: bool = False       # the forward of a fused stage, under no_grad only
+    fwd: bool = False             # the forward, in any grad mode
+    bwd_data: bool = False        # the input gradient
+    bwd_weight: bool = False      # the weight gradients
+
+
+_SPLIT = SplitMode()
 
 
 @contextlib.contextmanager
+def _split(**on):
+    """Inside: `_SPLIT` with the named fields True, every other field as found; on exit, the record that was found."""
+    global _SPLIT
+    prev, _SPLIT = _SPLIT, replace(_SPLIT, **on)
+    try:
+        yield
+    finally:
+        _SPLIT = prev
+
+
 def split_precision_inference():
     """OPT-IN, inference only: inside, a fused conv + InstanceNorm + PReLU stage whose inputs need no gradient (torch.no_grad() / eval serving) and whose
     geometry is in scope of `kan_conv_fwd_split` (default B-spline spec on 8x8 / 16x16 planes, 3x3 / stride 1 / pad 1, one group, C % 8 == 0, O % 128 == 0,
     even batch on 8x8) runs its conv stage in split precision (3 x bf16 pieces, six bf16 MFMA products; ~4e-6 of the largest pre-norm value from the exact result, 1.7x
     faster).  Everything else -- every other layer, and every training step -- stays on exact fp32 MFMA.  Never on by default."""
-    global _SPLIT_INFERENCE
-    prev, _SPLIT_INFERENCE = _SPLIT_INFERENCE, True
-    try:
-        yield
-    finally:
-        _SPLIT_INFERENCE = prev
+    return _split(inference=True)
 
 
-_SPLIT_FWD = False
-
-
-@contextlib.contextmanager
 def split_precision_forward():
     """OPT-IN, training and inference: inside, a conv stage (`kan_conv`, `kan_conv_in_prelu`) in scope of `kan_conv_fwd_split` (one group, base branch, no
     second input, no phases, no plane windows, `kan_split_supported`: default B-spline spec on 8x8 / 16x16 planes, 3x3 / stride 1 / pad 1, C % 8 == 0,
     O % 128 == 0, even batch on 8x8) runs its FORWARD in split precision (3 x bf16 pieces, six bf16 MFMA products), with grad mode on or off.  Its backward
     stays the exact one -- the forward hands it what it needs -- unless the backward contexts are entered too (`split_precision_training`).  Every other
     layer stays on exact fp32 MFMA.  Never on by default."""
-    global _SPLIT_FWD
-    prev, _SPLIT_FWD = _SPLIT_FWD, True
-    try:
-        yield
-    finally:
-        _SPLIT_FWD = prev
+    return _split(fwd=True)
 
 
-def _split_stage(spec: ConvSpec, x: torch.Tensor, xn, phases, w_base, w_basis):
-    """[B, O, H, W] pre-norm values through kan_conv_fwd_split, or None when the stage is out of its scope (the host conditions of `_split_bwd_weights`,
-    then `kan_split_supported`).  The cut weights are cached per weight pair on the scheme of `_SPLIT_BWD_CACHE`: ONE buffer, re-cut in place when a version
-    stamp or the epoch moved and, under `always_pack` (a recorded step), unconditionally; the entry goes when a weight tensor dies."""
+def split_precision_backward_data():
+    """OPT-IN, training: a conv autograd Function whose FORWARD runs inside with grad mode on (the decision is taken there, as autocast takes it), whose
+    input needs a gradient and whose stage is in scope of `kan_conv_bwd_data_split` (one group, base branch, no second input, no phases, no plane
+    windows, `kan_split_supported`: default B-spline spec on 8x8 / 16x16 planes, 3x3 / stride 1 / pad 1, C % 8 == 0, O % 128 == 0, even batch on 8x8)
+    computes its INPUT gradient in split precision (3 x bf16 pieces, six bf16 MFMA products).  The forward, the weight gradient and every other layer
+    stay on exact fp32 MFMA.  Never on by default."""
+    return _split(bwd_data=True)
+
+
+def split_precision_backward_weight():
+    """OPT-IN, training: a conv autograd Function whose FORWARD runs inside (the decision is taken there and carried on the autograd node, so a backward
+    run outside still takes it), whose weights need a gradient and whose stage is in scope of `kan_conv_bwd_weight_split` (one group, base branch, no
+    second input, no phases, no plane windows, `kan_split_supported`: default B-spline spec on 8x8 / 16x16 planes, 3x3 / stride 1 / pad 1, C % 8 == 0,
+    O % 128 == 0, even batch on 8x8) computes its WEIGHT gradient in split precision (3 x bf16 pieces, six bf16 MFMA products), straight into the tensors
+    the exact path would fill (GRAD_SINKS included).  The forward, the input gradient and every other layer stay on exact fp32 MFMA.  Never on by default."""
+    return _split(bwd_weight=True)
+
+
+def split_precision_backward():
+    """`split_precision_backward_data` and `split_precision_backward_weight` at once: the whole backward of the layers in scope."""
+    return _split(bwd_data=True, bwd_weight=True)
+
+
+def split_precision_training():
+    """`split_precision_forward`, `split_precision_backward_data` and `split_precision_backward_weight` at once: all three conv launches of the layers in
+    scope, for a training step run inside (`train.train_step(..., split_precision=True)`).  `split_precision_inference` is a switch of its own."""
+    return _split(fwd=True, bwd_data=True, bwd_weight=True)
+
+
+# THE sentence that states the scope (every refusal quotes it), and THE rule (every launch asks it).
+_SPLIT_SCOPE = ("default B-spline spec (grid 5, order 3, SiLU base branch), 8x8 or 16x16 planes, 3x3 / stride 1 / pad 1, one group, no second input, no phases, "
+                "no plane window, C % 8 == 0, O % 128 == 0, even batch on 8x8 planes")
+
+
+def _split_scope(spec: ConvSpec, x: torch.Tensor, xn, phases, Og: int):
+    """(geom, basis) of a stage the split-precision launches take, None for every other: the host conditions, then the library's (`kan_split_supported`).
+    Each launch then asks its own byte count, which is 0 where that launch is over its size limit."""
     if spec.groups != 1 or not spec.has_base or xn is not None or phases is not None or x.dim() != 4 or spec.first or spec.w_layout == W_IOD:
         return None
-    lib = L.load()
-    wb, ws = w_base[0], w_basis[0]
-    geom, basis, _ = _plan_cached(*_plan_key(spec, x.shape, ws.shape[0]))
-    nbytes = lib.kan_split_weight_bytes(C.byref(geom), C.byref(basis)) if lib.kan_split_supported(C.byref(geom), C.byref(basis)) else 0
+    geom, basis, _ = _plan_cached(*_plan_key(spec, x.shape, Og))
+    return (geom, basis) if L.load().kan_split_supported(C.byref(geom), C.byref(basis)) else None
+
+
+def _split_launch(which: str, nbytes_export: str, spec: ConvSpec, x: torch.Tensor, Og: Optional[int] = None, dz: Optional[torch.Tensor] = None):
+    """(geom, basis, byte count of `nbytes_export`) for a public entry point, or its refusal: the stage out of scope or over the launch's size limit, or
+    (the two backward launches, which take the output count from it) a `dz` that is not the stage's output gradient."""
+    if dz is not None:
+        if x.dim() != 4 or dz.dim() != 4:
+            raise L.KanConvError(f"split-precision {which}: NCHW x and dz, got {tuple(x.shape)} and {tuple(dz.shape)}")
+        Og = dz.shape[1]
+    scope = _split_scope(spec, x, None, None, Og)
+    nbytes = _split_bytes(nbytes_export, *scope) if scope is not None else 0
     if not nbytes:
-        return None
-    key = (wb.data_ptr(), ws.data_ptr(), x.device.index)
-    stamps = (_owner(wb)._version, _owner(ws)._version, _EPOCH)
-    ent = _SPLIT_CACHE.get(key)
-    if ent is None:                                     # drop the entry when a weight tensor dies: another model's weights may get the same addresses and stamps
-        for o in (_owner(wb), _owner(ws)):
-            weakref.finalize(o, _SPLIT_CACHE.pop, key, None)
-    wc = ent[1] if ent is not None and ent[1].numel() == nbytes else None
-    if wc is None or ent[0] != stamps or _ALWAYS_PACK:
-        with torch.cuda.device(x.device):
-            if wc is None:
-                wc = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
-            L.check(lib.kan_split_pack_weights(_ptr(wb), _ptr(ws), C.c_void_p(wc.data_ptr()), C.byref(geom), C.byref(basis), _stream(x)), "kan_split_pack_weights")
-    _SPLIT_CACHE[key] = (stamps, wc)
-    _SPLIT_CACHE.move_to_end(key)
-    while len(_SPLIT_CACHE) > 16:
-        _SPLIT_CACHE.popitem(last=False)
-    return kan_conv_fwd_split(spec, x, wb, ws, wc)[0]
+        raise L.KanConvError(f"split-precision {which}: {_SPLIT_SCOPE} only")
+    geom, basis = scope
+    if dz is not None and tuple(dz.shape) != (geom.B, Og, geom.Ho, geom.Wo):
+        raise L.KanConvError(f"split-precision {which}: dz {tuple(dz.shape)} != {(geom.B, Og, geom.Ho, geom.Wo)}")
+    return geom, basis, nbytes
+
+
+def _split_bytes(nbytes_export: str, geom, basis) -> int:
+    """A launch's own byte-count export: 0 where it does not take the stage (out of scope, or over its size limit)."""
+    return getattr(L.load(), nbytes_export)(C.byref(geom), C.byref(basis))
+
+
+def _cut_weights(nbytes_export: str, pack_export: str, geom, basis, w_base: torch.Tensor, w_basis: torch.Tensor, buf: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The weights cut into bf16 pieces by `pack_export`, into `buf` (allocated when None)."""
+    if buf is None:
+        buf = torch.empty(_split_bytes(nbytes_export, geom, basis), device=w_base.device, dtype=torch.uint8)
+    L.check(getattr(L.load(), pack_export)(_ptr(w_base), _ptr(w_basis), C.c_void_p(buf.data_ptr()), C.byref(geom), C.byref(basis), _stream(w_base)), pack_export)
+    return buf
+
+
+_cut_weights_fwd = partial(_cut_weights, "kan_split_weight_bytes", "kan_split_pack_weights")
+_cut_weights_bwd_data = partial(_cut_weights, "kan_split_bwd_data_weight_bytes", "kan_split_pack_weights_bwd_data")
+
+
+class CutWeightCache:
+    """The cut weights of one split-precision launch, per weight pair.  `nbytes(geom, basis)`: the size of the cut (0: the launch does not take the stage);
+    `pack(geom, basis, w_base, w_basis, buf)`: the cut, into `buf`.  ONE buffer per pair: re-cut in place when a version stamp of the two owners or the
+    `weights_changed()` epoch moved and, under `always_pack` (a recorded step), unconditionally -- a replay cuts the weights as they are then, into the
+    address it was recorded with; reallocated only when its size is wrong.  At most `bound` pairs, the least recently used goes first."""
+
+    def __init__(self, nbytes, pack, bound: int = 16):
+        self.nbytes, self.pack, self.bound = nbytes, pack, bound
+        self.entries: "OrderedDict" = OrderedDict()      # (weight addresses, device index) -> (version stamps and epoch, cut weights)
+
+    def get(self, geom, basis, wb: torch.Tensor, ws: torch.Tensor) -> Optional[torch.Tensor]:
+        nbytes = self.nbytes(geom, basis)
+        if not nbytes:
+            return None
+        key = (wb.data_ptr(), ws.data_ptr(), wb.device.index)
+        stamps = (_owner(wb)._version, _owner(ws)._version, _EPOCH)
+        ent = self.entries.get(key)
+        if ent is None:                                     # drop the entry when a weight tensor dies: another model's weights may get the same addresses and stamps
+            for o in (_owner(wb), _owner(ws)):
+                weakref.finalize(o, self.entries.pop, key, None)
+        buf = ent[1] if ent is not None and ent[1].numel() == nbytes else None
+        if buf is None or ent[0] != stamps or _ALWAYS_PACK:
+            if buf is None:
+                buf = torch.empty(nbytes, device=wb.device, dtype=torch.uint8)
+            self.pack(geom, basis, wb, ws, buf)
+        self.entries[key] = (stamps, buf)
+        self.entries.move_to_end(key)
+        while len(self.entries) > self.bound:
+            self.entries.popitem(last=False)
+        return buf
+
+
+_CUT_FWD = CutWeightCache(partial(_split_bytes, "kan_split_weight_bytes"), _cut_weights_fwd)
+_CUT_BWD_DATA = CutWeightCache(partial(_split_bytes, "kan_split_bwd_data_weight_bytes"), _cut_weights_bwd_data)
 
 
 def _split_fwd_keeps(spec: ConvSpec, x: torch.Tensor, w_base, w_basis, exact_x: bool, exact_w: bool):
@@ -426,107 +516,102 @@ def _split_fwd_keeps(spec: ConvSpec, x: torch.Tensor, w_base, w_basis, exact_x: 
     return wd, x_pm, plan
 
 
-_SPLIT_BWD_DATA = False
-_SPLIT_BWD_CACHE: "OrderedDict" = OrderedDict()         # (weight addresses) -> (version stamps, epoch, cut weights of the bwd-data launch)
+class SplitStage(NamedTuple):
+    """What `_split_decision` settled for one conv stage."""
+    z: Optional[torch.Tensor] = None          # [B, O, H, W] pre-norm values of the split-precision forward, which has then run; None: the exact forward is due
+    wcd: Optional[torch.Tensor] = None        # cut weights for kan_conv_bwd_data_split; None: the input gradient is the exact one
+    dw_split: bool = False                    # the weight gradients come from kan_conv_bwd_weight_split
 
 
-@contextlib.contextmanager
-def split_precision_backward_data():
-    """OPT-IN, training: a conv autograd Function whose FORWARD runs inside with grad mode on (the decision is taken there, as autocast takes it), whose
-    input needs a gradient and whose stage is in scope of `kan_conv_bwd_data_split` (one group, base branch, no second input, no phases, no plane
-    windows, `kan_split_supported`: default B-spline spec on 8x8 / 16x16 planes, 3x3 / stride 1 / pad 1, C % 8 == 0, O % 128 == 0, even batch on 8x8)
-    computes its INPUT gradient in split precision (3 x bf16 pieces, six bf16 MFMA products).  The forward, the weight gradient and every other layer
-    stay on exact fp32 MFMA.  Never on by default."""
-    global _SPLIT_BWD_DATA
-    prev, _SPLIT_BWD_DATA = _SPLIT_BWD_DATA, True
-    try:
-        yield
-    finally:
-        _SPLIT_BWD_DATA = prev
+_NOTHING_SPLIT = SplitStage()
 
 
-def _split_bwd_weights(spec: ConvSpec, x: torch.Tensor, xn, phases, w_base, w_basis, need_dgrad: bool):
-    """The cut weights `wcd` a backward hands to kan_conv_bwd_data_split, or None: outside `split_precision_backward_data`, without an input gradient to
-    compute (grad mode off, or an input that needs none), or for a stage out of scope.  Cached per weight pair: ONE buffer, re-cut in place when a
-    version stamp moved and, under `always_pack` (a recorded step), unconditionally -- a replay cuts the weights as they are then, into the address it
-    was recorded with."""
-    if not (_SPLIT_BWD_DATA and need_dgrad):            # need_dgrad comes from ctx.needs_input_grad: False whenever the caller's grad mode is off
-        return None
-    if spec.groups != 1 or not spec.has_base or xn is not None or phases is not None or x.dim() != 4 or spec.first or spec.w_layout == W_IOD:
-        return None
+def _split_decision(spec: ConvSpec, x: torch.Tensor, xn, phases, w_base, w_basis, want_fwd: bool, need_dgrad: bool, need_w: bool) -> SplitStage:
+    """Which of a stage's three conv launches run in split precision, taken in the autograd forward (as autocast takes its own) and carried on the node, so a
+    backward run outside the contexts still follows it.  `want_fwd`: the caller saw `split_precision_forward` (or `split_precision_inference` under no_grad);
+    `need_dgrad` / `need_w` come from ctx.needs_input_grad: False whenever the caller's grad mode is off.  With no switch on it returns before any plan
+    lookup or library call.  The three public entry points are reached through the module globals (the tests' spies replace them)."""
+    want_x, want_w = _SPLIT.bwd_data and need_dgrad, _SPLIT.bwd_weight and need_w
+    if not (want_fwd or want_x or want_w):
+        return _NOTHING_SPLIT
+    scope = _split_scope(spec, x, xn, phases, w_basis[0].shape[0])
+    if scope is None:
+        return _NOTHING_SPLIT
+    geom, basis = scope
     wb, ws = w_base[0], w_basis[0]
-    geom, basis, _ = _plan_cached(*_plan_key(spec, x.shape, ws.shape[0]))
-    nbytes = L.load().kan_split_bwd_data_weight_bytes(C.byref(geom), C.byref(basis))
-    if not nbytes:
-        return None
-    key = (wb.data_ptr(), ws.data_ptr(), x.device.index)
-    stamps = (_owner(wb)._version, _owner(ws)._version, _EPOCH)
-    ent = _SPLIT_BWD_CACHE.get(key)
-    if ent is None:                                     # drop the entry when a weight tensor dies: another model's weights may get the same addresses and stamps
-        for o in (_owner(wb), _owner(ws)):
-            weakref.finalize(o, _SPLIT_BWD_CACHE.pop, key, None)
-    wcd = ent[1] if ent is not None and ent[1].numel() == nbytes else None
-    if wcd is None or ent[0] != stamps or _ALWAYS_PACK:
-        wcd = _cut_weights_bwd_data(geom, basis, wb, ws, wcd)
-    _SPLIT_BWD_CACHE[key] = (stamps, wcd)
-    _SPLIT_BWD_CACHE.move_to_end(key)
-    while len(_SPLIT_BWD_CACHE) > 16:
-        _SPLIT_BWD_CACHE.popitem(last=False)
-    return wcd
+    wcd = _CUT_BWD_DATA.get(geom, basis, wb, ws) if want_x else None
+    dw_split = bool(want_w and _split_bytes("kan_split_bwd_weight_workspace_bytes", geom, basis) > 0)
+    wc = _CUT_FWD.get(geom, basis, wb, ws) if want_fwd else None
+    z = kan_conv_fwd_split(spec, x, wb, ws, wc)[0] if wc is not None else None
+    return SplitStage(z, wcd, dw_split)
 
 
-def _cut_weights_bwd_data(geom, basis, w_base: torch.Tensor, w_basis: torch.Tensor, wcd: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """kan_split_pack_weights_bwd_data into `wcd` (allocated when None)."""
+def _conv_forward_or_split(spec: ConvSpec, x, xn, phases, w_base, w_basis, want_fwd: bool, need_dgrad: bool, need_w: bool):
+    """The forward of a conv stage under `_split_decision`.  Returns (z_slabs [S,B,O,Ho,Wo], (bwd-data weight layout or None, position-major x or None), plan,
+    the SplitStage): after a split-precision forward (one slab) the pair holds what the EXACT launches of the backward will read, no more."""
+    split = _split_decision(spec, x, xn, phases, w_base, w_basis, want_fwd, need_dgrad, need_w)
+    if split.z is None:
+        zs, packed, _, _, plan = _conv_forward(spec, x, xn, w_base, w_basis, need_dgrad, phases)
+        return zs, packed, plan, split
+    wd, x_pm, plan = _split_fwd_keeps(spec, x, w_base, w_basis, need_dgrad and split.wcd is None, need_w and not split.dw_split)
+    return split.z.unsqueeze(0), (wd, x_pm), plan, split
+
+
+def kan_conv_fwd_split(spec: ConvSpec, x: torch.Tensor, w_base: torch.Tensor, w_basis: torch.Tensor, wc: Optional[torch.Tensor] = None):
+    """OPT-IN split-precision conv stage (forward only, no autograd; kanconv.h `kan_conv_fwd_split`): the fp32 result of `kan_conv` to ~4e-6 of its largest
+    element, through 3 x bf16 pieces and six bf16 MFMA products per k-block.  The layers take it only inside `split_precision_inference` /
+    `split_precision_forward`; scope: `_SPLIT_SCOPE` (raises KanConvError otherwise).  Returns (z, wc): pass `wc` back while the weights are unchanged to
+    skip the cut (0.05 ms at 256 -> 256)."""
     lib = L.load()
-    if wcd is None:
-        wcd = torch.empty(lib.kan_split_bwd_data_weight_bytes(C.byref(geom), C.byref(basis)), device=w_base.device, dtype=torch.uint8)
-    L.check(lib.kan_split_pack_weights_bwd_data(_ptr(w_base), _ptr(w_basis), C.c_void_p(wcd.data_ptr()), C.byref(geom), C.byref(basis), _stream(w_base)),
-            "kan_split_pack_weights_bwd_data")
-    return wcd
+    x, w_base, w_basis = _require(x, "x"), _require(w_base, "w_base"), _require(w_basis, "w_basis")
+    Ot = w_basis.shape[0]
+    geom, basis, _ = _split_launch("forward", "kan_split_weight_bytes", spec, x, Ot)
+    with torch.cuda.device(x.device):
+        if wc is None:
+            wc = _cut_weights_fwd(geom, basis, w_base, w_basis)
+        z = torch.empty((geom.B, Ot, geom.H, geom.W), device=x.device, dtype=torch.float32)
+        L.check(lib.kan_conv_fwd_split(_ptr(x), C.c_void_p(wc.data_ptr()), _ptr(z), C.byref(geom), C.byref(basis), _stream(x)), "kan_conv_fwd_split")
+    return z, wc
 
 
-_SPLIT_BWD_WEIGHT = False
+def kan_conv_bwd_data_split(spec: ConvSpec, x: torch.Tensor, dz: torch.Tensor, w_base: Optional[torch.Tensor], w_basis: Optional[torch.Tensor],
+                            wcd: Optional[torch.Tensor] = None):
+    """OPT-IN split-precision input gradient of the conv stage (no autograd; kanconv.h `kan_conv_bwd_data_split`): what the backward of `kan_conv` returns for
+    x, through 3 x bf16 pieces of dz and the weights and six bf16 MFMA products per k-block; the derivative planes are the exact kernel's.  Scope: that of
+    `kan_conv_fwd_split` (raises KanConvError otherwise).  Returns (dx, wcd): pass `wcd` back while the weights are unchanged to skip the cut (the
+    weights may then be None)."""
+    lib = L.load()
+    x, dz = _require(x, "x"), _require(dz, "dz")
+    geom, basis, nbytes = _split_launch("bwd-data", "kan_split_bwd_data_weight_bytes", spec, x, dz=dz)
+    with torch.cuda.device(x.device):
+        if wcd is None:
+            wcd = _cut_weights_bwd_data(geom, basis, _require(w_base, "w_base"), _require(w_basis, "w_basis"))
+        elif wcd.numel() != nbytes or wcd.dtype != torch.uint8 or wcd.device != x.device:
+            raise L.KanConvError(f"split-precision bwd-data: wcd must hold {nbytes} bytes on {x.device}")
+        dx = torch.empty_like(x)
+        L.check(lib.kan_conv_bwd_data_split(_ptr(dz), _ptr(x), C.c_void_p(wcd.data_ptr()), _ptr(dx), C.byref(geom), C.byref(basis), _stream(x)), "kan_conv_bwd_data_split")
+    return dx, wcd
 
 
-@contextlib.contextmanager
-def split_precision_backward_weight():
-    """OPT-IN, training: a conv autograd Function whose FORWARD runs inside (the decision is taken there and carried on the autograd node, so a backward
-    run outside still takes it), whose weights need a gradient and whose stage is in scope of `kan_conv_bwd_weight_split` (one group, base branch, no
-    second input, no phases, no plane windows, `kan_split_supported`: default B-spline spec on 8x8 / 16x16 planes, 3x3 / stride 1 / pad 1, C % 8 == 0,
-    O % 128 == 0, even batch on 8x8) computes its WEIGHT gradient in split precision (3 x bf16 pieces, six bf16 MFMA products), straight into the tensors
-    the exact path would fill (GRAD_SINKS included).  The forward, the input gradient and every other layer stay on exact fp32 MFMA.  Never on by default."""
-    global _SPLIT_BWD_WEIGHT
-    prev, _SPLIT_BWD_WEIGHT = _SPLIT_BWD_WEIGHT, True
-    try:
-        yield
-    finally:
-        _SPLIT_BWD_WEIGHT = prev
-
-
-@contextlib.contextmanager
-def split_precision_backward():
-    """`split_precision_backward_data` and `split_precision_backward_weight` at once: the whole backward of the layers in scope."""
-    with split_precision_backward_data(), split_precision_backward_weight():
-        yield
-
-
-@contextlib.contextmanager
-def split_precision_training():
-    """`split_precision_forward`, `split_precision_backward_data` and `split_precision_backward_weight` at once: all three conv launches of the layers in
-    scope, for a training step run inside (`train.train_step(..., split_precision=True)`).  `split_precision_inference` is a switch of its own."""
-    with split_precision_forward(), split_precision_backward_data(), split_precision_backward_weight():
-        yield
-
-
-def _split_bwd_weight_stage(spec: ConvSpec, x: torch.Tensor, xn, phases, w_basis, need_w: bool) -> bool:
-    """Whether this stage's backward takes kan_conv_bwd_weight_split: inside `split_precision_backward_weight`, with a weight gradient to compute, under
-    the host conditions of `_split_bwd_weights` and with a workspace size from the library (0 = out of scope)."""
-    if not (_SPLIT_BWD_WEIGHT and need_w):
-        return False
-    if spec.groups != 1 or not spec.has_base or xn is not None or phases is not None or x.dim() != 4 or spec.first or spec.w_layout == W_IOD:
-        return False
-    geom, basis, _ = _plan_cached(*_plan_key(spec, x.shape, w_basis[0].shape[0]))
-    return L.load().kan_split_bwd_weight_workspace_bytes(C.byref(geom), C.byref(basis)) > 0
+def kan_conv_bwd_weight_split(spec: ConvSpec, x: torch.Tensor, dz: torch.Tensor, out=None):
+    """OPT-IN split-precision weight gradient of the conv stage (no autograd; kanconv.h `kan_conv_bwd_weight_split`): what the backward of `kan_conv` returns
+    for the base / spline weights, through 3 x bf16 pieces of the plane values (the exact kernel's) and of dz and six bf16 MFMA products per k-block.  Scope:
+    that of `kan_conv_fwd_split` (raises KanConvError otherwise).  Returns (dw_base [O, C, 3, 3], dw_basis [O, C * 8, 3, 3]); `out`: a pair of contiguous
+    fp32 tensors of those shapes to write into.  The workspace (cut dz + depth-split partial sums) comes from torch's allocator on the current stream."""
+    lib = L.load()
+    x, dz = _require(x, "x"), _require(dz, "dz")
+    geom, basis, nbytes = _split_launch("bwd-weight", "kan_split_bwd_weight_workspace_bytes", spec, x, dz=dz)
+    Ot, Ct = dz.shape[1], x.shape[1]
+    shapes = ((Ot, Ct, 3, 3), (Ot, Ct * spec.n_basis, 3, 3))
+    with torch.cuda.device(x.device):
+        if out is None:
+            out = tuple(torch.empty(sh, device=x.device, dtype=torch.float32) for sh in shapes)
+        elif any(tuple(t.shape) != sh or t.dtype != torch.float32 or t.device != x.device or not t.is_contiguous() for t, sh in zip(out, shapes)):
+            raise L.KanConvError(f"split-precision bwd-weight: out must be contiguous fp32 tensors {shapes} on {x.device}")
+        ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
+        L.check(lib.kan_conv_bwd_weight_split(_ptr(dz), _ptr(x), _ptr(out[0]), _ptr(out[1]), C.c_void_p(ws.data_ptr()), C.byref(geom), C.byref(basis), _stream(x)),
+                "kan_conv_bwd_weight_split")
+    return out[0], out[1]
 
 
 def weights_changed() -> None:
@@ -690,11 +775,11 @@ def _sink_for(wid, shape, device):
     return t
 
 
-def _conv_backward(spec: ConvSpec, x, xn, packed, dz, need_x: bool, need_xn: bool, need_w: bool, phases=None, mode: int = 0, wids=None, dparams=None, wcd=None, wsplit: bool = False):
+def _conv_backward(spec: ConvSpec, x, xn, packed, dz, need_x: bool, need_xn: bool, need_w: bool, phases=None, mode: int = 0, wids=None, dparams=None, wcd=None, dw_split: bool = False):
     """dz: [B,O,Ho,Wo] contiguous.  Returns (dx, dxn, dw_base list, dw_basis list) -- per-group views of stacked gradients.
     `wids`: ids of the (base, basis) weight Parameters of a single-group layer, for GRAD_SINKS.
-    `wcd`: cut weights handed over by a forward under `split_precision_backward_data`: dx comes from kan_conv_bwd_data_split iff it is given.
-    `wsplit`: decided by a forward under `split_precision_backward_weight`: the weight gradients come from kan_conv_bwd_weight_split."""
+    `wcd`, `dw_split`: the forward's SplitStage fields (`_split_decision`): dx comes from kan_conv_bwd_data_split iff `wcd` is given, the weight gradients
+    from kan_conv_bwd_weight_split iff `dw_split`."""
     lib = L.load()
     B, Ct, H, W = x.shape
     G = spec.groups
@@ -709,15 +794,18 @@ def _conv_backward(spec: ConvSpec, x, xn, packed, dz, need_x: bool, need_xn: boo
     wd, x_pm = packed
     dw_base: List[Optional[torch.Tensor]] = [None] * G
     dw_basis: List[Optional[torch.Tensor]] = [None] * G
-    exact_w, exact_x = need_w and not wsplit, (need_x or need_xn) and not (need_x and wcd is not None)      # the launches that read dz_pm
+    split_w = need_w and dw_split                        # which launches run in split precision ...
+    split_x = need_x and wcd is not None
+    exact_w = need_w and not split_w                     # ... and which exact ones are left: only they read dz_pm
+    exact_x = (need_x or need_xn) and not split_x
     dz_pm = _position_major(dz, 0, Ot) if (plan.dz_pm_wanted and xn is None and (exact_w or exact_x)) else None
-    if need_w and wsplit:                                # opt-in split-precision weight gradient: no packed slabs, no unpack; same tensors, same sinks
+    if split_w:                                          # opt-in split-precision weight gradient: no packed slabs, no unpack; same tensors, same sinks
         sb, ss = (_sink_for(wids[0], (Og, Cg, kh, kw), x.device), _sink_for(wids[1], (Og, Cg * spec.n_basis, kh, kw), x.device)) if wids else (None, None)
         dwb = sb if sb is not None else torch.empty((Og, Cg, kh, kw), device=x.device, dtype=torch.float32)
         dws = ss if ss is not None else torch.empty((Og, Cg * spec.n_basis, kh, kw), device=x.device, dtype=torch.float32)
         kan_conv_bwd_weight_split(spec, x, dz, out=(dwb, dws))
         dw_base, dw_basis = list(dwb.unsqueeze(0).unbind(0)), list(dws.unsqueeze(0).unbind(0))       # views, as the exact path returns them
-    elif need_w:
+    elif exact_w:
         dwp = torch.empty(plan.bwd_weight_splits * plan.bwd_weight_slab_elems, device=x.device, dtype=torch.float32)
         if plan.bwd_weight_expanded and xn is None and dz_pm is not None:
             # small padded planes: expanded position-major operand, DMA + MFMA weight gradient (kanconv.h)
@@ -743,9 +831,9 @@ def _conv_backward(spec: ConvSpec, x, xn, packed, dz, need_x: bool, need_xn: boo
             if spec.has_base:
                 dw_base = list(dwb.unbind(0))
     dx = dxn = None
-    if need_x and wcd is not None:                       # opt-in split-precision input gradient: one slab, no reduce
+    if split_x:                                          # opt-in split-precision input gradient: one slab, no reduce
         dx, _ = kan_conv_bwd_data_split(spec, x, dz, None, None, wcd)
-    elif need_x or need_xn:
+    elif exact_x:
         S = plan.bwd_data_splits
         separate = xn is not None
         dxs = torch.empty((S, B, Ct, H, W), device=x.device, dtype=torch.float32)
@@ -820,18 +908,12 @@ class _KanConv(torch.autograd.Function):
         need_dgrad = bool(ctx.needs_input_grad[2] or (xn is not None and ctx.needs_input_grad[3]))         # (0: spec, 1: split, 2: x, 3: xn, 4: phases, 5...: weights)
         need_w = any(ctx.needs_input_grad[5:])
         with torch.cuda.device(x.device):
-            wcd = _split_bwd_weights(spec, x, xn, phases, w_base, w_basis, need_dgrad)
-            ctx.wsplit = _split_bwd_weight_stage(spec, x, xn, phases, w_basis, need_w)
-            z = _split_stage(spec, x, xn, phases, w_base, w_basis) if split else None
-            if z is not None:                            # opt-in split-precision forward: one slab; the backward is exact unless its contexts are on too
-                wd, x_pm, _ = _split_fwd_keeps(spec, x, w_base, w_basis, need_dgrad and wcd is None, need_w and not ctx.wsplit)
-            else:
-                z, (wd, x_pm), geom, _, plan = _conv_forward(spec, x, xn, w_base, w_basis, need_dgrad, phases)
-                z = _sum_slabs(z, geom.B, z.shape[2], geom.Ho * geom.Wo)
-        ctx.spec = spec
+            zs, (wd, x_pm), _, stage = _conv_forward_or_split(spec, x, xn, phases, w_base, w_basis, split, need_dgrad, need_w)
+            z = _sum_slabs(zs, zs.shape[1], zs.shape[2], zs.shape[3] * zs.shape[4])
+        ctx.spec, ctx.wsplit = spec, stage.dw_split
         # the basis weights are kept only for the parameter gradient (their version counters are then checked in the backward)
         kept_w = {f"w_basis{g}": w for g, w in enumerate(w_basis)} if phases is not None else {}
-        _save(ctx, x=x, xn=xn, phases=phases, wd=wd, x_pm=x_pm, wcd=wcd, **kept_w)
+        _save(ctx, x=x, xn=xn, phases=phases, wd=wd, x_pm=x_pm, wcd=stage.wcd, **kept_w)
         return z
 
     @staticmethod
@@ -850,7 +932,7 @@ class _KanConv(torch.autograd.Function):
             dpar = None
             if in_epilogue:                                    # ReLU-KAN: [Cg, 2, n] directly; Gram: 64 slot rows of partial sums
                 dpar = torch.zeros_like(phases) if spec.kind == L.BASIS_RELU else phases.new_zeros((64, spec.n_basis))
-            dx, dxn, dwb, dws = _conv_backward(spec, x, xn, packed, dz, need_x, need_xn, need_w, phases, dparams=dpar, wcd=wcd, wsplit=ctx.wsplit)
+            dx, dxn, dwb, dws = _conv_backward(spec, x, xn, packed, dz, need_x, need_xn, need_w, phases, dparams=dpar, wcd=wcd, dw_split=ctx.wsplit)
             if in_epilogue:
                 dph = dpar if spec.kind == L.BASIS_RELU else dpar.sum(dim=0)
             if need_p and not in_epilogue:
@@ -1003,20 +1085,13 @@ class _KanConvInPrelu(torch.autograd.Function):
             raise L.KanConvError("only scalar-slope PReLU (nn.PReLU()) is supported, as in kan_layers.py:182")
         with torch.cuda.device(x.device):
             need_x, need_w = bool(ctx.needs_input_grad[7]), any(ctx.needs_input_grad[8:8 + nw])
-            wcd = _split_bwd_weights(spec, x, None, None, w_base, w_basis, need_x)
-            ctx.wsplit = _split_bwd_weight_stage(spec, x, None, None, w_basis, need_w)
-            zs = _split_stage(spec, x, None, None, w_base, w_basis) if split else None
-            if zs is not None:                           # opt-in split-precision forward (split_precision_inference / split_precision_forward): one slab
-                zs = zs.unsqueeze(0)
-                wd, x_pm, plan = _split_fwd_keeps(spec, x, w_base, w_basis, need_x and wcd is None, need_w and not ctx.wsplit)
-            else:
-                zs, (wd, x_pm), _, _, plan = _conv_forward(spec, x, None, w_base, w_basis, need_x)
+            zs, (wd, x_pm), plan, stage = _conv_forward_or_split(spec, x, None, None, w_base, w_basis, split, need_x, need_w)
             # all groups in one launch: per-channel gamma/beta concatenated, one PReLU slope per Og channels
             gamma, beta, slope = _cat(gammas), _cat(betas), _cat(prelus)
             y, z, mean, rstd, pidx = _norm_fwd(zs, plan.fwd_slab_elems, gamma, beta, slope, eps, G, pool, bn=bn)
-        ctx.spec, ctx.pool, ctx.bn = spec, pool, bn
+        ctx.spec, ctx.pool, ctx.bn, ctx.wsplit = spec, pool, bn, stage.dw_split
         ctx.wids = (id(w_base[0]) if spec.has_base else None, id(w_basis[0])) if G == 1 else None
-        _save(ctx, x=x, z=z, mean=mean, rstd=rstd, wd=wd, x_pm=x_pm, gamma=gamma, beta=beta, slope=slope, pidx=pidx, wcd=wcd)
+        _save(ctx, x=x, z=z, mean=mean, rstd=rstd, wd=wd, x_pm=x_pm, gamma=gamma, beta=beta, slope=slope, pidx=pidx, wcd=stage.wcd)
         return y
 
     @staticmethod
@@ -1028,7 +1103,7 @@ class _KanConvInPrelu(torch.autograd.Function):
             nw = G * (2 if spec.has_base else 1)
             need_x = ctx.needs_input_grad[7]
             need_w = any(ctx.needs_input_grad[8:8 + nw])
-            dx, _, dwb, dws = _conv_backward(spec, x, None, (wd, x_pm), dz, need_x, False, need_w, wids=ctx.wids, wcd=wcd, wsplit=ctx.wsplit)
+            dx, _, dwb, dws = _conv_backward(spec, x, None, (wd, x_pm), dz, need_x, False, need_w, wids=ctx.wids, wcd=wcd, dw_split=ctx.wsplit)
         grads = _flat_grads(spec, dwb, dws)
         if gamma is not None:
             grads += tuple(dgam.view(G, -1).unbind(0)) + tuple(dbet.view(G, -1).unbind(0))
@@ -1148,7 +1223,7 @@ def _apply(stage, spec: ConvSpec, x, xn, w_base, w_basis, extra=()) -> torch.Ten
 
 def kan_conv(spec: ConvSpec, x: torch.Tensor, xn: Optional[torch.Tensor], w_base: Sequence[torch.Tensor],
              w_basis: Sequence[torch.Tensor]) -> torch.Tensor:
-    split = _SPLIT_FWD                                  # opt-in split-precision forward: decided here, where the caller's flags are visible; each run of images decides its scope
+    split = _SPLIT.fwd                                  # opt-in split-precision forward: decided here, where the caller's flags are visible; each run of images decides its scope
     return _apply(lambda a, b, *ws: _KanConv.apply(spec, split, a, b, None, *ws), spec, x, xn, w_base, w_basis)
 
 
@@ -1190,90 +1265,11 @@ def kan_conv_in_prelu(spec: ConvSpec, x: torch.Tensor, w_base: Sequence[torch.Te
     if bn is not None and not fits_one_launch(spec, x, w_basis):
         raise L.KanConvError("a BatchNorm tail cannot be cut into runs of images: run kan_conv, then batch_norm")
     # opt-in split-precision forward, decided where the caller's grad mode and flags are visible: the inference switch under no_grad only, the forward switch always
-    split = _SPLIT_FWD or (_SPLIT_INFERENCE and not torch.is_grad_enabled())
+    split = _SPLIT.fwd or (_SPLIT.inference and not torch.is_grad_enabled())
     aff = gammas is not None
     extra = (list(gammas) + list(betas) if aff else []) + (list(prelus) if prelus is not None else [])
     return _apply(lambda a, _, *ps: _KanConvInPrelu.apply(spec, float(eps), aff, prelus is not None, pool, split, bn, a, *ps),
                   spec, x, None, w_base, w_basis, extra)
-
-
-def kan_conv_fwd_split(spec: ConvSpec, x: torch.Tensor, w_base: torch.Tensor, w_basis: torch.Tensor, wc: Optional[torch.Tensor] = None):
-    """OPT-IN split-precision conv stage (forward only, no autograd; kanconv.h `kan_conv_fwd_split`): the fp32 result of `kan_conv` to ~4e-6 of its largest
-    element, through 3 x bf16 pieces and six bf16 MFMA products per k-block.  The layers take it only inside `split_precision_inference` / `split_precision_forward`; scope: default B-spline spec on 8x8 or 16x16 planes, 3x3 /
-    stride 1 / pad 1, one group, C % 8 == 0, O % 128 == 0, even batch on 8x8 (raises KanConvError otherwise).  Returns (z, wc): pass `wc` back while the
-    weights are unchanged to skip the cut (0.05 ms at 256 -> 256)."""
-    lib = L.load()
-    x, w_base, w_basis = _require(x, "x"), _require(w_base, "w_base"), _require(w_basis, "w_basis")
-    (B, _, H, W), Ot = x.shape, w_basis.shape[0]
-    geom, basis, _ = _plan_cached(*_plan_key(spec, x.shape, Ot))
-    if not lib.kan_split_supported(C.byref(geom), C.byref(basis)):
-        raise L.KanConvError("split-precision forward: default B-spline spec (grid 5, order 3, SiLU base branch), 8x8 or 16x16 planes, 3x3 / stride 1 / pad 1, one group, C % 8 == 0, O % 128 == 0, "
-                             "even batch only")
-    with torch.cuda.device(x.device):
-        if wc is None:
-            wc = torch.empty(lib.kan_split_weight_bytes(C.byref(geom), C.byref(basis)), device=x.device, dtype=torch.uint8)
-            L.check(lib.kan_split_pack_weights(_ptr(w_base), _ptr(w_basis), C.c_void_p(wc.data_ptr()), C.byref(geom), C.byref(basis), _stream(x)),
-                    "kan_split_pack_weights")
-        z = torch.empty((B, Ot, H, W), device=x.device, dtype=torch.float32)
-        L.check(lib.kan_conv_fwd_split(_ptr(x), C.c_void_p(wc.data_ptr()), _ptr(z), C.byref(geom), C.byref(basis), _stream(x)), "kan_conv_fwd_split")
-    return z, wc
-
-
-def kan_conv_bwd_data_split(spec: ConvSpec, x: torch.Tensor, dz: torch.Tensor, w_base: Optional[torch.Tensor], w_basis: Optional[torch.Tensor],
-                            wcd: Optional[torch.Tensor] = None):
-    """OPT-IN split-precision input gradient of the conv stage (no autograd; kanconv.h `kan_conv_bwd_data_split`): what the backward of `kan_conv` returns for
-    x, through 3 x bf16 pieces of dz and the weights and six bf16 MFMA products per k-block; the derivative planes are the exact kernel's.  Scope: that of
-    `kan_conv_fwd_split` (raises KanConvError otherwise).  Returns (dx, wcd): pass `wcd` back while the weights are unchanged to skip the cut (the
-    weights may then be None)."""
-    lib = L.load()
-    x, dz = _require(x, "x"), _require(dz, "dz")
-    if x.dim() != 4 or dz.dim() != 4:
-        raise L.KanConvError(f"split-precision bwd-data: NCHW x and dz, got {tuple(x.shape)} and {tuple(dz.shape)}")
-    Ot = dz.shape[1]
-    geom, basis, _ = _plan_cached(*_plan_key(spec, x.shape, Ot))
-    nbytes = lib.kan_split_bwd_data_weight_bytes(C.byref(geom), C.byref(basis)) if spec.groups == 1 and spec.has_base and not spec.first else 0
-    if not nbytes:
-        raise L.KanConvError("split-precision bwd-data: default B-spline spec (grid 5, order 3, SiLU base branch), 8x8 or 16x16 planes, 3x3 / stride 1 / pad 1, one group, C % 8 == 0, "
-                             "O % 128 == 0, even batch only")
-    if tuple(dz.shape) != (geom.B, Ot, geom.Ho, geom.Wo):
-        raise L.KanConvError(f"split-precision bwd-data: dz {tuple(dz.shape)} != {(geom.B, Ot, geom.Ho, geom.Wo)}")
-    with torch.cuda.device(x.device):
-        if wcd is None:
-            wcd = _cut_weights_bwd_data(geom, basis, _require(w_base, "w_base"), _require(w_basis, "w_basis"))
-        elif wcd.numel() != nbytes or wcd.dtype != torch.uint8 or wcd.device != x.device:
-            raise L.KanConvError(f"split-precision bwd-data: wcd must hold {nbytes} bytes on {x.device}")
-        dx = torch.empty_like(x)
-        L.check(lib.kan_conv_bwd_data_split(_ptr(dz), _ptr(x), C.c_void_p(wcd.data_ptr()), _ptr(dx), C.byref(geom), C.byref(basis), _stream(x)), "kan_conv_bwd_data_split")
-    return dx, wcd
-
-
-def kan_conv_bwd_weight_split(spec: ConvSpec, x: torch.Tensor, dz: torch.Tensor, out=None):
-    """OPT-IN split-precision weight gradient of the conv stage (no autograd; kanconv.h `kan_conv_bwd_weight_split`): what the backward of `kan_conv` returns
-    for the base / spline weights, through 3 x bf16 pieces of the plane values (the exact kernel's) and of dz and six bf16 MFMA products per k-block.  Scope:
-    that of `kan_conv_fwd_split` (raises KanConvError otherwise).  Returns (dw_base [O, C, 3, 3], dw_basis [O, C * 8, 3, 3]); `out`: a pair of contiguous
-    fp32 tensors of those shapes to write into.  The workspace (cut dz + depth-split partial sums) comes from torch's allocator on the current stream."""
-    lib = L.load()
-    x, dz = _require(x, "x"), _require(dz, "dz")
-    if x.dim() != 4 or dz.dim() != 4:
-        raise L.KanConvError(f"split-precision bwd-weight: NCHW x and dz, got {tuple(x.shape)} and {tuple(dz.shape)}")
-    Ot, Ct = dz.shape[1], x.shape[1]
-    geom, basis, _ = _plan_cached(*_plan_key(spec, x.shape, Ot))
-    nbytes = lib.kan_split_bwd_weight_workspace_bytes(C.byref(geom), C.byref(basis)) if spec.groups == 1 and spec.has_base and not spec.first else 0
-    if not nbytes:
-        raise L.KanConvError("split-precision bwd-weight: default B-spline spec (grid 5, order 3, SiLU base branch), 8x8 or 16x16 planes, 3x3 / stride 1 / pad 1, one group, "
-                             "C % 8 == 0, O % 128 == 0, even batch on 8x8 planes only")
-    if tuple(dz.shape) != (geom.B, Ot, geom.Ho, geom.Wo):
-        raise L.KanConvError(f"split-precision bwd-weight: dz {tuple(dz.shape)} != {(geom.B, Ot, geom.Ho, geom.Wo)}")
-    shapes = ((Ot, Ct, 3, 3), (Ot, Ct * spec.n_basis, 3, 3))
-    with torch.cuda.device(x.device):
-        if out is None:
-            out = tuple(torch.empty(sh, device=x.device, dtype=torch.float32) for sh in shapes)
-        elif any(tuple(t.shape) != sh or t.dtype != torch.float32 or t.device != x.device or not t.is_contiguous() for t, sh in zip(out, shapes)):
-            raise L.KanConvError(f"split-precision bwd-weight: out must be contiguous fp32 tensors {shapes} on {x.device}")
-        ws = torch.empty(nbytes, device=x.device, dtype=torch.uint8)
-        L.check(lib.kan_conv_bwd_weight_split(_ptr(dz), _ptr(x), _ptr(out[0]), _ptr(out[1]), C.c_void_p(ws.data_ptr()), C.byref(geom), C.byref(basis), _stream(x)),
-                "kan_conv_bwd_weight_split")
-    return out[0], out[1]
 
 
 def instance_norm(x: torch.Tensor, gamma: Optional[torch.Tensor] = None, beta: Optional[torch.Tensor] = None, eps: float = 1e-5):

@@ -11,6 +11,7 @@ Measured on an MI355X (max-normalised dx error against fp64: split kernel / exac
    64 -> 256 @ 8x8,   B 2:  2.0e-6 / 2.8e-7 / 3.2e-7;  2.1e-6       64 -> 128 @ 16x16, B 2:  9.1e-7 / 3.1e-7 / 2.9e-7;  1.0e-6
   256 -> 256 @ 8x8,   B 2:  9.5e-7 / 3.1e-7 / 2.3e-7;  9.5e-7
 KAN-VGG11, bs 8, inside the context: weight gradients of the layers before the 256 -> 256 @ 8x8 layer 0.7 - 1.4e-6 (max-normalised) from the exact step's."""
+import contextlib
 import copy
 import ctypes as C
 
@@ -18,16 +19,12 @@ import pytest
 import torch
 
 from helpers import TOL_DX, relerr
+from split_cells import same_but_slopes, spies, vgg_step
+from split_cells import split_layer as _layer
 
 pytestmark = pytest.mark.gpu
 
 SHAPES = [(8, 128, 2, 8), (16, 128, 4, 8), (64, 256, 2, 8), (256, 256, 2, 8), (8, 128, 1, 16), (24, 128, 3, 16), (64, 128, 2, 16)]
-
-
-def _layer(C_, O_):
-    import convkan_amd as K
-    layer = K.KANConv2DLayer(C_, O_, 3, padding=1, base_activation=torch.nn.SiLU).cuda()      # (as models/kan_vgg.py builds it)
-    return layer, layer.conv_spec(), layer.base_conv[0].weight.detach(), layer.spline_conv[0].weight.detach()
 
 
 def _exact_dx(spec, x, dz, wb, ws):
@@ -144,13 +141,6 @@ def test_nothing_outside_dx_is_written(C_, O_, B, PW, gpu_lib):
     assert bool((big[:pad] == sentinel).all()) and bool((big[pad + n:] == sentinel).all())
 
 
-def _vgg_step(model, x, target):
-    model.zero_grad(set_to_none=True)
-    y = model(x)
-    torch.nn.functional.cross_entropy(y, target).backward()
-    return y.detach().clone(), {n: p.grad.detach().clone() for n, p in model.named_parameters()}
-
-
 def test_context_on_kan_vgg11(gpu_lib):
     """Inside ops.split_precision_backward_data() one training step of KAN-VGG11 runs the split launch for exactly its 256 -> 256 @ 8x8, 128 -> 256 @ 8x8 and
     64 -> 128 @ 16x16 layers (backward order).  dx only feeds EARLIER layers: logits and every gradient from the 256 -> 256 layer onwards stay bit-equal to
@@ -161,43 +151,31 @@ def test_context_on_kan_vgg11(gpu_lib):
     m = vggkan(3, 10, arch="VGG11", kan_conv="KAN", dropout_linear=0.0).cuda().train()
     x = torch.randn(8, 3, 32, 32, device="cuda")
     t = torch.randint(0, 10, (8,), device="cuda")
-    calls = []
-    orig = ops.kan_conv_bwd_data_split
-    ops.kan_conv_bwd_data_split = lambda *a, **k: (calls.append(tuple(a[1].shape)), orig(*a, **k))[1]
-    try:
-        y0, g0 = _vgg_step(m, x, t)
+    with spies() as all_calls:
+        calls = all_calls["kan_conv_bwd_data_split"]
+        y0, g0 = vgg_step(m, x, t)
         assert calls == []
-        with ops.split_precision_backward_data():
-            y1, g1 = _vgg_step(m, x, t)
+        y1, g1 = vgg_step(m, x, t, ops.split_precision_backward_data())
         assert calls == [(8, 256, 8, 8), (8, 128, 8, 8), (8, 64, 16, 16)], calls
         assert torch.equal(y0, y1)
         late = [n for n in g0 if not n.startswith("features.") or int(n.split(".")[1]) >= 5]      # features.5 is the 256 -> 256 @ 8x8 layer
         early = [n for n in g0 if n not in late]
-        # The scalar PReLU slopes are summed by float atomics across workgroups: their order, and so their last bits, differ between two runs of the
-        # EXACT step as well.  Every other late gradient must be bit-equal; the slopes are judged together under the project's bound for these
-        # scalars (helpers.check_vs_oracle: 2e-5, max-normalised), far below anything a changed dz would leave.
-        slopes = [n for n in late if g0[n].numel() == 1]
-        exact_late = [n for n in late if n not in slopes]
-        assert exact_late and early and all(torch.equal(g0[n], g1[n]) for n in exact_late), [n for n in exact_late if not torch.equal(g0[n], g1[n])]
-        e_slopes = relerr(torch.cat([g1[n].reshape(-1) for n in slopes]), torch.cat([g0[n].reshape(-1) for n in slopes]))
+        # Every late gradient must be bit-equal but the scalar PReLU slopes (atomic sums: split_cells.same_but_slopes), which are judged together under the
+        # project's bound for these scalars (helpers.check_vs_oracle: 2e-5, max-normalised), far below anything a changed dz would leave.
+        assert early
+        e_slopes = same_but_slopes(g0, g1, late)
         print(f"[split bwd-data KAN-VGG11 bs 8] late PReLU slope gradients vs the exact step (atomic sums, judged together): {e_slopes:.1e}")
-        assert e_slopes <= 2e-5, e_slopes
         assert all(bool(torch.isfinite(g1[n]).all()) for n in early) and not all(torch.equal(g0[n], g1[n]) for n in early)
         print("[split bwd-data KAN-VGG11 bs 8] gradient distance from the exact step (max-normalised): "
               + "  ".join(f"{n} {relerr(g1[n], g0[n]):.1e}" for n in early if g0[n].dim() == 4))
         n_calls = len(calls)
-        with ops.split_precision_inference():                             # outside the context: the exact step bit for bit
-            y2, g2 = _vgg_step(m, x, t)
-        assert len(calls) == n_calls and torch.equal(y0, y2) and all(torch.equal(g0[n], g2[n]) for n in g0 if g0[n].numel() > 1)
-        assert relerr(torch.cat([g2[n].reshape(-1) for n in g0 if g0[n].numel() == 1]), torch.cat([g0[n].reshape(-1) for n in g0 if g0[n].numel() == 1])) <= 2e-5
-        m.zero_grad(set_to_none=True)
-        with ops.split_precision_backward_data():                         # decided at forward time ...
-            loss = torch.nn.functional.cross_entropy(m(x), t)
-        loss.backward()                                                   # ... so a backward outside still runs the split kernel
+        y2, g2 = vgg_step(m, x, t, ops.split_precision_inference())       # outside the context: the exact step bit for bit
+        assert len(calls) == n_calls and torch.equal(y0, y2)
+        same_but_slopes(g0, g2, list(g0))
+        y3, g3 = vgg_step(m, x, t, ops.split_precision_backward_data(), contextlib.nullcontext())      # decided at forward time: a backward outside still runs the split kernel
         assert len(calls) == n_calls + 3
-        assert all(torch.equal(g1[n], p.grad) for n, p in m.named_parameters() if p.numel() > 1)
-    finally:
-        ops.kan_conv_bwd_data_split = orig
+        assert all(torch.equal(g1[n], g3[n]) for n in g1 if g1[n].numel() > 1)
+        assert all(c == [] for n, c in all_calls.items() if n != "kan_conv_bwd_data_split"), all_calls
 
 
 def test_graphed_steps_inside_the_context_equal_eager_steps_bitwise(gpu_lib):

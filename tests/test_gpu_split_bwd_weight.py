@@ -19,6 +19,10 @@ import pytest
 import torch
 
 from helpers import TOL_DW, relerr
+from split_cells import same_but_slopes as _same_but_slopes
+from split_cells import spies
+from split_cells import split_layer as _layer
+from split_cells import vgg_step as _vgg_step
 
 pytestmark = pytest.mark.gpu
 
@@ -34,12 +38,6 @@ SHAPES = [(8, 128, 2, 8), (16, 128, 4, 8), (64, 256, 2, 8), (256, 256, 2, 8), (8
 #   (64, 256, 10, 16)   8 units on KS = 4: upper and lower half of an octet (the row offset moves, the octet stays)
 MULTI_UNIT = [(8, 128, 264, 8), (64, 256, 34, 8), (256, 256, 24, 8), (8, 128, 72, 16), (64, 256, 10, 16)]
 IN_CONTEXT = [(8, 256, 8, 8), (8, 128, 8, 8), (8, 64, 16, 16)]        # x shapes of the KAN-VGG11 bs-8 layers the context takes, in backward order
-
-
-def _layer(C_, O_):
-    import convkan_amd as K
-    layer = K.KANConv2DLayer(C_, O_, 3, padding=1, base_activation=torch.nn.SiLU).cuda()      # (as models/kan_vgg.py builds it)
-    return layer, layer.conv_spec(), layer.base_conv[0].weight.detach(), layer.spline_conv[0].weight.detach()
 
 
 def _exact_dw(spec, x, dz, wb, ws):
@@ -172,24 +170,6 @@ def test_split_bwd_weight_scope_is_enforced(gpu_lib):
             ops.kan_conv_bwd_weight_split(layer.conv_spec(), x, dz)
 
 
-def _vgg_step(model, x, target):
-    model.zero_grad(set_to_none=True)
-    y = model(x)
-    torch.nn.functional.cross_entropy(y, target).backward()
-    return y.detach().clone(), {n: p.grad.detach().clone() for n, p in model.named_parameters()}
-
-
-def _same_but_slopes(g0, g1, names):
-    """Bit-equal on every tensor of `names` with more than one element.  The scalar PReLU slopes are summed by float atomics across workgroups (their last
-    bits differ between two runs of the EXACT step as well): judged together under the project's bound for these scalars, 2e-5 max-normalised."""
-    slopes = [n for n in names if g0[n].numel() == 1]
-    others = [n for n in names if g0[n].numel() > 1]
-    assert others and all(torch.equal(g0[n], g1[n]) for n in others), [n for n in others if not torch.equal(g0[n], g1[n])]
-    e = relerr(torch.cat([g1[n].reshape(-1) for n in slopes]), torch.cat([g0[n].reshape(-1) for n in slopes]))
-    assert e <= 2e-5, e
-    return e
-
-
 def test_contexts_on_kan_vgg11(gpu_lib):
     """Inside ops.split_precision_backward_weight() one training step of KAN-VGG11 runs the split launch for exactly the layers of IN_CONTEXT (backward
     order).  A weight gradient feeds nothing else: logits and every other gradient stay bit-equal to the exact step, the six base / spline weight gradients
@@ -209,10 +189,8 @@ def test_contexts_on_kan_vgg11(gpu_lib):
             ids[id(mod.base_conv[0].weight)] = ids[id(mod.spline_conv[0].weight)] = True
     changed = [n for n, p in m.named_parameters() if id(p) in ids]
     assert len(changed) == 2 * len(IN_CONTEXT), changed
-    calls = []
-    orig = ops.kan_conv_bwd_weight_split
-    ops.kan_conv_bwd_weight_split = lambda *a, **k: (calls.append(tuple(a[1].shape)), orig(*a, **k))[1]
-    try:
+    with spies() as all_calls:
+        calls = all_calls["kan_conv_bwd_weight_split"]
         y0, g0 = _vgg_step(m, x, t)
         assert calls == []
         with ops.split_precision_backward_weight():
@@ -245,8 +223,6 @@ def test_contexts_on_kan_vgg11(gpu_lib):
         assert len(calls) == n_calls + 3 * len(IN_CONTEXT)
         _same_but_slopes(g3, g4, list(g3))
         assert any(not torch.equal(g3[n], g1[n]) for n in g1 if n not in changed)      # and the input gradient did go split as well
-    finally:
-        ops.kan_conv_bwd_weight_split = orig
 
 
 def test_graphed_steps_inside_the_context_equal_eager_steps_bitwise(gpu_lib):
@@ -339,7 +315,7 @@ def test_cut_weight_cache_entry_dies_with_its_weights(gpu_lib):
     with ops.split_precision_backward():
         layer(x).sum().backward()
     key = (layer.base_conv[0].weight.data_ptr(), layer.spline_conv[0].weight.data_ptr(), x.device.index)
-    assert key in ops._SPLIT_BWD_CACHE
+    assert key in ops._CUT_BWD_DATA.entries
     del layer
     gc.collect()
-    assert key not in ops._SPLIT_BWD_CACHE
+    assert key not in ops._CUT_BWD_DATA.entries

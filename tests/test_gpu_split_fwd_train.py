@@ -18,6 +18,11 @@ import pytest
 import torch
 
 from helpers import check_vs_oracle, relerr
+from split_cells import ENTRY_POINTS
+from split_cells import same_but_slopes as _same_but_slopes
+from split_cells import spies as _spies
+from split_cells import split_layer as _layer
+from split_cells import vgg_step as _vgg_step
 
 pytestmark = pytest.mark.gpu
 
@@ -25,32 +30,6 @@ SILU = torch.nn.SiLU
 BARE = [(8, 128, 2, 8), (128, 256, 4, 8), (256, 256, 2, 8), (16, 256, 2, 16), (64, 128, 3, 16)]       # C, O, B, plane (an odd batch is in scope on 16x16)
 LAYERS = [(8, 128, 2, 8), (64, 256, 2, 8), (16, 256, 2, 16), (64, 128, 2, 16)]
 IN_CONTEXT = [(8, 64, 16, 16), (8, 128, 8, 8), (8, 256, 8, 8)]        # x shapes of the KAN-VGG11 bs-8 layers the context takes, in forward order
-ENTRY_POINTS = ("kan_conv_fwd_split", "kan_conv_bwd_data_split", "kan_conv_bwd_weight_split")
-
-
-def _layer(C_, O_, **kw):
-    import convkan_amd as K
-    kw.setdefault("base_activation", SILU)
-    layer = K.KANConv2DLayer(C_, O_, 3, padding=1, **kw).cuda()      # (as models/kan_vgg.py builds it)
-    return layer, layer.conv_spec(), layer.base_conv[0].weight.detach(), layer.spline_conv[0].weight.detach()
-
-
-@contextlib.contextmanager
-def _spies():
-    """Record the x shape of every call of the three module-level split entry points."""
-    from convkan_amd import ops
-    calls = {n: [] for n in ENTRY_POINTS}
-    orig = {n: getattr(ops, n) for n in ENTRY_POINTS}
-
-    def spy(name):
-        return lambda *a, **k: (calls[name].append(tuple(a[1].shape)), orig[name](*a, **k))[1]
-    for n in ENTRY_POINTS:
-        setattr(ops, n, spy(n))
-    try:
-        yield calls
-    finally:
-        for n in ENTRY_POINTS:
-            setattr(ops, n, orig[n])
 
 
 def _bare(spec, x, dz, wb, ws, ctx):
@@ -144,30 +123,6 @@ def test_layer_inside_the_context_vs_fp64_oracle(C_, O_, B, PW, norm, gpu_lib):
 
 
 # ------------------------------------------------------------------------------------------ C: KAN-VGG11
-def _vgg_step(model, x, target, fwd_ctx=None, bwd_ctx=None):
-    model.zero_grad(set_to_none=True)
-    with fwd_ctx if fwd_ctx is not None else contextlib.nullcontext():
-        y = model(x)
-        loss = torch.nn.functional.cross_entropy(y, target)
-        if bwd_ctx is None:                                               # the whole step inside the forward's context
-            loss.backward()
-    if bwd_ctx is not None:
-        with bwd_ctx:
-            loss.backward()
-    return y.detach().clone(), {n: p.grad.detach().clone() for n, p in model.named_parameters()}
-
-
-def _same_but_slopes(g0, g1, names):
-    """Bit-equal on every tensor of `names` with more than one element.  The scalar PReLU slopes are summed by float atomics across workgroups (their last
-    bits differ between two runs of the EXACT step as well): judged together under the project's bound for these scalars, 2e-5 max-normalised."""
-    slopes = [n for n in names if g0[n].numel() == 1]
-    others = [n for n in names if g0[n].numel() > 1]
-    assert others and all(torch.equal(g0[n], g1[n]) for n in others), [n for n in others if not torch.equal(g0[n], g1[n])]
-    if slopes:
-        e = relerr(torch.cat([g1[n].reshape(-1) for n in slopes]), torch.cat([g0[n].reshape(-1) for n in slopes]))
-        assert e <= 2e-5, e
-
-
 def test_contexts_on_kan_vgg11(gpu_lib):
     """One training step of KAN-VGG11 (bs 8) inside ops.split_precision_forward() runs the split forward for exactly the layers of IN_CONTEXT and no split
     backward; its logits are those of split_precision_inference under no_grad bit for bit, within 1e-4 of the exact step's (SURVEY 8(c)'s model tolerance);
@@ -302,7 +257,7 @@ def test_cut_weights_follow_the_optimizer_and_train_step_is_the_context(gpu_lib)
             z2 = ops.kan_conv(spec, x, None, [wb], [ws])
         assert torch.equal(z2, ops.kan_conv_fwd_split(spec, x, wb.detach().clone(), ws.detach().clone())[0]) and not torch.equal(z2, z)
         assert bool(torch.isfinite(loss2)) and float(loss2) != float(loss)
-    assert ops._SPLIT_FWD is False and ops._SPLIT_BWD_DATA is False and ops._SPLIT_BWD_WEIGHT is False
+    assert ops._SPLIT == ops.SplitMode()
 
 
 # ------------------------------------------------------------------------------------------ F: a recorded step
@@ -328,7 +283,7 @@ def test_graphed_steps_with_split_precision_equal_eager_steps_bitwise(gpu_lib):
                     losses.append(float(K.train_step(model, d, t, opt)))
         elif mode == "graph":
             step = K.GraphedStep(model, batches[0][0], batches[0][1], split_precision=True)
-            assert ops._SPLIT_FWD is False and ops._SPLIT_BWD_DATA is False and ops._SPLIT_BWD_WEIGHT is False
+            assert ops._SPLIT == ops.SplitMode()
             for d, t in batches:
                 losses.append(float(step(d, t)))
                 opt.step()
@@ -373,7 +328,7 @@ def test_forward_cut_weight_cache_entry_dies_with_its_weights(gpu_lib):
         with torch.no_grad(), ctx():
             layer(x)
         key = (layer.base_conv[0].weight.data_ptr(), layer.spline_conv[0].weight.data_ptr(), x.device.index)
-        assert key in ops._SPLIT_CACHE
+        assert key in ops._CUT_FWD.entries
         del layer
         gc.collect()
-        assert key not in ops._SPLIT_CACHE
+        assert key not in ops._CUT_FWD.entries

@@ -402,20 +402,21 @@ def test_alexnet_plain_pool_detection():
 
 
 def test_opt_in_switches_restore_their_flags_and_pool_arguments_are_checked():
-    """ops.always_pack / ops.split_precision_inference are context managers that leave no state behind (also on an exception); the fused-pool argument
-    takes True, False or a (kernel, stride) pair with 2 <= kernel <= 15, 1 <= stride <= kernel."""
+    """ops.always_pack / ops.split_precision_inference are context managers that leave no state behind (also on an exception; every split-precision
+    context, every nesting: tests/test_split_host.py); the fused-pool argument takes True, False or a (kernel, stride) pair with 2 <= kernel <= 15,
+    1 <= stride <= kernel."""
     from convkan_amd import ops
-    assert ops._ALWAYS_PACK is False and ops._SPLIT_INFERENCE is False
+    assert ops._ALWAYS_PACK is False and ops._SPLIT.inference is False
     with ops.always_pack():
         assert ops._ALWAYS_PACK is True
         with ops.split_precision_inference():
-            assert ops._SPLIT_INFERENCE is True
-        assert ops._SPLIT_INFERENCE is False
+            assert ops._SPLIT.inference is True and ops._ALWAYS_PACK is True
+        assert ops._SPLIT.inference is False
     assert ops._ALWAYS_PACK is False
     with pytest.raises(RuntimeError):
-        with ops.split_precision_inference():
+        with ops.always_pack(), ops.split_precision_inference():
             raise RuntimeError("x")
-    assert ops._SPLIT_INFERENCE is False
+    assert ops._SPLIT.inference is False and ops._ALWAYS_PACK is False
     assert ops._norm_pool(False) is False and ops._norm_pool(True) is True and ops._norm_pool((3, 2)) == (3, 2) and ops._norm_pool([2, 2]) == (2, 2)
     for bad in ((1, 1), (3, 4), (16, 2), (3, 0)):
         with pytest.raises(L.KanConvError):

@@ -1,5 +1,6 @@
 """CPU: the host side of the OPT-IN split-precision input gradient (kan_conv_bwd_data_split) -- the three exports, the byte count of
-the cut weights against a restatement of their layout, refusals that need no device, the context switch, and the arithmetic itself emulated in torch:
+the cut weights against a restatement of their layout, refusals that need no device, and the arithmetic itself emulated in torch (the context switch:
+tests/test_split_host.py):
 three bf16 pieces per operand and the kernel's six products (summed smallest first) against fp64, next to the three-product form that is NOT enough."""
 import ctypes as C
 import os
@@ -11,24 +12,11 @@ import torch.nn.functional as F
 
 import convkan_amd as K
 from convkan_amd import _lib as L
-from convkan_amd import ops
 from conftest import ROOT
+from split_cells import OUT_OF_SCOPE
+from split_cells import geom_basis as _gb
 
 NEW = ("kan_split_bwd_data_weight_bytes", "kan_split_pack_weights_bwd_data", "kan_conv_bwd_data_split")
-
-
-def _gb(C_, O_, H, B=2, nb=8, act=L.ACT_SILU):
-    """(geom, basis) as the ops build them for a 3x3 / stride 1 / pad 1 B-spline layer."""
-    table = tuple(float(v) for v in torch.linspace(-2.2, 2.2, nb + 4).tolist())
-    spec = ops.ConvSpec(kind=L.BASIS_BSPLINE, n_basis=nb, order=3, act=act, p0=0.0, p1=0.0, table=table, kernel=(3, 3), stride=(1, 1),
-                        padding=(1, 1), dilation=(1, 1))
-    g, b, _ = ops._plan_cached(spec, B, C_, H, H, O_, C_, O_)
-    return g, b
-
-
-# the out-of-scope cases of test_gpu_split.py::test_split_forward_scope_is_enforced
-OUT_OF_SCOPE = [dict(C_=16, O_=128, H=4), dict(C_=16, O_=128, H=8, nb=11), dict(C_=16, O_=64, H=8), dict(C_=16, O_=128, H=8, B=3),
-                dict(C_=16, O_=128, H=8, act=L.ACT_GELU)]
 
 
 def test_three_symbols_declared_bound_and_exported():
@@ -105,17 +93,3 @@ def test_six_products_reach_fp32_and_three_do_not(C_, O_, B, PW):
     e3 = float((three.double() - ref).abs().max()) / scale
     print(f"[split bwd-data emulation {C_}->{O_} @{PW}x{PW} B={B}] six products {e6:.2e}  three products {e3:.2e}")
     assert e6 <= 1e-6 < e3, (e6, e3)
-
-
-def test_context_switch_restores_its_flag():
-    assert ops._SPLIT_BWD_DATA is False
-    with ops.split_precision_backward_data():
-        assert ops._SPLIT_BWD_DATA is True
-        with ops.split_precision_backward_data():
-            assert ops._SPLIT_BWD_DATA is True
-        assert ops._SPLIT_BWD_DATA is True
-    assert ops._SPLIT_BWD_DATA is False
-    with pytest.raises(RuntimeError):
-        with ops.split_precision_backward_data():
-            raise RuntimeError("x")
-    assert ops._SPLIT_BWD_DATA is False

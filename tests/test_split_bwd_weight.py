@@ -1,6 +1,6 @@
 """CPU: the host side of the OPT-IN split-precision weight gradient (kan_conv_bwd_weight_split) -- the two exports, the workspace size
-against a restatement of the layout the header documents, refusals that need no device, the context switches, and the arithmetic itself emulated in torch on
-real plane values: three bf16 pieces per operand and the kernel's six products (summed smallest first) against fp64, next to the three-product form that is
+against a restatement of the layout the header documents, refusals that need no device, and the arithmetic itself emulated in torch on real plane values (the
+context switches: tests/test_split_host.py): three bf16 pieces per operand and the kernel's six products (summed smallest first) against fp64, next to the three-product form that is
 NOT enough."""
 import ctypes as C
 import os
@@ -12,24 +12,11 @@ import torch.nn.functional as F
 
 import convkan_amd as K
 from convkan_amd import _lib as L
-from convkan_amd import ops
 from conftest import ROOT
+from split_cells import OUT_OF_SCOPE
+from split_cells import geom_basis as _gb
 
 NEW = ("kan_split_bwd_weight_workspace_bytes", "kan_conv_bwd_weight_split")
-
-
-def _gb(C_, O_, H, B=2, nb=8, act=L.ACT_SILU):
-    """(geom, basis) as the ops build them for a 3x3 / stride 1 / pad 1 B-spline layer."""
-    table = tuple(float(v) for v in torch.linspace(-2.2, 2.2, nb + 4).tolist())
-    spec = ops.ConvSpec(kind=L.BASIS_BSPLINE, n_basis=nb, order=3, act=act, p0=0.0, p1=0.0, table=table, kernel=(3, 3), stride=(1, 1),
-                        padding=(1, 1), dilation=(1, 1))
-    g, b, _ = ops._plan_cached(spec, B, C_, H, H, O_, C_, O_)
-    return g, b
-
-
-# the out-of-scope cases of test_split_bwd_data.py: 4x4 planes, another spec, 64 outputs, odd batch on 8x8, GELU base branch
-OUT_OF_SCOPE = [dict(C_=16, O_=128, H=4), dict(C_=16, O_=128, H=8, nb=11), dict(C_=16, O_=64, H=8), dict(C_=16, O_=128, H=8, B=3),
-                dict(C_=16, O_=128, H=8, act=L.ACT_GELU)]
 
 
 def test_two_symbols_declared_bound_and_exported():
@@ -110,29 +97,3 @@ def test_six_products_reach_fp32_and_three_do_not(C_, O_, B, PW):
     e3 = float((three.double() - ref).abs().max()) / scale
     print(f"[split bwd-weight emulation {C_}->{O_} @{PW}x{PW} B={B}] six products {e6:.2e}  three products {e3:.2e}")
     assert e6 <= 1e-6 < e3, (e6, e3)
-
-
-def test_context_switches_restore_their_flags():
-    assert ops._SPLIT_BWD_WEIGHT is False and ops._SPLIT_BWD_DATA is False
-    with ops.split_precision_backward_weight():
-        assert ops._SPLIT_BWD_WEIGHT is True and ops._SPLIT_BWD_DATA is False
-        with ops.split_precision_backward_weight():
-            assert ops._SPLIT_BWD_WEIGHT is True
-        assert ops._SPLIT_BWD_WEIGHT is True
-    assert ops._SPLIT_BWD_WEIGHT is False
-    with pytest.raises(RuntimeError):
-        with ops.split_precision_backward_weight():
-            raise RuntimeError("x")
-    assert ops._SPLIT_BWD_WEIGHT is False
-    with ops.split_precision_backward():
-        assert ops._SPLIT_BWD_WEIGHT is True and ops._SPLIT_BWD_DATA is True
-        with ops.split_precision_backward():
-            assert ops._SPLIT_BWD_WEIGHT is True and ops._SPLIT_BWD_DATA is True
-        assert ops._SPLIT_BWD_WEIGHT is True and ops._SPLIT_BWD_DATA is True
-    assert ops._SPLIT_BWD_WEIGHT is False and ops._SPLIT_BWD_DATA is False
-    with ops.split_precision_backward_data():                 # the combined context restores what it found, not False
-        with pytest.raises(RuntimeError):
-            with ops.split_precision_backward():
-                raise RuntimeError("x")
-        assert ops._SPLIT_BWD_WEIGHT is False and ops._SPLIT_BWD_DATA is True
-    assert ops._SPLIT_BWD_WEIGHT is False and ops._SPLIT_BWD_DATA is False
