@@ -112,8 +112,7 @@ __global__ __launch_bounds__(256) void k_fingerprint(const float* __restrict__ a
     // `s_waitcnt vmcnt(0)` behind every load it has to branch around, which left one load in flight: 1.2 TB/s)
     auto pass = [&](const float* __restrict__ src, unsigned n, unsigned pos_base) {
         const unsigned nfull = n / 4u, ngr = (nfull + stride - 1u) / stride;             // sampled whole groups
-        if (ngr == 0u) return;
-        for (unsigned i0 = tid0; i0 < ngr; i0 += nthreads * U) {
+        for (unsigned i0 = tid0; i0 < ngr; i0 += nthreads * U) {       // (a tensor of fewer than four elements has no whole group, only a tail)
             float4 v[U]; unsigned e[U]; bool ok[U];
 #pragma unroll
             for (int u = 0; u < U; ++u) {
