@@ -29,10 +29,11 @@ import os
 import weakref
 from collections import OrderedDict
 from dataclasses import dataclass, replace
-from functools import lru_cache, partial
+from functools import lru_cache, partial, wraps
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
+from torch.autograd.function import once_differentiable
 
 from . import _lib as L
 
@@ -156,12 +157,25 @@ def _stream(t: torch.Tensor) -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
-def _require(t: torch.Tensor, name: str) -> torch.Tensor:
+def _dense(t: torch.Tensor) -> torch.Tensor:
+    """`t` itself when it is contiguous and starts on a 16-byte boundary, else a copy that is (torch's allocator hands out 256-byte aligned blocks).
+    What the kernels may assume of every activation and incoming-gradient pointer: the library picks its 8- and 16-byte
+    routes from the pointers it is given (the norm kernels' float2 variants, the quadrant forward), so a view that starts 4 bytes into its storage
+    would take another kernel than the same values in a tensor of their own; after this it takes the same one."""
+    t = t.contiguous()
+    return t.clone() if t.data_ptr() & 15 else t
+
+
+def _require(t: torch.Tensor, name: str, align: bool = True) -> torch.Tensor:
+    """`t` as the kernels read it: on a ROCm device, fp32, contiguous and (`align`) 16-byte aligned -- refused or copied on the host, before any launch.
+    `align=False`: the conv weights, whose alignment `_pack` itself looks at (a copy here would hide the Parameter the cache is keyed by)."""
+    if not isinstance(t, torch.Tensor):
+        raise L.KanConvError(f"{name} must be a tensor, got {type(t).__name__}")
     if not t.is_cuda:
         raise L.KanConvError(f"{name} is on {t.device}: this path runs only on a ROCm device (MI355X); there is no CPU fallback")
     if t.dtype != torch.float32:
         raise L.KanConvError(f"{name} must be float32, got {t.dtype}")
-    return t.contiguous()
+    return _dense(t) if align else t.contiguous()
 
 
 def _split_weights(spec: ConvSpec, weights: Sequence[torch.Tensor]):
@@ -867,6 +881,28 @@ def _save(ctx, **named) -> None:
     ctx.save_for_backward(*(t for t in named.values() if t is not None))
 
 
+def _once(backward):
+    """`once_differentiable` for the backwards of this module, which run raw kernels: differentiating what they return raises torch's
+    once-differentiable error instead of silently treating it as a constant.  torch's decorator attaches that error only when an incoming gradient
+    carries a graph; under create_graph=True (grad mode is then on in here) with plain incoming gradients -- `autograd.grad(y.sum(), x, create_graph=True)`,
+    the gradient-penalty idiom -- the returned gradients would carry no graph and a penalty term added to a loss would contribute nothing, with no
+    error.  So in that case the incoming gradients are made to require one."""
+    inner = once_differentiable(backward)
+
+    @wraps(backward)
+    def wrapper(ctx, *grads):
+        if torch.is_grad_enabled() and not any(g is not None and g.requires_grad for g in grads):
+            grads = tuple(g.detach().requires_grad_(True) if g is not None else None for g in grads)
+        return inner(ctx, *grads)
+    return wrapper
+
+
+def _asked(ctx, grads: tuple) -> tuple:
+    """What a backward returns: `grads` with None in every position whose input did not ask for a gradient (ctx.needs_input_grad) -- a kernel that fills
+    several gradients at once (the norm parameters, the wavelet parameters, all weight groups) hands back only those that were asked for."""
+    return tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad))
+
+
 def _saved(ctx, *names):
     """The tensors `_save` kept under `names` (None for one that was None), in that order."""
     kept = dict(zip(ctx.saved_names, ctx.saved_tensors))
@@ -893,7 +929,7 @@ class _KanConv(torch.autograd.Function):
     def forward(ctx, spec: ConvSpec, split: bool, x, xn, phases, *weights):
         x = _require(x, "x")
         xn = _require(xn, "xn") if xn is not None else None
-        weights = [_require(w, "weight") for w in weights]
+        weights = [_require(w, "weight", align=False) for w in weights]
         w_base, w_basis = _split_weights(spec, weights)
         if spec.w_layout == W_IOD:
             want = (x.shape[1], w_basis[0].shape[1] if w_basis[0].dim() == 3 else -1, spec.n_basis)
@@ -917,13 +953,14 @@ class _KanConv(torch.autograd.Function):
         return z
 
     @staticmethod
+    @_once
     def backward(ctx, dz):
         spec, G = ctx.spec, ctx.spec.groups
         x, xn, phases, wd, x_pm, wcd, *w_basis = _saved(ctx, "x", "xn", "phases", "wd", "x_pm", "wcd", *(f"w_basis{g}" for g in range(G)))
         packed = (wd, x_pm)
         need_x, need_xn = ctx.needs_input_grad[2], xn is not None and ctx.needs_input_grad[3]
         need_p, need_w = ctx.needs_input_grad[4], any(ctx.needs_input_grad[5:])
-        dz = dz.contiguous()
+        dz = _dense(dz)
         dph = None
         with torch.cuda.device(x.device):
             # ReLU-KAN / Gram: when the input gradient is computed anyway, its launch also accumulates the parameter gradients from the same G tiles
@@ -948,7 +985,7 @@ class _KanConv(torch.autograd.Function):
                     dph = torch.zeros_like(phases)
                     for mode in range(1, n - 1):
                         dph[mode + 1] = factor(mode).sum()
-        return (None, None, dx if need_x else None, dxn if need_xn else None, dph) + _flat_grads(spec, dwb, dws)
+        return _asked(ctx, (None, None, dx, dxn, dph) + _flat_grads(spec, dwb, dws))
 
 
 def _cat(ts: Sequence[Optional[torch.Tensor]]) -> Optional[torch.Tensor]:
@@ -992,6 +1029,8 @@ def _norm_fwd(zs, slab_elems: int, gamma, beta, slope, eps: float, groups: int =
     lib = L.load()
     S, z = (1, zs) if zs.dim() == 4 else (zs.shape[0], zs[0])
     B, Ct, Ho, Wo = z.shape
+    if z.numel() == 0:                                  # refused here, not by an empty grid (the conv stages stop in kan_plan, the loss at B < 1)
+        raise L.KanConvError(f"the norm kernels take a non-empty tensor, got {tuple(z.shape)}")
     HW, span, st = Ho * Wo, (Ct // groups if groups > 1 else 0), _stream(zs)
     mean = torch.empty(B * Ct if bn is None else Ct, device=zs.device, dtype=torch.float32)
     rstd = torch.empty_like(mean)
@@ -1005,7 +1044,7 @@ def _norm_fwd(zs, slab_elems: int, gamma, beta, slope, eps: float, groups: int =
             raise ValueError(f"Expected more than 1 value per channel when training, got input size {tuple(z.shape)}")
         for t in (bn.running_mean, bn.running_var):
             if t is not None and (_require(t, "running statistics") is not t or t.numel() != Ct):
-                raise L.KanConvError(f"running statistics must be contiguous [{Ct}] tensors")
+                raise L.KanConvError(f"running statistics must be contiguous, 16-byte aligned [{Ct}] tensors (the kernels update them in place)")
         y = torch.empty((B, Ct, Ho // 2, Wo // 2) if pool else z.shape, device=zs.device, dtype=torch.float32)
         pidx = torch.empty(y.shape, device=zs.device, dtype=torch.uint8) if pool else None
         L.check(lib.kan_batchnorm_prelu_fwd(_ptr(zs), S, slab_elems, _ptr(z), _ptr(gamma), _ptr(beta), _ptr(slope), _ptr(y),
@@ -1038,7 +1077,7 @@ def _norm_fwd(zs, slab_elems: int, gamma, beta, slope, eps: float, groups: int =
 def _norm_bwd(dy, z, mean, rstd, gamma, beta, slope, pidx, groups: int = 1, pool=False, *, bn: Optional[BatchStats] = None):
     """Backward of `_norm_fwd` from what it returned.  Returns (dz, dgamma, dbeta, dslope), None for a parameter that is None."""
     lib = L.load()
-    dy = dy.contiguous()
+    dy = _dense(dy)
     B, Ct, Ho, Wo = z.shape
     HW, span, st = Ho * Wo, (Ct // groups if groups > 1 else 0), _stream(z)
     dz = torch.empty_like(z)
@@ -1073,9 +1112,9 @@ class _KanConvInPrelu(torch.autograd.Function):
     @staticmethod
     def forward(ctx, spec: ConvSpec, eps: float, use_affine: bool, use_prelu: bool, pool, split: bool, bn, x, *params):
         x = _require(x, "x")
-        params = [_require(p, "parameter") for p in params]
         G = spec.groups
         nw = G * (2 if spec.has_base else 1)
+        params = [_require(p, "parameter", align=i >= nw) for i, p in enumerate(params)]
         w_base, w_basis = _split_weights(spec, params[:nw])
         rest = params[nw:]
         gammas = rest[:G] if use_affine else [None] * G
@@ -1095,6 +1134,7 @@ class _KanConvInPrelu(torch.autograd.Function):
         return y
 
     @staticmethod
+    @_once
     def backward(ctx, dy):
         spec, G = ctx.spec, ctx.spec.groups
         x, z, mean, rstd, wd, x_pm, gamma, beta, slope, pidx, wcd = _saved(ctx, "x", "z", "mean", "rstd", "wd", "x_pm", "gamma", "beta", "slope", "pidx", "wcd")
@@ -1109,7 +1149,7 @@ class _KanConvInPrelu(torch.autograd.Function):
             grads += tuple(dgam.view(G, -1).unbind(0)) + tuple(dbet.view(G, -1).unbind(0))
         if slope is not None:
             grads += tuple(dpre.view(G, 1).unbind(0))
-        return (None, None, None, None, None, None, None, dx if need_x else None) + grads
+        return _asked(ctx, (None, None, None, None, None, None, None, dx) + grads)
 
 
 class _InstanceNorm(torch.autograd.Function):
@@ -1118,6 +1158,15 @@ class _InstanceNorm(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, eps: float, bn=None):
         x = _require(x, "x")
+        if x.dim() != 4:
+            raise L.KanConvError(f"the norm ops take an NCHW tensor, got {tuple(x.shape)}")
+        # the public `instance_norm` / `batch_norm`: gamma and beta are the caller's tensors, validated like every other one (a strided view would be
+        # read as if it were dense, an fp64 one as fp32, a host address handed to a kernel, a short one read past its end)
+        gamma = _require(gamma, "gamma") if gamma is not None else None
+        beta = _require(beta, "beta") if beta is not None else None
+        for t, n in ((gamma, "gamma"), (beta, "beta")):
+            if t is not None and (t.device != x.device or t.numel() != x.shape[1]):
+                raise L.KanConvError(f"{n} must hold {x.shape[1]} values on {x.device}, got {tuple(t.shape)} on {t.device}")
         with torch.cuda.device(x.device):
             y, _, mean, rstd, _ = _norm_fwd(x, 0, gamma, beta, None, eps, bn=bn)
         ctx.bn = bn
@@ -1125,11 +1174,12 @@ class _InstanceNorm(torch.autograd.Function):
         return y
 
     @staticmethod
+    @_once
     def backward(ctx, dy):
         x, mean, rstd, gamma, beta = _saved(ctx, "x", "mean", "rstd", "gamma", "beta")
         with torch.cuda.device(x.device):
             dx, dg, db, _ = _norm_bwd(dy, x, mean, rstd, gamma, beta, None, None, bn=ctx.bn)
-        return dx, dg, db, None, None
+        return _asked(ctx, (dx, dg, db, None, None))
 
 
 # --------------------------------------------------------------------------------------- Wav-KAN wavelet stage
@@ -1151,7 +1201,9 @@ class _WavStage(torch.autograd.Function):
     @staticmethod
     def forward(ctx, wavelet, stride, padding, dilation, x, scale, trans, w):
         lib = L.load()
-        x, scale, trans, w = (_require(t, n).contiguous() for t, n in ((x, "x"), (scale, "scale"), (trans, "translation"), (w, "wavelet weights")))
+        x, scale, trans, w = (_require(t, n) for t, n in ((x, "x"), (scale, "scale"), (trans, "translation"), (w, "wavelet weights")))
+        if x.dim() != 4 or w.dim() != 4 or x.numel() == 0:
+            raise L.KanConvError(f"the wavelet stage takes a non-empty NCHW input and [O, C, kh, kw] weights, got {tuple(x.shape)} and {tuple(w.shape)}")
         if scale.shape != (w.shape[0], w.shape[1]) or trans.shape != scale.shape or w.shape[1] != x.shape[1]:
             raise L.KanConvError(f"wavelet parameter shapes {tuple(scale.shape)}, {tuple(trans.shape)}, {tuple(w.shape)} do not match input {tuple(x.shape)}")
         geom = _WavStage._geom(wavelet, x, w, stride, padding, dilation)
@@ -1162,11 +1214,12 @@ class _WavStage(torch.autograd.Function):
         return u
 
     @staticmethod
+    @_once
     def backward(ctx, du):
         lib = L.load()
         x, scale, trans, w = ctx.saved_tensors
         geom = ctx.geom
-        du = du.contiguous()
+        du = _dense(du)
         st = _stream(x)
         dx = dscale = dtrans = dw = None
         if ctx.needs_input_grad[4]:
@@ -1177,7 +1230,7 @@ class _WavStage(torch.autograd.Function):
             dw, dscale, dtrans = torch.empty_like(w), torch.empty_like(scale), torch.empty_like(trans)
             L.check(lib.kan_wav_bwd_params(_ptr(du), _ptr(x), _ptr(scale), _ptr(trans), _ptr(w), _ptr(dw), _ptr(dscale), _ptr(dtrans), _ptr(ws),
                                            C.byref(geom), st), "kan_wav_bwd_params")
-        return None, None, None, None, dx, dscale, dtrans, dw
+        return _asked(ctx, (None, None, None, None, dx, dscale, dtrans, dw))
 
 
 def wav_stage(wavelet: int, x: torch.Tensor, scale: torch.Tensor, trans: torch.Tensor, w: torch.Tensor, stride, padding, dilation) -> torch.Tensor:
@@ -1312,6 +1365,7 @@ class _CrossEntropy(torch.autograd.Function):
         return loss
 
     @staticmethod
+    @_once
     def backward(ctx, g):
         lib = L.load()
         logits, target, lse = ctx.saved_tensors
@@ -1319,7 +1373,7 @@ class _CrossEntropy(torch.autograd.Function):
         dlogits = torch.empty_like(logits)
         L.check(lib.kan_xent_bwd(_ptr(logits), _ptr(target), _ptr(lse), _ptr(g), _ptr(dlogits), logits.shape[0], logits.shape[1], _stream(logits)),
                 "kan_xent_bwd")
-        return dlogits, None, None
+        return _asked(ctx, (dlogits, None, None))
 
 
 def cross_entropy(logits: torch.Tensor, target: torch.Tensor, metrics=None) -> torch.Tensor:
