@@ -2969,6 +2969,73 @@ AdamArgs adam_args(double lr, double beta1, double beta2, double eps, double wei
     return a;
 }
 
+// ---- the capturable step: lr and the step counts live in DEVICE memory, so a recorded launch (HIP graph) computes step k at its k-th replay.
+// What does not change between steps -- betas, eps, weight decay, grad_scale -- stays a kernel argument (a change means re-recording).
+struct AdamHyper { double beta1, beta2, eps, weight_decay; float gscale; };
+
+// adam_args() on the device: the same expressions in double, pow(beta, (double)step), each result rounded to float once.  Device pow and
+// host pow may differ in the last bit of a double, so a float of the nine can be one ulp off the host's in rare cases, never more.
+__device__ __forceinline__ AdamArgs adam_args_dev(double lr, int step, const AdamHyper& h) {
+    const double bc1 = 1.0 - pow(h.beta1, (double)step), bc2 = 1.0 - pow(h.beta2, (double)step);
+    AdamArgs a;
+    a.decay = (float)(1.0 - lr * h.weight_decay);
+    a.w1 = (float)(1.0 - h.beta1); a.b1 = (float)h.beta1; a.b2 = (float)h.beta2; a.w2 = (float)(1.0 - h.beta2);
+    a.gscale = h.gscale; a.inv_bc2_sqrt = (float)(1.0 / sqrt(bc2)); a.eps = (float)h.eps; a.neg_step = (float)(-lr / bc1);
+    return a;
+}
+
+// seg_step[s] += (segment s has a gradient): a segment without one does not age (torch counts steps per parameter).  One thread per segment.
+__global__ __launch_bounds__(256) void k_adamw_advance(int* __restrict__ seg_step, const unsigned long long* __restrict__ seg_grad, int n_seg) {
+    const int s = blockIdx.x * 256 + threadIdx.x;
+    if (s < n_seg) seg_step[s] += seg_grad[s] != 0 ? 1 : 0;
+}
+
+// k_adamw_seg with the per-step scalars read from device memory: lr_dev[0] (double) and the segment's own step count seg_step[sg] (already
+// advanced, >= 1 for a segment with a gradient).  Thread 0 forms the nine floats once per workgroup; the element update is adam1, unchanged.
+__global__ __launch_bounds__(256) void k_adamw_seg_dev(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
+                                                       const unsigned long long* __restrict__ seg_grad, const long long* __restrict__ seg_off,
+                                                       const int* __restrict__ seg_n, const int* __restrict__ chunk_seg,
+                                                       const int* __restrict__ chunk_start, const double* __restrict__ lr_dev,
+                                                       const int* __restrict__ seg_step, int chunk, AdamHyper h) {
+    __shared__ AdamArgs sh_a;
+    const int sg = chunk_seg[blockIdx.x], start = chunk_start[blockIdx.x];
+    const float* g = (const float*)seg_grad[sg];
+    if (!g) return;                                             // uniform over the workgroup: nobody waits at the barrier below
+    if (threadIdx.x == 0) sh_a = adam_args_dev(lr_dev[0], seg_step[sg], h);
+    __syncthreads();
+    const AdamArgs a = sh_a;
+    const int n = min(chunk, seg_n[sg] - start);
+    const long long off = seg_off[sg] + start;
+    p += off; m += off; v += off; g += start;
+    if ((((uintptr_t)g) & 15u) == 0) {                          // p / m / v chunks are 16-byte aligned by construction
+        for (int i = threadIdx.x; i < (n >> 2); i += 256) {
+            float4 P = ((float4*)p)[i], G = ((const float4*)g)[i], M = ((float4*)m)[i], V = ((float4*)v)[i];
+            adam1(P.x, G.x, M.x, V.x, a); adam1(P.y, G.y, M.y, V.y, a); adam1(P.z, G.z, M.z, V.z, a); adam1(P.w, G.w, M.w, V.w, a);
+            ((float4*)p)[i] = P; ((float4*)m)[i] = M; ((float4*)v)[i] = V;
+        }
+        const int t = (n & ~3) + threadIdx.x;
+        if (t < n) adam1(p[t], g[t], m[t], v[t], a);
+    } else {
+        for (int i = threadIdx.x; i < n; i += 256) adam1(p[i], g[i], m[i], v[i], a);
+    }
+}
+
+// The nine floats adam_args_dev forms for one (lr, step) pair held in device memory, written out in AdamArgs order (test-facing).
+__global__ void k_adamw_dev_args(const double* __restrict__ lr_dev, const int* __restrict__ step_dev, AdamHyper h, float* __restrict__ out9) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    const AdamArgs a = adam_args_dev(lr_dev[0], step_dev[0], h);
+    out9[0] = a.decay; out9[1] = a.w1; out9[2] = a.b1; out9[3] = a.b2; out9[4] = a.w2; out9[5] = a.gscale; out9[6] = a.inv_bc2_sqrt; out9[7] = a.eps;
+    out9[8] = a.neg_step;
+}
+
+// Up to 64 addresses, passed BY VALUE, into table[first .. first + n): how the gradient-address table is filled while the stream is capturing
+// (the values become part of the graph node; no host memory has to outlive the capture).
+struct U64x64 { unsigned long long v[64]; };
+__global__ __launch_bounds__(64) void k_set_u64_table(unsigned long long* __restrict__ table, int first, int n, U64x64 vals) {
+    const int t = threadIdx.x;
+    if (t < n) table[first + t] = vals.v[t];
+}
+
 // ============================================================================ Wav-KAN wavelet stage (own C-ABI entry points inside)
 #include "wavkan.inc"
 
@@ -3628,6 +3695,56 @@ int kan_adamw_step_segments(float* p, float* m, float* v, const unsigned long lo
     hipLaunchKernelGGL(k_adamw_seg, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, p, m, v, seg_grad, seg_off, seg_n, chunk_seg,
                        chunk_start, seg_bias, chunk_elems, a);
     return launch_ok("adamw_seg");
+}
+
+static bool adam_hyper(double beta1, double beta2, double eps, double weight_decay, float grad_scale, AdamHyper* h) {
+    if (!(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(weight_decay >= 0.0)) return false;
+    h->beta1 = beta1; h->beta2 = beta2; h->eps = eps; h->weight_decay = weight_decay; h->gscale = grad_scale;
+    return true;
+}
+
+int kan_adamw_advance(int* seg_step, const unsigned long long* seg_grad, int n_seg, void* stream) {
+    if (!seg_step || !seg_grad) return fail("null tensor pointer");
+    if (n_seg < 0) return fail("adamw_advance: n_seg must be >= 0");
+    if (n_seg == 0) return 0;
+    hipLaunchKernelGGL(k_adamw_advance, dim3((unsigned)((n_seg + 255) / 256)), dim3(256), 0, (hipStream_t)stream, seg_step, seg_grad, n_seg);
+    return launch_ok("adamw_advance");
+}
+
+int kan_adamw_step_segments_dev(float* p, float* m, float* v, const unsigned long long* seg_grad, const long long* seg_off, const int* seg_n,
+                                const int* chunk_seg, const int* chunk_start, const double* lr_dev, const int* seg_step, int n_chunks,
+                                int chunk_elems, double beta1, double beta2, double eps, double weight_decay, float grad_scale, void* stream) {
+    if (!p || !m || !v || !seg_grad || !seg_off || !seg_n || !chunk_seg || !chunk_start || !lr_dev || !seg_step) return fail("null tensor pointer");
+    if (n_chunks < 0 || chunk_elems < 4 || (chunk_elems & 3)) return fail("adamw: bad chunk table");
+    if (((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15u) return fail("adamw: blocks must be 16-byte aligned");
+    if (((uintptr_t)lr_dev & 7u) || ((uintptr_t)seg_step & 3u)) return fail("adamw: lr_dev must be 8-byte and seg_step 4-byte aligned");
+    AdamHyper h;
+    if (!adam_hyper(beta1, beta2, eps, weight_decay, grad_scale, &h)) return fail("adamw: invalid hyper-parameters");
+    if (n_chunks == 0) return 0;
+    hipLaunchKernelGGL(k_adamw_seg_dev, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, p, m, v, seg_grad, seg_off, seg_n, chunk_seg,
+                       chunk_start, lr_dev, seg_step, chunk_elems, h);
+    return launch_ok("adamw_seg_dev");
+}
+
+int kan_adamw_dev_args(const double* lr_dev, const int* step_dev, double beta1, double beta2, double eps, double weight_decay, float grad_scale,
+                       float* out9, void* stream) {
+    if (!lr_dev || !step_dev || !out9) return fail("null tensor pointer");
+    if (((uintptr_t)lr_dev & 7u) || ((uintptr_t)step_dev & 3u) || ((uintptr_t)out9 & 3u)) return fail("adamw_dev_args: misaligned pointer");
+    AdamHyper h;
+    if (!adam_hyper(beta1, beta2, eps, weight_decay, grad_scale, &h)) return fail("adamw: invalid hyper-parameters");
+    hipLaunchKernelGGL(k_adamw_dev_args, dim3(1), dim3(64), 0, (hipStream_t)stream, lr_dev, step_dev, h, out9);
+    return launch_ok("adamw_dev_args");
+}
+
+int kan_set_u64_table(unsigned long long* table, int first, const unsigned long long* values, int n, void* stream) {
+    if (!table || !values) return fail("null pointer");
+    if (first < 0 || n < 0 || n > 64) return fail("set_u64_table: first must be >= 0 and n in 0..64");
+    if ((uintptr_t)table & 7u) return fail("set_u64_table: the table must be 8-byte aligned");
+    if (n == 0) return 0;
+    U64x64 vals;
+    for (int i = 0; i < 64; ++i) vals.v[i] = i < n ? values[i] : 0ull;           // read NOW, on the host: the node carries the values
+    hipLaunchKernelGGL(k_set_u64_table, dim3(1), dim3(64), 0, (hipStream_t)stream, table, first, n, vals);
+    return launch_ok("set_u64_table");
 }
 
 }  // extern "C"

@@ -42,49 +42,69 @@ def _split_context(on: bool):
 
 
 class GraphedStep:
-    """zero_grad / forward / loss / backward of ``model`` on fixed shapes, recorded ONCE into a HIP graph and replayed per batch.
+    """zero_grad / forward / loss / backward of ``model`` on fixed shapes -- and, with ``optimizer=``, the optimizer step -- recorded ONCE into a HIP
+    graph and replayed per batch.
 
     Every launch of the hot path goes through ctypes onto torch's current stream, so ``torch.cuda.graph`` captures the conv-KAN kernels next to
     torch's own; a replay costs one graph launch instead of the host's per-kernel work.  That pays where the step is launch-bound -- small models and
     single layers (BASELINE config 2: 0.23 ms replayed against 0.43-0.48 ms eager, bit-identical); KAN-VGG11 at bs 256 keeps the GPU busy either way.
     The weight packs are recorded unconditionally (``ops.always_pack``): the replay reads the weights as they are at replay time, so an optimizer may
-    update them in place between replays.  ``split_precision=True`` (OPT-IN) warms up and records inside ``ops.split_precision_training()``.  Keep the optimizer step OUTSIDE the graph (AdamW's bias correction takes the step count as a kernel
-    argument) and do not call ``zero_grad`` between replays: the recorded backward assigns ``p.grad`` (static tensors) rather than accumulating.
+    update them in place between replays.  ``split_precision=True`` (OPT-IN) warms up and records inside ``ops.split_precision_training()``.
+    Do not call ``zero_grad`` between replays: the recorded backward assigns ``p.grad`` (static tensors) rather than accumulating.
     The criterion inside a recorded step is torch's: ``convkan_amd.CrossEntropyLoss`` (the device-side counters of ``ClassMetrics``) is refused here --
     recording it is not supported yet; ``train_step`` takes it.
 
-        step = GraphedStep(model, example_data, example_target)
+    ``optimizer``: None, or a ``FusedAdamW(capturable=True)`` (anything else: ValueError).  Its ``step()`` is then the last thing of the recorded
+    region -- it reads lr and the step counts from device memory, so replay k computes step k.  The warm-up runs full steps, optimizer included, and
+    then the parameters, both moments and the step counts are put back to what they were: the first replay starts from the state the first eager
+    step would.  Each call brings lr up to date (``optimizer.sync_hyper()``: nothing unless a scheduler moved it), replays, and bumps the version
+    counter of every parameter the recorded step updates, so that a later eager forward (``evaluate``, a ragged last batch through ``train_step``)
+    sees the new weights through the packed-weight cache.  Which parameters have a gradient, betas, eps and weight_decay are frozen at recording
+    time.  Not built: gradient clipping, a recorded ``convkan_amd.CrossEntropyLoss``, and a DP reducer inside the graph.
+
+        step = GraphedStep(model, example_data, example_target, optimizer=opt)       # opt = FusedAdamW(..., capturable=True)
         for data, target in batches:
             loss = step(data, target)          # device-resident, overwritten by the next call
-            optimizer.step()
+
+    Without ``optimizer`` the caller steps after each call (any optimizer that updates the parameters in place).
     """
 
     def __init__(self, model: nn.Module, example_data: torch.Tensor, example_target: torch.Tensor, criterion: Optional[nn.Module] = None,
-                 warmup: int = 3, split_precision: bool = False):
+                 warmup: int = 3, split_precision: bool = False, optimizer=None):
         from . import ops
         from .loss import CrossEntropyLoss
         if isinstance(criterion, CrossEntropyLoss):
             raise NotImplementedError("GraphedStep does not record convkan_amd.CrossEntropyLoss yet: keep torch's criterion in a recorded step")
+        if optimizer is not None and not (isinstance(optimizer, FusedAdamW) and optimizer.capturable):
+            raise ValueError("GraphedStep(optimizer=...) records only a convkan_amd FusedAdamW(capturable=True); step any other optimizer after each call")
         if not example_data.is_cuda:
             raise ValueError("GraphedStep needs device tensors")
         self.model = model
+        self.optimizer = optimizer
         self.criterion = criterion if criterion is not None else nn.CrossEntropyLoss()
         self.data, self.target = example_data.clone(), example_target.clone()
+        saved = optimizer.snapshot() if optimizer is not None else None
         side = torch.cuda.Stream(device=example_data.device)
         side.wait_stream(torch.cuda.current_stream(example_data.device))
         with torch.cuda.stream(side), _split_context(split_precision):      # warm-up off the capture stream: plans, workspaces, torch's lazy initialisations
             for _ in range(max(1, warmup)):
                 self._eager()
+            if optimizer is not None:                      # (the warm-up uploaded lr; the recording below must find it on the device)
+                optimizer.restore(saved)
         torch.cuda.current_stream(example_data.device).wait_stream(side)
+        del saved
         self.graph = torch.cuda.CUDAGraph()
         self.model.zero_grad(set_to_none=True)             # recorded backward then ASSIGNS the gradients (tensors of the graph's pool)
         with _split_context(split_precision), ops.always_pack(), torch.cuda.graph(self.graph):
             self.loss = self._eager()
+        self._captured = optimizer.captured_addresses() if optimizer is not None else None
 
     def _eager(self) -> torch.Tensor:
         self.model.zero_grad(set_to_none=True)
         loss = self.criterion(self.model(self.data), self.target)
         loss.backward()
+        if self.optimizer is not None:
+            self.optimizer.step()
         return loss.detach()
 
     def __call__(self, data: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
@@ -92,24 +112,53 @@ class GraphedStep:
             raise ValueError(f"GraphedStep was recorded for {tuple(self.data.shape)} / {tuple(self.target.shape)}, got {tuple(data.shape)} / {tuple(target.shape)}")
         self.data.copy_(data, non_blocking=True)
         self.target.copy_(target, non_blocking=True)
+        if self.optimizer is not None:
+            self.optimizer.sync_hyper()
         self.graph.replay()
+        if self.optimizer is not None:
+            self.optimizer.after_replay(self._captured)
         return self.loss
+
+
+class _BatchRunner:
+    """One training batch for the drivers below: ``train_step``, or -- ``graphed`` -- ONE ``GraphedStep(optimizer=...)`` recorded on the first batch
+    (taken as the full-size one) and replayed for every batch of that shape; any other shape (the ragged last batch) goes through eager
+    ``train_step`` with the same optimizer."""
+
+    def __init__(self, model, optimizer, criterion, reducer, split_precision, graphed):
+        if graphed:
+            if not (isinstance(optimizer, FusedAdamW) and optimizer.capturable):
+                raise ValueError("graphed=True needs a convkan_amd FusedAdamW(capturable=True)")
+            if reducer is not None:
+                raise ValueError("graphed=True: a reducer inside a recorded step is not built")
+        self.model, self.optimizer, self.criterion, self.reducer, self.split, self.graphed = model, optimizer, criterion, reducer, split_precision, graphed
+        self.step = None
+
+    def __call__(self, data: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        if self.graphed:
+            if self.step is None:
+                self.step = GraphedStep(self.model, data, target, self.criterion, split_precision=self.split, optimizer=self.optimizer)
+            if data.shape == self.step.data.shape and target.shape == self.step.target.shape:
+                return self.step(data, target)
+        return train_step(self.model, data, target, self.optimizer, self.criterion, self.reducer, self.split)
 
 
 def train_model_generic(model: nn.Module, train_batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], device="cuda",
                         learning_rate: float = 1e-3, weight_decay: float = 1e-4, gamma: float = 0.8, epochs: int = 15,
-                        reducer=None, split_precision: bool = False) -> List[float]:
+                        reducer=None, split_precision: bool = False, graphed: bool = False) -> List[float]:
     """generic_train.py:19-30 without the dataset / metric / checkpoint plumbing; returns the average loss per epoch.
-    ``train_batches`` is re-iterated every epoch (a list of (data, target) pairs or a DataLoader).  ``split_precision``: handed to every ``train_step``."""
+    ``train_batches`` is re-iterated every epoch (a list of (data, target) pairs or a DataLoader).  ``split_precision``: handed to every ``train_step``.
+    ``graphed``: the optimizer is a capturable ``FusedAdamW`` and the whole step of every full-size batch is one graph replay (``_BatchRunner``)."""
     model.to(device).train()
-    optimizer = FusedAdamW(model.parameters(), lr=learning_rate, weight_decay=weight_decay)
+    optimizer = FusedAdamW(model.parameters(), lr=learning_rate, weight_decay=weight_decay, capturable=graphed)
     scheduler = torch.optim.lr_scheduler.ExponentialLR(optimizer, gamma=gamma)
     criterion = nn.CrossEntropyLoss()
+    run = _BatchRunner(model, optimizer, criterion, reducer, split_precision, graphed)
     history = []
     for _ in range(epochs):
         total, n = torch.zeros((), device=device), 0
         for data, target in train_batches:
-            total += train_step(model, data.to(device), target.to(device), optimizer, criterion, reducer, split_precision)
+            total += run(data.to(device), target.to(device))
             n += 1
         history.append(float(total) / max(n, 1))
         scheduler.step()
@@ -145,19 +194,22 @@ def evaluate(model: nn.Module, batches: Iterable[Tuple[torch.Tensor, torch.Tenso
 
 def train_and_test_models(model: nn.Module, train_batches: Iterable[Tuple[torch.Tensor, torch.Tensor]],
                           test_batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], optimizer: torch.optim.Optimizer, scheduler=None,
-                          epochs: int = 15, reducer=None, split_precision: bool = False, criterion: Optional[nn.Module] = None):
+                          epochs: int = 15, reducer=None, split_precision: bool = False, criterion: Optional[nn.Module] = None,
+                          graphed: bool = False):
     """evaluations.py:156-247: per epoch the ``train_step`` loop (one read of the accumulated loss), then ``evaluate`` (one read of the
     counters), then ``scheduler.step()``.  Runs on the device the model is on.  Returns the first seven lists of evaluations.py:247: train loss,
     test loss, accuracy, precision, recall, F1 and the learning rate each epoch started with.  Checkpoints (``torch.save``), early stopping
-    (``patience``), plots and timing are not carried over."""
+    (``patience``), plots and timing are not carried over.  ``graphed``: ``optimizer`` must be a ``FusedAdamW(capturable=True)``; every full-size
+    training batch is then one replay of a recorded step, optimizer included (``_BatchRunner``), the evaluation stays eager."""
     device = next(model.parameters()).device
+    run = _BatchRunner(model, optimizer, criterion, reducer, split_precision, graphed)
     train_loss, test_loss, accuracy, precision, recall, f1, rates = [], [], [], [], [], [], []
     for _ in range(epochs):
         rates.append(optimizer.param_groups[0]["lr"])
         model.train()
         total, n = torch.zeros((), device=device), 0
         for data, target in train_batches:
-            total += train_step(model, data.to(device), target.to(device), optimizer, criterion, reducer, split_precision)
+            total += run(data.to(device), target.to(device))
             n += 1
         train_loss.append(float(total) / max(n, 1))
         r = evaluate(model, test_batches, device)

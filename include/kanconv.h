@@ -437,6 +437,39 @@ int kan_adamw_step_segments(float* p, float* m, float* v, const unsigned long lo
                             const int* chunk_seg, const int* chunk_start, const float* seg_bias, int n_chunks, int chunk_elems, double lr,
                             double beta1, double beta2, double eps, double weight_decay, int step, float grad_scale, void* stream);
 
+/* ---- The capturable step: the same update with the scalars that change between steps held in DEVICE memory, so that a launch recorded into
+ * a HIP graph computes step k at its k-th replay.  Stands in, like the two entry points above, for generic_train.py:24-25 (`optim.AdamW` +
+ * `ExponentialLR`: the scheduler changes lr between epochs, the step count grows every batch) in torch's single-tensor AdamW order (above).
+ * The caller owns every buffer; everything runs on `stream`; nothing allocates, synchronises or copies; all of it may be stream-captured.
+ *
+ * Adds 1 to seg_step[s] (int32, DEVICE) for every segment s in [0, n_seg) whose seg_grad[s] is not 0: a segment without a gradient does not
+ * age, as torch's per-parameter `step` (the `state[p]["step"] += 1` of its single-tensor AdamW) does not.  Launch it in front of the dev step
+ * below, once per step. */
+int kan_adamw_advance(int* seg_step, const unsigned long long* seg_grad, int n_seg, void* stream);
+
+/* The segment step above with lr read from lr_dev[0] (a DEVICE double) and each segment's step count from seg_step[s] (DEVICE int32, already
+ * advanced: >= 1 wherever seg_grad[s] != 0).  decay = 1 - lr*weight_decay, -lr / (1 - beta1^step) and 1 / sqrt(1 - beta2^step) are formed on
+ * the device per segment, in double with pow(beta, (double)step), each rounded to float once -- the expressions of the host path, so where
+ * the floats agree bit for bit (device and host pow can differ in the last bit of a double: rarely one float ulp, never more) the results are
+ * those of the segment step above bit for bit.  There is no seg_bias: per-segment step counts are native.  betas, eps, weight_decay and
+ * grad_scale are kernel arguments: they are frozen into a recorded launch, and changing one means recording again. */
+int kan_adamw_step_segments_dev(float* p, float* m, float* v, const unsigned long long* seg_grad, const long long* seg_off, const int* seg_n,
+                                const int* chunk_seg, const int* chunk_start, const double* lr_dev, const int* seg_step, int n_chunks,
+                                int chunk_elems, double beta1, double beta2, double eps, double weight_decay, float grad_scale, void* stream);
+
+/* Test-facing: the nine floats the dev step forms for ONE (lr_dev[0], step_dev[0]) pair, by the same device function -- the scalars torch's
+ * single-tensor AdamW derives from `lr`, `weight_decay`, the betas and `step` (generic_train.py:24-25) --, written to the DEVICE
+ * array out9 in the order decay, 1 - beta1, beta1, beta2, 1 - beta2, grad_scale, 1 / sqrt(1 - beta2^step), eps, -lr / (1 - beta1^step). */
+int kan_adamw_dev_args(const double* lr_dev, const int* step_dev, double beta1, double beta2, double eps, double weight_decay, float grad_scale,
+                       float* out9, void* stream);
+
+/* Writes values[0 .. n) (HOST memory, read before the call returns; n <= 64) into the DEVICE array table[first .. first + n) with one small
+ * launch that carries the values as its argument: the way to fill seg_grad while `stream` is capturing, where a host-to-device copy is not
+ * allowed (outside capture the table is re-uploaded with a copy).  Stands in for nothing in the reference: torch's AdamW (generic_train.py:24-25) walks
+ * `p.grad` on the host every step; this is what replaces that walk inside a recorded step.  The values become part of the graph node; `values` need
+ * not outlive the call. */
+int kan_set_u64_table(unsigned long long* table, int first, const unsigned long long* values, int n, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- cross-entropy loss and test metrics
  * The criterion of the training script (generic_train.py:26 `nn.CrossEntropyLoss()`, called at evaluations.py:61 and :131: mean reduction, no
  * class weights, no ignore_index, no label smoothing) and what the evaluation loop collects per batch (evaluations.py:131-136: the batch loss,
