@@ -117,6 +117,10 @@ SIGNATURES = {
     "kan_adamw_advance": (_I, [_P, _P, _I, _P]),
     "kan_adamw_step_segments_dev": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _D, _D, _D, _D, _F, _P]),
     "kan_adamw_dev_args": (_I, [_P, _P, _D, _D, _D, _D, _F, _P, _P]),
+    "kan_grad_sqnorm_chunks": (_I, [_P, _P, _P, _P, _I, _I, _P, _P]),
+    "kan_grad_norm_finish": (_I, [_P, _P, _I, _P, _P, _P, _P]),
+    "kan_adamw_step_segments_clip": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _D, _D, _D, _D, _D, _I, _P, _P]),
+    "kan_adamw_step_segments_dev_clip": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _D, _D, _D, _D, _P, _P]),
     "kan_xent_workspace_bytes": (_LL, [_I]),
     "kan_xent_metrics_bytes": (_LL, [_I]),
     "kan_xent_fwd": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),

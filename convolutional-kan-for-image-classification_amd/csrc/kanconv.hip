@@ -2935,14 +2935,18 @@ __global__ __launch_bounds__(256) void k_adamw(float* __restrict__ p, const floa
 // The same update over SEGMENTS of the flat block whose gradients live wherever autograd (or the all-reduce bucket) left
 // them: workgroup b owns chunk b = elements [start, start + chunk) of segment chunk_seg[b]; a segment whose gradient
 // pointer is null is skipped, as torch skips parameters without .grad.  Nothing is copied or zeroed per step.
+// DEV_SCALE (the _clip entry points): grad_scale is read from scale_dev[0], the clip coefficient k_grad_norm_finish (kan_clip.hip) left in device
+// memory; without it the pointer is not touched and the kernel is the one it was.
+template <bool DEV_SCALE>
 __global__ __launch_bounds__(256) void k_adamw_seg(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
                                                    const unsigned long long* __restrict__ seg_grad, const long long* __restrict__ seg_off,
                                                    const int* __restrict__ seg_n, const int* __restrict__ chunk_seg,
                                                    const int* __restrict__ chunk_start, const float* __restrict__ seg_bias, int chunk,
-                                                   AdamArgs a) {
+                                                   AdamArgs a, const float* __restrict__ scale_dev) {
     const int sg = chunk_seg[blockIdx.x], start = chunk_start[blockIdx.x];
     const float* g = (const float*)seg_grad[sg];
     if (!g) return;
+    if (DEV_SCALE) a.gscale = scale_dev[0];
     if (seg_bias) { a.neg_step = seg_bias[2 * sg]; a.inv_bc2_sqrt = seg_bias[2 * sg + 1]; }     // per-parameter step counts
     const int n = min(chunk, seg_n[sg] - start);
     const long long off = seg_off[sg] + start;
@@ -2992,16 +2996,21 @@ __global__ __launch_bounds__(256) void k_adamw_advance(int* __restrict__ seg_ste
 
 // k_adamw_seg with the per-step scalars read from device memory: lr_dev[0] (double) and the segment's own step count seg_step[sg] (already
 // advanced, >= 1 for a segment with a gradient).  Thread 0 forms the nine floats once per workgroup; the element update is adam1, unchanged.
+// DEV_SCALE: as in k_adamw_seg.
+template <bool DEV_SCALE>
 __global__ __launch_bounds__(256) void k_adamw_seg_dev(float* __restrict__ p, float* __restrict__ m, float* __restrict__ v,
                                                        const unsigned long long* __restrict__ seg_grad, const long long* __restrict__ seg_off,
                                                        const int* __restrict__ seg_n, const int* __restrict__ chunk_seg,
                                                        const int* __restrict__ chunk_start, const double* __restrict__ lr_dev,
-                                                       const int* __restrict__ seg_step, int chunk, AdamHyper h) {
+                                                       const int* __restrict__ seg_step, int chunk, AdamHyper h, const float* __restrict__ scale_dev) {
     __shared__ AdamArgs sh_a;
     const int sg = chunk_seg[blockIdx.x], start = chunk_start[blockIdx.x];
     const float* g = (const float*)seg_grad[sg];
     if (!g) return;                                             // uniform over the workgroup: nobody waits at the barrier below
-    if (threadIdx.x == 0) sh_a = adam_args_dev(lr_dev[0], seg_step[sg], h);
+    if (threadIdx.x == 0) {
+        if (DEV_SCALE) h.gscale = scale_dev[0];
+        sh_a = adam_args_dev(lr_dev[0], seg_step[sg], h);
+    }
     __syncthreads();
     const AdamArgs a = sh_a;
     const int n = min(chunk, seg_n[sg] - start);
@@ -3692,9 +3701,22 @@ int kan_adamw_step_segments(float* p, float* m, float* v, const unsigned long lo
     if (((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15u) return fail("adamw: blocks must be 16-byte aligned");
     if (n_chunks == 0) return 0;
     const AdamArgs a = adam_args(lr, beta1, beta2, eps, weight_decay, step, grad_scale);
-    hipLaunchKernelGGL(k_adamw_seg, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, p, m, v, seg_grad, seg_off, seg_n, chunk_seg,
-                       chunk_start, seg_bias, chunk_elems, a);
+    hipLaunchKernelGGL(k_adamw_seg<false>, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, p, m, v, seg_grad, seg_off, seg_n, chunk_seg,
+                       chunk_start, seg_bias, chunk_elems, a, (const float*)nullptr);
     return launch_ok("adamw_seg");
+}
+
+int kan_adamw_step_segments_clip(float* p, float* m, float* v, const unsigned long long* seg_grad, const long long* seg_off, const int* seg_n,
+                                 const int* chunk_seg, const int* chunk_start, const float* seg_bias, int n_chunks, int chunk_elems, double lr,
+                                 double beta1, double beta2, double eps, double weight_decay, int step, const float* scale_dev, void* stream) {
+    if (!p || !m || !v || !seg_grad || !seg_off || !seg_n || !chunk_seg || !chunk_start || !scale_dev) return fail("null tensor pointer");
+    if (n_chunks <= 0 || step < 1 || chunk_elems < 4 || (chunk_elems & 3)) return fail("adamw_clip: bad chunk table or step");
+    if (((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15u) return fail("adamw: blocks must be 16-byte aligned");
+    if ((uintptr_t)scale_dev & 3u) return fail("adamw_clip: scale_dev must be 4-byte aligned");
+    const AdamArgs a = adam_args(lr, beta1, beta2, eps, weight_decay, step, 1.0f);
+    hipLaunchKernelGGL(k_adamw_seg<true>, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, p, m, v, seg_grad, seg_off, seg_n, chunk_seg,
+                       chunk_start, seg_bias, chunk_elems, a, scale_dev);
+    return launch_ok("adamw_seg_clip");
 }
 
 static bool adam_hyper(double beta1, double beta2, double eps, double weight_decay, float grad_scale, AdamHyper* h) {
@@ -3721,9 +3743,26 @@ int kan_adamw_step_segments_dev(float* p, float* m, float* v, const unsigned lon
     AdamHyper h;
     if (!adam_hyper(beta1, beta2, eps, weight_decay, grad_scale, &h)) return fail("adamw: invalid hyper-parameters");
     if (n_chunks == 0) return 0;
-    hipLaunchKernelGGL(k_adamw_seg_dev, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, p, m, v, seg_grad, seg_off, seg_n, chunk_seg,
-                       chunk_start, lr_dev, seg_step, chunk_elems, h);
+    hipLaunchKernelGGL(k_adamw_seg_dev<false>, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, p, m, v, seg_grad, seg_off, seg_n,
+                       chunk_seg, chunk_start, lr_dev, seg_step, chunk_elems, h, (const float*)nullptr);
     return launch_ok("adamw_seg_dev");
+}
+
+int kan_adamw_step_segments_dev_clip(float* p, float* m, float* v, const unsigned long long* seg_grad, const long long* seg_off, const int* seg_n,
+                                     const int* chunk_seg, const int* chunk_start, const double* lr_dev, const int* seg_step, int n_chunks,
+                                     int chunk_elems, double beta1, double beta2, double eps, double weight_decay, const float* scale_dev,
+                                     void* stream) {
+    if (!p || !m || !v || !seg_grad || !seg_off || !seg_n || !chunk_seg || !chunk_start || !lr_dev || !seg_step || !scale_dev)
+        return fail("null tensor pointer");
+    if (n_chunks <= 0 || chunk_elems < 4 || (chunk_elems & 3)) return fail("adamw_clip: bad chunk table");
+    if (((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15u) return fail("adamw: blocks must be 16-byte aligned");
+    if (((uintptr_t)lr_dev & 7u) || (((uintptr_t)seg_step | (uintptr_t)scale_dev) & 3u))
+        return fail("adamw_clip: lr_dev must be 8-byte, seg_step and scale_dev 4-byte aligned");
+    AdamHyper h;
+    if (!adam_hyper(beta1, beta2, eps, weight_decay, 1.0f, &h)) return fail("adamw: invalid hyper-parameters");
+    hipLaunchKernelGGL(k_adamw_seg_dev<true>, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, p, m, v, seg_grad, seg_off, seg_n,
+                       chunk_seg, chunk_start, lr_dev, seg_step, chunk_elems, h, scale_dev);
+    return launch_ok("adamw_seg_dev_clip");
 }
 
 int kan_adamw_dev_args(const double* lr_dev, const int* step_dev, double beta1, double beta2, double eps, double weight_decay, float grad_scale,

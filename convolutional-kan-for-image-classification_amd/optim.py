@@ -17,6 +17,13 @@ parameter -- so that ``step()`` may be recorded into a HIP graph (``train.Graphe
 step, as ``torch.optim.AdamW(capturable=True)`` does.  A step is then two launches per group, ``kan_adamw_advance`` (the counts of the
 parameters that have a gradient) and ``kan_adamw_step_segments_dev``; the host keeps no count and reads the device ones only for
 ``state_dict()`` / ``sync_steps()``.  See ``FusedAdamW.step`` for what a recording freezes.
+
+``max_grad_norm=c`` (default None: off) clips by the global gradient norm inside the step -- what the reference asks for at evaluations.py:33
+(``clip_grad_norm_(model.parameters(), max_norm=1.0)``) -- without a host walk or an in-place rescaling pass: ``kan_grad_sqnorm_chunks`` per group
+and one ``kan_grad_norm_finish`` leave the norm and ``min(1, c / (norm + 1e-6))`` in device memory, and the ``_clip`` step kernels multiply by that
+coefficient as they read each gradient (32 bytes per element instead of 28; ``p.grad`` itself is not modified).  ``opt.grad_norm``,
+``opt.clip_scale`` and ``opt.grad_norms()`` (the per-parameter norms of evaluations.py:66-71) are device reads.  It works in both modes and inside
+a recorded step.
 """
 from __future__ import annotations
 
@@ -32,20 +39,27 @@ _CHUNK = 8192        # elements per workgroup of the segment kernel (256 threads
 
 
 class FusedAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, capturable: bool = False):
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, capturable: bool = False,
+                 max_grad_norm=None):
         if lr < 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
             raise ValueError("invalid AdamW hyper-parameters")
         self.capturable = bool(capturable)           # not a param_groups entry: a state_dict must load into torch.optim.AdamW on any device
         self._captured = None
+        self._max_grad_norm = self._check_max_norm(max_grad_norm)     # like capturable, not a param_groups entry
+        self._clip = None
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._flat = []
         for group in self.param_groups:
             self._flat.append(self._flatten(group))
+        if self._max_grad_norm is not None:
+            self._clip = self._build_clip()
 
     def add_param_group(self, param_group):
         super().add_param_group(param_group)
         if hasattr(self, "_flat"):                   # groups added after construction get their own flat block
             self._flat.append(self._flatten(self.param_groups[-1]))
+            if self._clip is not None:               # a new layout: the statistics buffer is rebuilt with it
+                self._clip = self._build_clip()
 
     # ------------------------------------------------------------------ layout
     @staticmethod
@@ -89,6 +103,100 @@ class FusedAdamW(torch.optim.Optimizer):
             st["step"] = torch.tensor(float(flat["steps"][flat["index"][id(p)]]))
             st["exp_avg"], st["exp_avg_sq"] = mv, vv
 
+    # ------------------------------------------------------------------ clipping: the statistics buffer
+    @staticmethod
+    def _check_max_norm(value):
+        if value is None:
+            return None
+        value = float(value)
+        if not value >= 0.0:                                              # negative or NaN
+            raise ValueError(f"max_grad_norm must be None or a float >= 0 (inf allowed), got {value}")
+        return value
+
+    @property
+    def max_grad_norm(self):
+        """None (no clipping: the step is the plain one) or the ``max_norm`` of ``clip_grad_norm_``.  Settable; the device copy follows like lr."""
+        return self._max_grad_norm
+
+    @max_grad_norm.setter
+    def max_grad_norm(self, value):
+        self._max_grad_norm = self._check_max_norm(value)
+        if self._max_grad_norm is not None and self._clip is None and hasattr(self, "_flat"):
+            self._clip = self._build_clip()
+
+    def _build_clip(self):
+        """ONE buffer for everything the norm kernels write, built with the layout tables: partial (double, one per chunk over all groups), seg_sq
+        (double, one per parameter), seg_first_chunk (int32, one per parameter + 1) and three floats (norm, scale, max_norm)."""
+        flats = [f for f in self._flat if f is not None]
+        dev = flats[0]["block"].device if flats else torch.device("cpu")
+        if any(f["block"].device != dev for f in flats):
+            raise L.KanConvError("FusedAdamW(max_grad_norm=...): one global norm needs every parameter group on one device")
+        first, chunk0 = [0], []
+        for f in self._flat:
+            chunk0.append(first[-1])
+            for p in (f["params"] if f is not None else ()):
+                first.append(first[-1] + (p.numel() + _CHUNK - 1) // _CHUNK)
+        nc, ns = first[-1], len(first) - 1
+        words = (ns + 2) // 2                                              # 8-byte words holding the ns + 1 int32
+        buf = torch.zeros(nc + ns + words + 2, dtype=torch.float64, device=dev)
+        ints = buf[nc + ns:nc + ns + words].view(torch.int32)[:ns + 1]
+        ints.copy_(torch.tensor(first, dtype=torch.int32))
+        return dict(buf=buf, partial=buf[:nc], seg_sq=buf[nc:nc + ns], seg_first_chunk=ints, out=buf[nc + ns + words:].view(torch.float32)[:3],
+                    chunk0=chunk0, host=None)                              # host: what out[2], the device copy of max_grad_norm, holds
+
+    def _need_clip(self, what):
+        if self._max_grad_norm is None or self._clip is None:
+            raise L.KanConvError(f"FusedAdamW.{what} belongs to max_grad_norm=...: this optimizer does not clip (max_grad_norm=None)")
+        return self._clip
+
+    @property
+    def grad_norm(self):
+        """0-dim float32 DEVICE tensor: the global norm, before clipping, of the gradients the last step (or replay) consumed.  A view of the
+        statistics buffer: no host read, and the next step overwrites it (like ``GraphedStep.loss``)."""
+        return self._need_clip("grad_norm")["out"][0]
+
+    @property
+    def clip_scale(self):
+        """0-dim float32 DEVICE tensor: min(1, max_grad_norm / (grad_norm + 1e-6)), what the last step multiplied every gradient by."""
+        return self._need_clip("clip_scale")["out"][1]
+
+    def grad_norms(self):
+        """float32 DEVICE vector: the gradient norm of every parameter that has ``requires_grad``, in ``param_groups`` order, as of the last step;
+        0 where there was no gradient.  No host read."""
+        return self._need_clip("grad_norms()")["seg_sq"].sqrt().float()
+
+    def _sync_max_norm(self, clip):
+        if clip["host"] != self._max_grad_norm:
+            if torch.cuda.is_current_stream_capturing():
+                raise L.KanConvError(f"FusedAdamW(max_grad_norm=...): the device copy of max_grad_norm holds {clip['host']}, the attribute is "
+                                     f"{self._max_grad_norm}; nothing may be uploaded while the stream is capturing -- run one eager step, or call "
+                                     "sync_hyper(), before recording")
+            clip["out"][2:3].fill_(self._max_grad_norm)                    # a fill launch carrying the value: no host memory is read later
+            clip["host"] = self._max_grad_norm
+
+    def _launch_norm(self, lib, clip, work):
+        """The first pass of a clipping step: every group's address table, one chunk launch per group, one finish."""
+        if self.capturable:
+            for _, group, flat, _, _ in work:                              # refuse a stale lr before anything is launched
+                self._sync_lr(group, flat)
+        self._sync_max_norm(clip)
+        dev = clip["buf"].device
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        with torch.cuda.device(dev):
+            for _, _, flat, ptrs, _ in work:
+                self._fill_table(lib, flat, ptrs)
+            if len(work) != sum(f is not None for f in self._flat):        # a group without any gradient launches nothing: its partials are 0
+                clip["partial"].zero_()
+            for gi, _, flat, _, _ in work:
+                tab, c0 = flat["tab"], clip["chunk0"][gi]
+                L.check(lib.kan_grad_sqnorm_chunks(C.c_void_p(tab["seg_grad"].data_ptr()), C.c_void_p(tab["seg_n"].data_ptr()),
+                                                   C.c_void_p(tab["chunk_seg"].data_ptr()), C.c_void_p(tab["chunk_start"].data_ptr()),
+                                                   tab["chunk_seg"].numel(), _CHUNK, C.c_void_p(clip["partial"].data_ptr() + 8 * c0), stream),
+                        "kan_grad_sqnorm_chunks")
+            L.check(lib.kan_grad_norm_finish(C.c_void_p(clip["partial"].data_ptr()), C.c_void_p(clip["seg_first_chunk"].data_ptr()),
+                                             clip["seg_sq"].numel(), C.c_void_p(clip["out"].data_ptr() + 8), C.c_void_p(clip["seg_sq"].data_ptr()),
+                                             C.c_void_p(clip["out"].data_ptr()), stream), "kan_grad_norm_finish")
+
     # ------------------------------------------------------------------ torch.optim surface
     @torch.no_grad()
     def step(self, closure=None):
@@ -99,16 +207,26 @@ class FusedAdamW(torch.optim.Optimizer):
         go into the graph through ``kan_set_u64_table`` nodes -- and (b) betas, eps and weight_decay, which are kernel arguments: changing one of
         them, or the set of parameters with a gradient, means recording again.  ``lr`` and the step counts are NOT frozen: they are read from
         device memory at replay time.  ``lr`` must already be on the device when recording starts (one eager step, or ``sync_hyper()``,
-        after the last change of ``group["lr"]``); between replays call ``sync_hyper()`` -- ``GraphedStep`` does."""
+        after the last change of ``group["lr"]``); between replays call ``sync_hyper()`` -- ``GraphedStep`` does.
+
+        ``max_grad_norm=c`` (default None: off, and the launches are the ones above): global-norm clipping as
+        ``torch.nn.utils.clip_grad_norm_(params, c)`` in front of the step computes it, in two passes over the groups -- one
+        ``kan_grad_sqnorm_chunks`` per group and ONE ``kan_grad_norm_finish`` (the norm is global, over all groups), then per group the ``_clip``
+        variant of the step, which multiplies every gradient by the coefficient as it reads it.  Unlike ``clip_grad_norm_``, ``p.grad`` is NOT
+        modified: the scale exists only inside the step.  ``opt.grad_norm``, ``opt.clip_scale`` and ``opt.grad_norms()`` are device reads of what
+        the step computed.  Under DP the step runs after ``reducer.finish()``, so the norm is that of the REDUCED gradients (every rank computes
+        the same one).  A recorded step freezes that clipping is on; the VALUE of ``max_grad_norm`` is NOT frozen -- it is read from device memory
+        at replay time and brought up to date like ``lr``, by the eager step or by ``sync_hyper()``.  If no parameter has a gradient, nothing launches."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         lib = L.load()
-        for group, flat in zip(self.param_groups, self._flat):
+        work = []
+        for gi, (group, flat) in enumerate(zip(self.param_groups, self._flat)):
             if flat is None:
                 continue
-            blk, tab = flat["block"], flat["tab"]
+            blk = flat["block"]
             if not blk.is_cuda:
                 raise L.KanConvError(f"FusedAdamW.step: parameters are on {blk.device}; the fused step runs only on a ROCm device "
                                      "(there is no CPU fallback)")
@@ -125,73 +243,88 @@ class FusedAdamW(torch.optim.Optimizer):
                     g = g.to(device=blk.device, dtype=torch.float32).contiguous()
                     keep.append(g)
                 ptrs.append(g.data_ptr())
-            if not any(ptrs):
-                continue
-            if self.capturable:
-                self._step_capturable(lib, group, flat, ptrs, keep)
-                continue
-            if ptrs != tab["grad_ptrs"]:                                 # the caching allocator hands back the same blocks step
-                tab["seg_grad"].copy_(torch.tensor(ptrs, dtype=torch.int64), non_blocking=False)      # after step: usually a no-op
-                tab["grad_ptrs"] = ptrs
-            b1, b2 = group["betas"]
-            steps = flat["steps"]                                          # torch counts steps per parameter
-            for i, a in enumerate(ptrs):
-                steps[i] += 1 if a else 0
-            group["step"] = max(steps)
-            bias = None
-            if any(a and st != group["step"] for a, st in zip(ptrs, steps)):      # rare: some parameter skipped earlier steps
-                bias = tab["seg_bias"]
-                bias.copy_(torch.tensor([[-group["lr"] / (1.0 - b1 ** max(st, 1)), 1.0 / (1.0 - b2 ** max(st, 1)) ** 0.5] for st in steps],
-                                        dtype=torch.float32))
-            row = lambda r: C.c_void_p(blk.data_ptr() + 4 * r * flat["n"])
-            with torch.cuda.device(blk.device):
-                L.check(lib.kan_adamw_step_segments(row(0), row(1), row(2), C.c_void_p(tab["seg_grad"].data_ptr()),
-                                                    C.c_void_p(tab["seg_off"].data_ptr()), C.c_void_p(tab["seg_n"].data_ptr()),
-                                                    C.c_void_p(tab["chunk_seg"].data_ptr()), C.c_void_p(tab["chunk_start"].data_ptr()),
-                                                    C.c_void_p(bias.data_ptr() if bias is not None else 0), tab["chunk_seg"].numel(), _CHUNK, group["lr"], b1, b2, group["eps"],
-                                                    group["weight_decay"], group["step"], 1.0,
-                                                    C.c_void_p(torch.cuda.current_stream(blk.device).cuda_stream)), "kan_adamw_step_segments")
-            del keep
-            for p, a in zip(flat["params"], ptrs):                         # the kernel wrote through raw pointers: tell autograd (and
-                if a:                                                      # the packed-weight cache of ops.py) that the values changed
-                    torch.autograd.graph.increment_version(p)
+            if any(ptrs):
+                work.append((gi, group, flat, ptrs, keep))
+        clip = self._clip if self._max_grad_norm is not None else None
+        if clip is not None and work:
+            self._launch_norm(lib, clip, work)
+        scale = C.c_void_p(clip["out"].data_ptr() + 4) if clip is not None else None
+        for _, group, flat, ptrs, _ in work:
+            with torch.cuda.device(flat["block"].device):
+                if self.capturable:
+                    self._step_capturable(lib, group, flat, ptrs, scale)
+                else:
+                    self._step_classic(lib, group, flat, ptrs, scale)
+            for p, a in zip(flat["params"], ptrs):                         # the kernel wrote through raw pointers: tell autograd (and the packed-
+                if a:                                                      # weight cache of ops.py) that the values changed.  Host-only, legal
+                    torch.autograd.graph.increment_version(p)              # under capture; a replay bumps them in after_replay()
+        del work
         return loss
 
-    # ------------------------------------------------------------------ the capturable step
-    def _step_capturable(self, lib, group, flat, ptrs, keep):
+    def _fill_table(self, lib, flat, ptrs):
+        """The group's device table of gradient addresses: a copy when an address changed (the caching allocator hands back the same blocks step
+        after step: usually nothing), or -- capturing, where no host-to-device copy is allowed -- by value, 64 per launch, as part of the graph."""
+        tab = flat["tab"]
+        if self.capturable and torch.cuda.is_current_stream_capturing():
+            seg_grad, stream = C.c_void_p(tab["seg_grad"].data_ptr()), C.c_void_p(torch.cuda.current_stream(flat["block"].device).cuda_stream)
+            vals = (C.c_ulonglong * 64)()
+            for first in range(0, len(ptrs), 64):
+                part = ptrs[first:first + 64]
+                vals[:len(part)] = part
+                L.check(lib.kan_set_u64_table(seg_grad, first, vals, len(part), stream), "kan_set_u64_table")
+            tab["grad_ptrs"] = None                                        # the table holds these addresses only after a replay: after_replay()
+            flat["captured_ptrs"] = list(ptrs)
+        elif ptrs != tab["grad_ptrs"]:
+            tab["seg_grad"].copy_(torch.tensor(ptrs, dtype=torch.int64), non_blocking=False)
+            tab["grad_ptrs"] = ptrs
+
+    def _step_classic(self, lib, group, flat, ptrs, scale):
         blk, tab = flat["block"], flat["tab"]
-        capturing = torch.cuda.is_current_stream_capturing()
+        if scale is None:
+            self._fill_table(lib, flat, ptrs)                              # (a clipping step filled every table in its first pass)
+        b1, b2 = group["betas"]
+        steps = flat["steps"]                                              # torch counts steps per parameter
+        for i, a in enumerate(ptrs):
+            steps[i] += 1 if a else 0
+        group["step"] = max(steps)
+        bias = None
+        if any(a and st != group["step"] for a, st in zip(ptrs, steps)):   # rare: some parameter skipped earlier steps
+            bias = tab["seg_bias"]
+            bias.copy_(torch.tensor([[-group["lr"] / (1.0 - b1 ** max(st, 1)), 1.0 / (1.0 - b2 ** max(st, 1)) ** 0.5] for st in steps],
+                                    dtype=torch.float32))
+        row = lambda r: C.c_void_p(blk.data_ptr() + 4 * r * flat["n"])
+        fn, name = (lib.kan_adamw_step_segments, "kan_adamw_step_segments") if scale is None else \
+                   (lib.kan_adamw_step_segments_clip, "kan_adamw_step_segments_clip")
+        L.check(fn(row(0), row(1), row(2), C.c_void_p(tab["seg_grad"].data_ptr()), C.c_void_p(tab["seg_off"].data_ptr()),
+                   C.c_void_p(tab["seg_n"].data_ptr()), C.c_void_p(tab["chunk_seg"].data_ptr()), C.c_void_p(tab["chunk_start"].data_ptr()),
+                   C.c_void_p(bias.data_ptr() if bias is not None else 0), tab["chunk_seg"].numel(), _CHUNK, group["lr"], b1, b2, group["eps"],
+                   group["weight_decay"], group["step"], 1.0 if scale is None else scale,
+                   C.c_void_p(torch.cuda.current_stream(blk.device).cuda_stream)), name)
+
+    # ------------------------------------------------------------------ the capturable step
+    def _sync_lr(self, group, flat):
         if flat["lr_host"] != group["lr"]:
-            if capturing:
+            if torch.cuda.is_current_stream_capturing():
                 raise L.KanConvError(f"FusedAdamW(capturable=True): the device copy of lr holds {flat['lr_host']}, group['lr'] is {group['lr']}; nothing "
                                      "may be uploaded while the stream is capturing -- run one eager step, or call sync_hyper(), before recording")
             self._upload_lr(group, flat)
+
+    def _step_capturable(self, lib, group, flat, ptrs, scale):
+        blk, tab = flat["block"], flat["tab"]
+        self._sync_lr(group, flat)
+        if scale is None:
+            self._fill_table(lib, flat, ptrs)
         b1, b2 = group["betas"]
         stream = C.c_void_p(torch.cuda.current_stream(blk.device).cuda_stream)
         seg_grad = C.c_void_p(tab["seg_grad"].data_ptr())
         row = lambda r: C.c_void_p(blk.data_ptr() + 4 * r * flat["n"])
-        with torch.cuda.device(blk.device):
-            if capturing:                                                  # no host-to-device copy under capture: the addresses travel by value,
-                vals = (C.c_ulonglong * 64)()                              # 64 per launch, and become part of the graph
-                for first in range(0, len(ptrs), 64):
-                    part = ptrs[first:first + 64]
-                    vals[:len(part)] = part
-                    L.check(lib.kan_set_u64_table(seg_grad, first, vals, len(part), stream), "kan_set_u64_table")
-                tab["grad_ptrs"] = None                                    # the table holds these addresses only after a replay: after_replay()
-                flat["captured_ptrs"] = list(ptrs)
-            elif ptrs != tab["grad_ptrs"]:
-                tab["seg_grad"].copy_(torch.tensor(ptrs, dtype=torch.int64), non_blocking=False)
-                tab["grad_ptrs"] = ptrs
-            L.check(lib.kan_adamw_advance(C.c_void_p(tab["seg_step"].data_ptr()), seg_grad, len(ptrs), stream), "kan_adamw_advance")
-            L.check(lib.kan_adamw_step_segments_dev(row(0), row(1), row(2), seg_grad, C.c_void_p(tab["seg_off"].data_ptr()),
-                                                    C.c_void_p(tab["seg_n"].data_ptr()), C.c_void_p(tab["chunk_seg"].data_ptr()),
-                                                    C.c_void_p(tab["chunk_start"].data_ptr()), C.c_void_p(flat["lr_dev"].data_ptr()),
-                                                    C.c_void_p(tab["seg_step"].data_ptr()), tab["chunk_seg"].numel(), _CHUNK, b1, b2, group["eps"],
-                                                    group["weight_decay"], 1.0, stream), "kan_adamw_step_segments_dev")
-        del keep
-        for p, a in zip(flat["params"], ptrs):                             # host-only, legal under capture; a replay bumps them in after_replay()
-            if a:
-                torch.autograd.graph.increment_version(p)
+        fn, name = (lib.kan_adamw_step_segments_dev, "kan_adamw_step_segments_dev") if scale is None else \
+                   (lib.kan_adamw_step_segments_dev_clip, "kan_adamw_step_segments_dev_clip")
+        L.check(lib.kan_adamw_advance(C.c_void_p(tab["seg_step"].data_ptr()), seg_grad, len(ptrs), stream), "kan_adamw_advance")
+        L.check(fn(row(0), row(1), row(2), seg_grad, C.c_void_p(tab["seg_off"].data_ptr()), C.c_void_p(tab["seg_n"].data_ptr()),
+                   C.c_void_p(tab["chunk_seg"].data_ptr()), C.c_void_p(tab["chunk_start"].data_ptr()), C.c_void_p(flat["lr_dev"].data_ptr()),
+                   C.c_void_p(tab["seg_step"].data_ptr()), tab["chunk_seg"].numel(), _CHUNK, b1, b2, group["eps"], group["weight_decay"],
+                   1.0 if scale is None else scale, stream), name)
 
     @staticmethod
     def _upload_lr(group, flat):
@@ -204,8 +337,11 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def sync_hyper(self):
         """Bring the device copy of every group's ``lr`` up to date with ``group["lr"]`` (one small launch per group whose lr a scheduler moved;
-        nothing otherwise).  Call it before recording and between replays -- never while the stream is capturing."""
+        nothing otherwise), and that of ``max_grad_norm`` likewise.  Call it before recording and between replays -- never while the stream is
+        capturing."""
         self._need_capturable("sync_hyper()")
+        if self._max_grad_norm is not None and self._clip["buf"].is_cuda:
+            self._sync_max_norm(self._clip)
         for group, flat in zip(self.param_groups, self._flat):
             if flat is not None and flat["block"].is_cuda and flat["lr_host"] != group["lr"]:
                 if torch.cuda.is_current_stream_capturing():

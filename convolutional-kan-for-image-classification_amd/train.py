@@ -60,7 +60,9 @@ class GraphedStep:
     step would.  Each call brings lr up to date (``optimizer.sync_hyper()``: nothing unless a scheduler moved it), replays, and bumps the version
     counter of every parameter the recorded step updates, so that a later eager forward (``evaluate``, a ragged last batch through ``train_step``)
     sees the new weights through the packed-weight cache.  Which parameters have a gradient, betas, eps and weight_decay are frozen at recording
-    time.  Not built: gradient clipping, a recorded ``convkan_amd.CrossEntropyLoss``, and a DP reducer inside the graph.
+    time.  Gradient clipping travels with the optimizer (``FusedAdamW(..., max_grad_norm=c)``): its norm kernels are part of the recorded step, and
+    ``max_grad_norm`` itself is read from device memory at replay time, like lr.  Not built: a recorded ``convkan_amd.CrossEntropyLoss``, and a DP
+    reducer inside the graph.
 
         step = GraphedStep(model, example_data, example_target, optimizer=opt)       # opt = FusedAdamW(..., capturable=True)
         for data, target in batches:
@@ -145,12 +147,13 @@ class _BatchRunner:
 
 def train_model_generic(model: nn.Module, train_batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], device="cuda",
                         learning_rate: float = 1e-3, weight_decay: float = 1e-4, gamma: float = 0.8, epochs: int = 15,
-                        reducer=None, split_precision: bool = False, graphed: bool = False) -> List[float]:
+                        reducer=None, split_precision: bool = False, graphed: bool = False, max_grad_norm=None) -> List[float]:
     """generic_train.py:19-30 without the dataset / metric / checkpoint plumbing; returns the average loss per epoch.
     ``train_batches`` is re-iterated every epoch (a list of (data, target) pairs or a DataLoader).  ``split_precision``: handed to every ``train_step``.
-    ``graphed``: the optimizer is a capturable ``FusedAdamW`` and the whole step of every full-size batch is one graph replay (``_BatchRunner``)."""
+    ``graphed``: the optimizer is a capturable ``FusedAdamW`` and the whole step of every full-size batch is one graph replay (``_BatchRunner``).
+    ``max_grad_norm``: None (off), or the global-norm clip the reference asks for at evaluations.py:33, done inside the optimizer step."""
     model.to(device).train()
-    optimizer = FusedAdamW(model.parameters(), lr=learning_rate, weight_decay=weight_decay, capturable=graphed)
+    optimizer = FusedAdamW(model.parameters(), lr=learning_rate, weight_decay=weight_decay, capturable=graphed, max_grad_norm=max_grad_norm)
     scheduler = torch.optim.lr_scheduler.ExponentialLR(optimizer, gamma=gamma)
     criterion = nn.CrossEntropyLoss()
     run = _BatchRunner(model, optimizer, criterion, reducer, split_precision, graphed)

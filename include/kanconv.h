@@ -470,6 +470,43 @@ int kan_adamw_dev_args(const double* lr_dev, const int* step_dev, double beta1, 
  * not outlive the call. */
 int kan_set_u64_table(unsigned long long* table, int first, const unsigned long long* values, int n, void* stream);
 
+/* ---- Global-norm gradient clipping inside the step.  The reference asks for it at evaluations.py:33
+ * (`clip_grad_norm_(model.parameters(), max_norm=1.0)  # Prevent exploding gradients`, called there before any gradient exists, so it does
+ * nothing) and for per-parameter gradient norms in the commented-out `GRAD NORM` print of evaluations.py:66-71.  torch walks the parameter list on
+ * the host, launches a norm per tensor and rescales every gradient in place; here two launches leave the norm and the clip coefficient in DEVICE
+ * memory and the segment step multiplies by the coefficient as it reads the gradient -- the gradients themselves are not modified.
+ * All four entry points run on `stream`, allocate nothing, read no host memory after they return and may be stream-captured; null pointers,
+ * n_chunks <= 0 (n_seg <= 0) and a chunk_elems that is not a positive multiple of 4 are refused before any launch (kan_last_error()).
+ *
+ * Sum of squares per chunk, over the chunk table of kan_adamw_step_segments (evaluations.py:33, the inner `torch.linalg.vector_norm` per
+ * parameter): workgroup b reads elements [chunk_start[b], chunk_start[b] + chunk_elems) of the gradient at seg_grad[chunk_seg[b]] and writes ONE
+ * double, partial[b]; exactly 0.0 where the address is 0.  Each square is (double)g * (double)g; every sum is in double in a fixed order (thread,
+ * wave, workgroup), without atomics: two launches give the same bits.  Nothing else is written.  One launch per parameter group, each at its own
+ * offset into `partial`. */
+int kan_grad_sqnorm_chunks(const unsigned long long* seg_grad, const int* seg_n, const int* chunk_seg, const int* chunk_start, int n_chunks,
+                           int chunk_elems, double* partial, void* stream);
+
+/* The global norm and the clip coefficient (evaluations.py:33: `total_norm` over ALL parameters, `clip_coef = max_norm / (total_norm + 1e-6)`
+ * clamped to 1; evaluations.py:66-71: the norm per parameter).  One workgroup; segment s owns partial[seg_first_chunk[s] .. seg_first_chunk[s + 1])
+ * -- the tables span all parameter groups.  Writes seg_sq[s] (double, the squared norm of parameter s) for every s in [0, n_seg), sums them in
+ * ascending order, and writes out[0] = (float)sqrt(total) and out[1] = (float)min(1.0, (double)max_norm_dev[0] / (sqrt(total) + 1e-6)), formed in
+ * double and rounded once.  Non-finite values propagate as in torch: an inf or NaN gradient gives a non-finite norm and the coefficient that
+ * expression gives for it, and a NaN quotient stays NaN (torch.clamp's rule), so the step after it poisons the parameters as torch's would. */
+int kan_grad_norm_finish(const double* partial, const int* seg_first_chunk, int n_seg, const float* max_norm_dev, double* seg_sq, float* out,
+                         void* stream);
+
+/* kan_adamw_step_segments and kan_adamw_step_segments_dev (generic_train.py:24-25) with grad_scale read from scale_dev[0] (DEVICE float: out + 1
+ * of kan_grad_norm_finish) instead of passed by value: the clipped step of evaluations.py:33 without the in-place rescaling pass.  The element
+ * update is the same function, and the two plain entry points are the same kernels instantiated without the pointer.  scale_dev is
+ * read at run time, so a recorded launch clips by whatever the recorded finish launch in front of it computes at replay. */
+int kan_adamw_step_segments_clip(float* p, float* m, float* v, const unsigned long long* seg_grad, const long long* seg_off, const int* seg_n,
+                                 const int* chunk_seg, const int* chunk_start, const float* seg_bias, int n_chunks, int chunk_elems, double lr,
+                                 double beta1, double beta2, double eps, double weight_decay, int step, const float* scale_dev, void* stream);
+int kan_adamw_step_segments_dev_clip(float* p, float* m, float* v, const unsigned long long* seg_grad, const long long* seg_off, const int* seg_n,
+                                     const int* chunk_seg, const int* chunk_start, const double* lr_dev, const int* seg_step, int n_chunks,
+                                     int chunk_elems, double beta1, double beta2, double eps, double weight_decay, const float* scale_dev,
+                                     void* stream);
+
 /* ---------------------------------------------------------------------------------------------- cross-entropy loss and test metrics
  * The criterion of the training script (generic_train.py:26 `nn.CrossEntropyLoss()`, called at evaluations.py:61 and :131: mean reduction, no
  * class weights, no ignore_index, no label smoothing) and what the evaluation loop collects per batch (evaluations.py:131-136: the batch loss,
