@@ -19,6 +19,7 @@ from .layers.kan_conv import relukan_conv   # noqa: F401,E402
 from .optim import FusedAdamW   # noqa: F401,E402
 from .train import GraphedStep, train_step, train_model_generic, evaluate, train_and_test_models   # noqa: F401,E402
 from .loss import CrossEntropyLoss, ClassMetrics   # noqa: F401,E402
+from .anomaly import AnomalyProbe   # noqa: F401,E402
 from .data import DeviceBatches, device_batches, TRANSFORMS   # noqa: F401,E402
 from .data import ResizedDeviceBatches, imagenet_device_batches, IMAGENET_TRANSFORMS, ResizeTables, resample_coeffs, resize_tables   # noqa: F401,E402
 from .layers.gram_layers import GRAMKANConvNDLayer, GRAMKANConv2DLayer   # noqa: F401,E402

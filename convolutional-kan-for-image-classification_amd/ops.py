@@ -1383,6 +1383,28 @@ def cross_entropy(logits: torch.Tensor, target: torch.Tensor, metrics=None) -> t
     return _CrossEntropy.apply(logits, target, getattr(metrics, "buffer", metrics))
 
 
+# --------------------------------------------------------------------------------------- the non-finite probe
+def count_nonfinite(t: torch.Tensor, record: torch.Tensor, tick: torch.Tensor) -> None:
+    """Add the number of NaN / +inf / -inf elements of fp32 ``t`` to ``record`` -- three int64 on ``t``'s device, [elements, first_tick, last_tick] --
+    with one launch of csrc/kan_guard.hip on the current stream; ``tick`` (one int64 on the device, read by the kernel) is what first_tick / last_tick
+    are set to when the launch finds something.  No autograd, no host read, nothing returned; usable while the stream is capturing.  A tensor that
+    is not contiguous is counted through a dense copy.  What ``AnomalyProbe`` launches per slot (the reference's counterpart: train.py:431)."""
+    if not isinstance(t, torch.Tensor):
+        raise L.KanConvError(f"count_nonfinite takes a tensor, got {type(t).__name__}")
+    if not t.is_cuda:
+        raise L.KanConvError(f"the tensor is on {t.device}: this path runs only on a ROCm device (MI355X); there is no CPU fallback")
+    if t.dtype != torch.float32:
+        raise L.KanConvError(f"count_nonfinite takes float32, got {t.dtype}")
+    for name, b, n in (("record", record, 3), ("tick", tick, 1)):
+        if not (isinstance(b, torch.Tensor) and b.dtype == torch.int64 and b.device == t.device and b.numel() == n and b.is_contiguous()):
+            raise L.KanConvError(f"count_nonfinite: {name} must be {n} contiguous int64 on {t.device}")
+    if t.numel() == 0:                                                     # (an empty tensor has no address to hand over)
+        return
+    t = t.detach().contiguous()
+    L.check(L.load().kan_nonfinite_count(C.c_void_p(t.data_ptr()), t.numel(), C.c_void_p(tick.data_ptr()), C.c_void_p(record.data_ptr()), _stream(t)),
+            "kan_nonfinite_count")
+
+
 # --------------------------------------------------------------------------------------- batches from a device-resident uint8 dataset
 def prepare_batch(images: torch.Tensor, table: torch.Tensor, out_hw, mean, std, labels: Optional[torch.Tensor] = None,
                   channels_last: bool = True, out=None):

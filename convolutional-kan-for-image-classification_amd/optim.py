@@ -24,6 +24,11 @@ and one ``kan_grad_norm_finish`` leave the norm and ``min(1, c / (norm + 1e-6))`
 coefficient as they read each gradient (32 bytes per element instead of 28; ``p.grad`` itself is not modified).  ``opt.grad_norm``,
 ``opt.clip_scale`` and ``opt.grad_norms()`` (the per-parameter norms of evaluations.py:66-71) are device reads.  It works in both modes and inside
 a recorded step.
+
+``opt.skip_nonfinite = True`` (default False; ``capturable=True`` only) guards the step: the same statistics pass runs, with or without clipping,
+and one ``kan_adamw_guard`` launch decides ON THE DEVICE whether any gradient holds an inf or a NaN; if so the step kernels are handed an
+all-zero address table and touch no parameter, no moment and no step count.  ``opt.last_step_skipped`` / ``opt.skipped_steps`` are device views,
+``opt.guard_report()`` is one read.  The watchdog the reference keeps on the host (train.py:431); ``AnomalyProbe`` says where the value was born.
 """
 from __future__ import annotations
 
@@ -47,6 +52,8 @@ class FusedAdamW(torch.optim.Optimizer):
         self._captured = None
         self._max_grad_norm = self._check_max_norm(max_grad_norm)     # like capturable, not a param_groups entry
         self._clip = None
+        self._skip_nonfinite = False                 # a settable attribute, not a keyword: see skip_nonfinite
+        self._guard = None
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._flat = []
         for group in self.param_groups:
@@ -60,6 +67,8 @@ class FusedAdamW(torch.optim.Optimizer):
             self._flat.append(self._flatten(self.param_groups[-1]))
             if self._clip is not None:               # a new layout: the statistics buffer is rebuilt with it
                 self._clip = self._build_clip()
+            if self._guard is not None:              # and the guard's tables; the counters carry over
+                self._guard = self._build_guard(self._guard)
 
     # ------------------------------------------------------------------ layout
     @staticmethod
@@ -175,11 +184,12 @@ class FusedAdamW(torch.optim.Optimizer):
             clip["host"] = self._max_grad_norm
 
     def _launch_norm(self, lib, clip, work):
-        """The first pass of a clipping step: every group's address table, one chunk launch per group, one finish."""
+        """The first pass of a clipping (or guarded) step: every group's address table, one chunk launch per group, one finish."""
         if self.capturable:
             for _, group, flat, _, _ in work:                              # refuse a stale lr before anything is launched
                 self._sync_lr(group, flat)
-        self._sync_max_norm(clip)
+        if clip is self._clip:                                             # (the guard's own statistics buffer holds max_norm = inf for good)
+            self._sync_max_norm(clip)
         dev = clip["buf"].device
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         with torch.cuda.device(dev):
@@ -196,6 +206,88 @@ class FusedAdamW(torch.optim.Optimizer):
             L.check(lib.kan_grad_norm_finish(C.c_void_p(clip["partial"].data_ptr()), C.c_void_p(clip["seg_first_chunk"].data_ptr()),
                                              clip["seg_sq"].numel(), C.c_void_p(clip["out"].data_ptr() + 8), C.c_void_p(clip["seg_sq"].data_ptr()),
                                              C.c_void_p(clip["out"].data_ptr()), stream), "kan_grad_norm_finish")
+
+    # ------------------------------------------------------------------ the non-finite guard
+    @property
+    def skip_nonfinite(self):
+        """False (default: an inf or NaN gradient poisons what torch's ``error_if_nonfinite=False`` path poisons, and the launches are the ones
+        described under ``step``) or True: a step whose gradients hold an inf or a NaN leaves every parameter, both moments and every step count
+        alone.  Settable, like ``max_grad_norm``; needs ``capturable=True`` (the classic mode counts steps on the host and could not know about a
+        skip without a read: ValueError) and every parameter group on one device.  A recorded step freezes whether it is on."""
+        return self._skip_nonfinite
+
+    @skip_nonfinite.setter
+    def skip_nonfinite(self, value):
+        value = bool(value)
+        if value and not self.capturable:
+            raise ValueError("FusedAdamW.skip_nonfinite needs capturable=True: the classic step counts on the host and cannot skip without a read")
+        if value and self._guard is None:
+            self._guard = self._build_guard()
+        self._skip_nonfinite = value
+
+    def _build_guard(self, old=None):
+        """Everything the guard owns, apart from ``_clip`` and the flat blocks (whose layouts stay as they are): a statistics buffer of its own for
+        the steps that do not clip (``_build_clip``'s, with max_norm = inf), and ONE int64 buffer holding the five counters, one flag per
+        parameter, the group descriptors of ``kan_adamw_guard`` and a masked copy of every group's gradient address table."""
+        stats = self._build_clip()                                         # (refuses groups on several devices)
+        dev = stats["buf"].device
+        stats["out"][2:3].fill_(float("inf"))
+        stats["host"] = float("inf")
+        ns, live = stats["seg_sq"].numel(), [f for f in self._flat if f is not None]
+        buf = torch.zeros(5 + ns + 3 * len(live) + ns, dtype=torch.int64, device=dev)
+        at, desc, masked = 5 + ns + 3 * len(live), [], []
+        for f in self._flat:
+            if f is None:
+                masked.append(None)
+                continue
+            n = len(f["params"])
+            masked.append(buf[at:at + n])
+            desc += [f["tab"]["seg_grad"].data_ptr(), masked[-1].data_ptr(), n]
+            at += n
+        groups = buf[5 + ns:5 + ns + 3 * len(live)]
+        if desc:
+            groups.copy_(torch.tensor(desc, dtype=torch.int64))
+        if old is not None:
+            buf[:5].copy_(old["counters"])
+        return dict(stats=stats, buf=buf, counters=buf[:5], flags=buf[5:5 + ns], groups=groups, masked=masked, n_groups=len(live))
+
+    def _need_guard(self, what):
+        if self._guard is None:
+            raise L.KanConvError(f"FusedAdamW.{what} belongs to skip_nonfinite = True: this optimizer has never been guarded")
+        return self._guard
+
+    @property
+    def last_step_skipped(self):
+        """0-dim int64 DEVICE view: 1 if the last guarded step (or replay) was skipped, else 0.  No host read."""
+        return self._need_guard("last_step_skipped")["counters"][4]
+
+    @property
+    def skipped_steps(self):
+        """0-dim int64 DEVICE view: how many guarded steps were skipped since the counters were last cleared.  No host read."""
+        return self._need_guard("skipped_steps")["counters"][1]
+
+    def guard_report(self):
+        """ONE host read of the guard's counters: ``guarded_steps``, ``skipped_steps``, ``first_skipped`` / ``last_skipped`` (the ordinal, counting
+        guarded steps from 1, of the first / last skipped one; None if none) and ``nonfinite_params``: the parameters whose gradient held an inf
+        or a NaN in the LAST skipped step, as indices into the parameters that have ``requires_grad``, in ``param_groups`` order (the indexing of
+        ``grad_norms()``)."""
+        g = self._need_guard("guard_report()")
+        words = g["buf"][:5 + g["flags"].numel()].tolist()
+        guarded, skipped, first, last = words[:4]
+        return dict(guarded_steps=guarded, skipped_steps=skipped, first_skipped=first if skipped else None, last_skipped=last if skipped else None,
+                    nonfinite_params=[i for i, f in enumerate(words[5:]) if f] if skipped else [])
+
+    def reset_guard(self):
+        """Clear the guard's counters and flags (one small launch)."""
+        g = self._need_guard("reset_guard()")
+        g["buf"][:5 + g["flags"].numel()].zero_()
+
+    def _launch_guard(self, lib, stats):
+        g = self._guard
+        with torch.cuda.device(g["buf"].device):
+            L.check(lib.kan_adamw_guard(C.c_void_p(stats["seg_sq"].data_ptr()), stats["seg_sq"].numel(), C.c_void_p(g["groups"].data_ptr()),
+                                        g["n_groups"], C.c_void_p(g["counters"].data_ptr()), C.c_void_p(g["flags"].data_ptr()),
+                                        C.c_void_p(torch.cuda.current_stream(g["buf"].device).cuda_stream)), "kan_adamw_guard")
 
     # ------------------------------------------------------------------ torch.optim surface
     @torch.no_grad()
@@ -216,7 +308,15 @@ class FusedAdamW(torch.optim.Optimizer):
         modified: the scale exists only inside the step.  ``opt.grad_norm``, ``opt.clip_scale`` and ``opt.grad_norms()`` are device reads of what
         the step computed.  Under DP the step runs after ``reducer.finish()``, so the norm is that of the REDUCED gradients (every rank computes
         the same one).  A recorded step freezes that clipping is on; the VALUE of ``max_grad_norm`` is NOT frozen -- it is read from device memory
-        at replay time and brought up to date like ``lr``, by the eager step or by ``sync_hyper()``.  If no parameter has a gradient, nothing launches."""
+        at replay time and brought up to date like ``lr``, by the eager step or by ``sync_hyper()``.  If no parameter has a gradient, nothing launches.
+
+        ``skip_nonfinite = True`` (default False, and the launches are the ones above; capturable only): the two norm launches run whether or not
+        the step clips, then ONE ``kan_adamw_guard`` -- it tests the exact double sum of squares of every parameter's gradient (non-finite exactly
+        when the gradient holds an inf or a NaN; a finite gradient whose float32 norm overflows does NOT skip), counts, and writes per group a masked
+        copy of the address table, zeros if the step is to be skipped -- and ``kan_adamw_advance`` and the step kernels read that copy: a skipped
+        step changes no parameter, no moment and no step count.  One decision per step over all groups, taken from device memory: a recorded
+        step decides anew at every replay.  On a skipped step ``grad_norm`` / ``clip_scale`` / ``grad_norms()`` show the non-finite values that
+        caused it.  Version counters are bumped either way.  Under DP every rank sees the reduced gradients and decides alike."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -246,13 +346,18 @@ class FusedAdamW(torch.optim.Optimizer):
             if any(ptrs):
                 work.append((gi, group, flat, ptrs, keep))
         clip = self._clip if self._max_grad_norm is not None else None
-        if clip is not None and work:
+        guard = self._guard if self._skip_nonfinite and self.capturable else None
+        if guard is not None and work:
+            stats = clip if clip is not None else guard["stats"]           # the statistics pass runs with or without clipping
+            self._launch_norm(lib, stats, work)
+            self._launch_guard(lib, stats)
+        elif clip is not None and work:
             self._launch_norm(lib, clip, work)
         scale = C.c_void_p(clip["out"].data_ptr() + 4) if clip is not None else None
-        for _, group, flat, ptrs, _ in work:
+        for gi, group, flat, ptrs, _ in work:
             with torch.cuda.device(flat["block"].device):
                 if self.capturable:
-                    self._step_capturable(lib, group, flat, ptrs, scale)
+                    self._step_capturable(lib, group, flat, ptrs, scale, guard["masked"][gi] if guard is not None else None)
                 else:
                     self._step_classic(lib, group, flat, ptrs, scale)
             for p, a in zip(flat["params"], ptrs):                         # the kernel wrote through raw pointers: tell autograd (and the packed-
@@ -309,14 +414,16 @@ class FusedAdamW(torch.optim.Optimizer):
                                      "may be uploaded while the stream is capturing -- run one eager step, or call sync_hyper(), before recording")
             self._upload_lr(group, flat)
 
-    def _step_capturable(self, lib, group, flat, ptrs, scale):
+    def _step_capturable(self, lib, group, flat, ptrs, scale, masked=None):
+        """``masked``: None, or the guard's copy of the group's address table (all zeros on a skipped step), which both launches then read
+        instead of ``seg_grad``."""
         blk, tab = flat["block"], flat["tab"]
         self._sync_lr(group, flat)
-        if scale is None:
+        if scale is None and masked is None:                               # (the statistics pass of a clipping or guarded step filled every table)
             self._fill_table(lib, flat, ptrs)
         b1, b2 = group["betas"]
         stream = C.c_void_p(torch.cuda.current_stream(blk.device).cuda_stream)
-        seg_grad = C.c_void_p(tab["seg_grad"].data_ptr())
+        seg_grad = C.c_void_p((tab["seg_grad"] if masked is None else masked).data_ptr())
         row = lambda r: C.c_void_p(blk.data_ptr() + 4 * r * flat["n"])
         fn, name = (lib.kan_adamw_step_segments_dev, "kan_adamw_step_segments_dev") if scale is None else \
                    (lib.kan_adamw_step_segments_dev_clip, "kan_adamw_step_segments_dev_clip")
@@ -375,12 +482,18 @@ class FusedAdamW(torch.optim.Optimizer):
                     torch.autograd.graph.increment_version(p)
 
     def snapshot(self):
-        """Copies of everything a step changes on the device (parameters, both moments, the step counts) -- ``restore()`` puts them back."""
+        """Copies of everything a step changes on the device (parameters, both moments, the step counts; behind them, once the optimizer has been
+        guarded, the guard's counters and flags) -- ``restore()`` puts them back."""
         self._need_capturable("snapshot()")
-        return [None if flat is None else (flat["block"].clone(), flat["tab"]["seg_step"].clone()) for flat in self._flat]
+        saved = [None if flat is None else (flat["block"].clone(), flat["tab"]["seg_step"].clone()) for flat in self._flat]
+        if self._guard is not None:
+            saved.append(self._guard["buf"][:5 + self._guard["flags"].numel()].clone())
+        return saved
 
     @torch.no_grad()
     def restore(self, saved):
+        if self._guard is not None and len(saved) > len(self._flat):
+            self._guard["buf"][:saved[-1].numel()].copy_(saved[-1])
         for flat, s in zip(self._flat, saved):
             if flat is None:
                 continue

@@ -13,6 +13,7 @@ csrc/kan_loss.hip and the counters are read once per evaluation.  Datasets, chec
 from __future__ import annotations
 
 import contextlib
+import warnings
 from typing import Iterable, List, Optional, Tuple
 
 import torch
@@ -61,7 +62,9 @@ class GraphedStep:
     counter of every parameter the recorded step updates, so that a later eager forward (``evaluate``, a ragged last batch through ``train_step``)
     sees the new weights through the packed-weight cache.  Which parameters have a gradient, betas, eps and weight_decay are frozen at recording
     time.  Gradient clipping travels with the optimizer (``FusedAdamW(..., max_grad_norm=c)``): its norm kernels are part of the recorded step, and
-    ``max_grad_norm`` itself is read from device memory at replay time, like lr.  Not built: a recorded ``convkan_amd.CrossEntropyLoss``, and a DP
+    ``max_grad_norm`` itself is read from device memory at replay time, like lr.  So does the non-finite guard (``optimizer.skip_nonfinite = True``
+    before this object is built: the decision is taken on the device at every replay, and the warm-up leaves the guard's counters where it found
+    them); an ``AnomalyProbe`` attached to ``model`` before this object is built is recorded too, and every replay counts.  Not built: a recorded ``convkan_amd.CrossEntropyLoss``, and a DP
     reducer inside the graph.
 
         step = GraphedStep(model, example_data, example_target, optimizer=opt)       # opt = FusedAdamW(..., capturable=True)
@@ -147,23 +150,36 @@ class _BatchRunner:
 
 def train_model_generic(model: nn.Module, train_batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], device="cuda",
                         learning_rate: float = 1e-3, weight_decay: float = 1e-4, gamma: float = 0.8, epochs: int = 15,
-                        reducer=None, split_precision: bool = False, graphed: bool = False, max_grad_norm=None) -> List[float]:
+                        reducer=None, split_precision: bool = False, graphed: bool = False, max_grad_norm=None,
+                        skip_nonfinite: bool = False) -> List[float]:
     """generic_train.py:19-30 without the dataset / metric / checkpoint plumbing; returns the average loss per epoch.
     ``train_batches`` is re-iterated every epoch (a list of (data, target) pairs or a DataLoader).  ``split_precision``: handed to every ``train_step``.
     ``graphed``: the optimizer is a capturable ``FusedAdamW`` and the whole step of every full-size batch is one graph replay (``_BatchRunner``).
-    ``max_grad_norm``: None (off), or the global-norm clip the reference asks for at evaluations.py:33, done inside the optimizer step."""
+    ``max_grad_norm``: None (off), or the global-norm clip the reference asks for at evaluations.py:33, done inside the optimizer step.
+    ``skip_nonfinite``: sets ``FusedAdamW.skip_nonfinite`` (needs ``graphed=True``: ValueError otherwise) -- a step whose gradients hold an inf or a
+    NaN changes nothing; the guard's counters are read with the epoch's loss, and an epoch that skipped steps issues ONE ``warnings.warn`` with the
+    count and the parameter indices."""
+    if skip_nonfinite and not graphed:
+        raise ValueError("skip_nonfinite=True needs graphed=True (a capturable FusedAdamW)")
     model.to(device).train()
     optimizer = FusedAdamW(model.parameters(), lr=learning_rate, weight_decay=weight_decay, capturable=graphed, max_grad_norm=max_grad_norm)
+    optimizer.skip_nonfinite = bool(skip_nonfinite)
     scheduler = torch.optim.lr_scheduler.ExponentialLR(optimizer, gamma=gamma)
     criterion = nn.CrossEntropyLoss()
     run = _BatchRunner(model, optimizer, criterion, reducer, split_precision, graphed)
-    history = []
-    for _ in range(epochs):
+    history, skipped_before = [], 0
+    for epoch in range(epochs):
         total, n = torch.zeros((), device=device), 0
         for data, target in train_batches:
             total += run(data.to(device), target.to(device))
             n += 1
         history.append(float(total) / max(n, 1))
+        if skip_nonfinite:
+            report = optimizer.guard_report()
+            if report["skipped_steps"] > skipped_before:
+                warnings.warn(f"epoch {epoch}: {report['skipped_steps'] - skipped_before} of {n} optimizer steps were skipped for non-finite "
+                              f"gradients (last one: step {report['last_skipped']}, parameters {report['nonfinite_params']})", RuntimeWarning)
+            skipped_before = report["skipped_steps"]
         scheduler.step()
     return history
 
@@ -203,7 +219,8 @@ def train_and_test_models(model: nn.Module, train_batches: Iterable[Tuple[torch.
     counters), then ``scheduler.step()``.  Runs on the device the model is on.  Returns the first seven lists of evaluations.py:247: train loss,
     test loss, accuracy, precision, recall, F1 and the learning rate each epoch started with.  Checkpoints (``torch.save``), early stopping
     (``patience``), plots and timing are not carried over.  ``graphed``: ``optimizer`` must be a ``FusedAdamW(capturable=True)``; every full-size
-    training batch is then one replay of a recorded step, optimizer included (``_BatchRunner``), the evaluation stays eager."""
+    training batch is then one replay of a recorded step, optimizer included (``_BatchRunner``), the evaluation stays eager.  The optimizer is the
+    caller's: set ``optimizer.skip_nonfinite = True`` before the call for guarded steps, and read ``optimizer.guard_report()`` after it."""
     device = next(model.parameters()).device
     run = _BatchRunner(model, optimizer, criterion, reducer, split_precision, graphed)
     train_loss, test_loss, accuracy, precision, recall, f1, rates = [], [], [], [], [], [], []

@@ -507,6 +507,34 @@ int kan_adamw_step_segments_dev_clip(float* p, float* m, float* v, const unsigne
                                      int chunk_elems, double beta1, double beta2, double eps, double weight_decay, const float* scale_dev,
                                      void* stream);
 
+/* ---- Device-side anomaly mode (OPT-IN; with neither entry point in use the step and the layers launch what they launched before).
+ * The reference never trains without a watchdog: train.py:431 calls `torch.autograd.set_detect_anomaly(True)` unconditionally, which names the op
+ * that first produced a NaN, and evaluations.py:33 is commented "Prevent exploding gradients".  In a recorded training loop the host looks at
+ * nothing per step, so both halves live on the device: a probe that counts, and a guard that lets the optimizer step leave everything alone.
+ *
+ * The probe (train.py:431): counts the non-finite elements -- NaN, +inf, -inf: exponent bits all ones, decided on the bit pattern -- of the dense
+ * fp32 buffer x[0 .. n) and adds the count to record[0]; record is three int64 words in DEVICE memory, [elements, first_tick, last_tick], zeroed by
+ * the caller.  tick[0] (DEVICE int64, read at run time: a recorded launch sees the tick of its replay) is written to first_tick by the one launch
+ * that finds the record at zero elements and something to add, and to last_tick by every launch that finds something; a launch that finds nothing
+ * writes nothing.  Integer atomics only, at most three per workgroup that found something: the record is exact whatever the order.  HBM-bound:
+ * 4 bytes read per element, float4 loads where x is 16-byte aligned.  Runs on `stream`, allocates nothing, may be stream-captured.  Null pointers,
+ * n < 0, a tick or record that is not 8-byte aligned and an x that is not 4-byte aligned are refused before any launch; n == 0 launches nothing. */
+int kan_nonfinite_count(const float* x, long long n, const long long* tick, long long* record, void* stream);
+
+/* The guard of the optimizer step (evaluations.py:33, "Prevent exploding gradients"; torch's counterpart is the found_inf skip of
+ * torch.optim.AdamW under a GradScaler): ONE decision per step over all parameter groups, taken on the device, so replay k decides for step k.
+ * Launch it behind kan_grad_norm_finish.  seg_sq[0 .. n_seg) are that launch's exact double sums of squares per parameter -- finite fp32 squares
+ * cannot overflow a double, so seg_sq[s] is non-finite exactly when gradient s holds a non-finite element; the double's exponent bits are tested.
+ * groups[g] = { address of group g's seg_grad table, address of its masked copy, number of segments } (DEVICE, 3 x n_groups 8-byte words): the
+ * masked copy receives the addresses on a clean step and zeros on a skipped one, and is what kan_adamw_advance and the dev step are then handed --
+ * both skip a segment whose address is 0, so a skipped step touches no parameter, no moment and no step count.
+ * counters (int64, DEVICE, zeroed by the caller): [0] guarded steps, [1] skipped steps, [2] / [3] the ordinal (counting guarded steps from 1) of the
+ * first / last skipped step, [4] 1 if this step was skipped, else 0.  flags[s] (int64) is set to 1 / 0 for every s by a SKIPPED step -- 1 where
+ * gradient s was non-finite -- and left alone by a clean one.  One workgroup; no atomics.  Null pointers, n_seg < 1, n_groups < 1 and pointers that
+ * are not 8-byte aligned are refused before any launch. */
+int kan_adamw_guard(const double* seg_sq, int n_seg, const unsigned long long* groups, int n_groups, long long* counters, long long* flags,
+                    void* stream);
+
 /* ---------------------------------------------------------------------------------------------- cross-entropy loss and test metrics
  * The criterion of the training script (generic_train.py:26 `nn.CrossEntropyLoss()`, called at evaluations.py:61 and :131: mean reduction, no
  * class weights, no ignore_index, no label smoothing) and what the evaluation loop collects per batch (evaluations.py:131-136: the batch loss,
