@@ -207,7 +207,9 @@ __device__ __forceinline__ void stage_unit(const DevBasis& bs, const float* sTab
     }
     if (FAST != 0 && KIND == KAN_BASIS_CHEBY) {
         // cheby_kan_layers.py:93-96 by recurrence; tanh through hardware exp2/rcp: (e-1)/(e+1), e = exp(2x), |err| ~1e-7 absolute
-        const float t = fminf(fmaxf(kan_tanh_fast(xb), bs.p0), bs.p1);
+        // (clamp by compare and select: a NaN passes, as through torch.clamp; fminf / fmaxf would return the bound)
+        const float t0 = kan_tanh_fast(xb);
+        const float t = t0 < bs.p0 ? bs.p0 : t0 > bs.p1 ? bs.p1 : t0;
         float Tm = 1.f, Tc = t;
         col[0] = inb ? 1.f : 0.f;
 #pragma unroll
@@ -306,8 +308,9 @@ __device__ __forceinline__ void stage_unit(const DevBasis& bs, const float* sTab
             j0 = i - 3;
         }
         col[0] = base;
+        const float dead = inb ? bspline_dead(3, xa) : 0.f;              // 0, or NaN for a non-finite input (kan_device.h)
 #pragma unroll
-        for (int p = 1; p < 9; ++p) col[p * ld] = 0.f;
+        for (int p = 1; p < 9; ++p) col[p * ld] = dead;
         *(((unsigned)j0 < 8u) ? col + (1 + j0) * ld : dump) = N0;
         *(((unsigned)(j0 + 1) < 8u) ? col + (2 + j0) * ld : dump) = N1;
         *(((unsigned)(j0 + 2) < 8u) ? col + (3 + j0) * ld : dump) = N2;
@@ -316,13 +319,14 @@ __device__ __forceinline__ void stage_unit(const DevBasis& bs, const float* sTab
     }
     const int P = bs.P, hb = bs.hb;
     if (KIND == KAN_BASIS_BSPLINE) {
-        float base = 0.f, N[4] = {0.f, 0.f, 0.f, 0.f}; int j0 = -8;
+        float base = 0.f, dead = 0.f, N[4] = {0.f, 0.f, 0.f, 0.f}; int j0 = -8;
         if (inb) {
             if (hb) base = kan_act_fast(bs.act, xa);
+            dead = bspline_dead(bs.order, xb);
             if (!bspline_uniform<false>(bs.order, xb, sTab, bs.nb + bs.order + 1, bs.inv_h, j0, N)) j0 = -8;
         }
 #pragma unroll 1
-        for (int p = 0; p < P; ++p) col[p * ld] = (p < hb) ? base : 0.f;      // (run-time loop: see kan_planes_each)
+        for (int p = 0; p < P; ++p) col[p * ld] = (p < hb) ? base : dead;     // (run-time loop: see kan_planes_each)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             if (r <= bs.order) {                                     // uniform
@@ -359,7 +363,7 @@ __device__ __forceinline__ InGrad stage_unit_grad(const DevBasis& bs, const floa
     } else if constexpr (KIND == KAN_BASIS_CHEBY) {
         // dT_k/dx = k U_{k-1}(t) (1 - tanh^2 x) inside the clamp, 0 where it is active (kan_device.h), tanh as in stage_unit
         const float t0 = kan_tanh_fast(xa);
-        const float t = fminf(fmaxf(t0, bs.p0), bs.p1);
+        const float t = t0 < bs.p0 ? bs.p0 : t0 > bs.p1 ? bs.p1 : t0;      // a NaN passes, as in stage_unit
         const float chain = (t0 >= bs.p0 && t0 <= bs.p1) ? (1.0f - t0 * t0) : 0.f;
         float Um = 0.f, Uc = 1.f, sb = 0.f;
 #pragma unroll

@@ -36,8 +36,9 @@ __device__ __forceinline__ float kan_tanh_fast(float x) { return tanhf(x); }
 __device__ __forceinline__ float kan_exp2k(float x, float K) { return __builtin_amdgcn_exp2f(x * K); }
 __device__ __forceinline__ float kan_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 // tanh through hardware exp2 / rcp: (e - 1) / (e + 1), e = exp(2x) (argument clamped: e stays finite), |err| ~ 1e-7 absolute
+// (the clamp is a compare and select, not fminf: a NaN argument must come out NaN, and fminf(NaN, 40) is 40)
 __device__ __forceinline__ float kan_tanh_fast(float x) {
-    const float e = __builtin_amdgcn_exp2f(fminf(x, 40.f) * 2.88539008177792681472f);
+    const float e = __builtin_amdgcn_exp2f((x > 40.f ? 40.f : x) * 2.88539008177792681472f);
     return (e - 1.0f) * __builtin_amdgcn_rcpf(e + 1.0f);
 }
 #endif
@@ -103,6 +104,11 @@ __device__ __forceinline__ float kan_act_fast(int act, float x) {
 // (max |delta| vs the reference recursion 1.8e-7).  N[r] is basis j0 + r,
 // j0 = i - S.  With DERIV, N holds d/dx instead (the indicator has zero gradient, so this is
 // what autograd of the reference recursion evaluates to).  `kn`: knot table in LDS.
+// A basis that is zero at x, as the reference's recursion leaves it: (x - g_j) / (k h) * 0, which is 0 for every finite x and NaN for
+// +-inf and NaN (kan_layers.py:226-233); the order-0 indicator is a plain 0.  Every form of the value planes fills its dead planes with this,
+// so a non-finite input comes out NaN as it does there.
+__device__ __forceinline__ float bspline_dead(int S, float x) { return S >= 1 ? 0.f * x : 0.f; }
+
 template <bool DERIV>
 __device__ __forceinline__ bool bspline_uniform(int S, float x, const float* kn, int nkn, float inv_h,
                                                 int& j0, float (&N)[4]) {
@@ -111,12 +117,14 @@ __device__ __forceinline__ bool bspline_uniform(int S, float x, const float* kn,
     int i = (int)floorf((x - kn[0]) * inv_h);
     i = min(max(i, 0), NI - 1);
     float gi = kn[i];
-    if (S == 0) {                                    // piecewise constant: the cell itself is the value, settle it exactly
+    if (S <= 1) {
+        // piecewise constant value (S = 0) or derivative (S = 1: slopes -1/h, +1/h of the cell's two bases): the cell itself is the
+        // result, and the fp32 index above is one off for inputs on a knot or an ulp from it -- settle it exactly against the knots
         if (x < gi) { i = max(i - 1, 0); gi = kn[i]; }
         else if (x >= kn[i + 1]) { i = min(i + 1, NI - 1); gi = kn[i]; }
     }
-    // S >= 1: a cell picked one off at a knot (x within an ulp of g_i) only shifts u to ~0 or ~1 of the neighbour,
-    // where the pieces agree to O(ulp) (C^0 for S=1 ... C^2 for S=3); u is clamped below.
+    // S >= 2: a cell picked one off at a knot (x within an ulp of g_i) only shifts u to ~0 or ~1 of the neighbour,
+    // where the pieces and their derivatives agree to O(ulp) (C^1 for S=2, C^2 for S=3); u is clamped below.
     j0 = i - S;
 #ifdef KAN_EXACT_TRANSCENDENTALS
     // measurement build: u and the pieces in double on the fp32 knots themselves, rounded once (<= 0.5 ulp per plane)
@@ -193,6 +201,11 @@ __device__ __forceinline__ void kan_planes(const DevBasis& bs, const float* tabs
                 val = d == 0 ? N[0] : val; val = d == 1 ? N[1] : val; val = d == 2 ? N[2] : val; val = d == 3 ? N[3] : val;
                 if (j >= 0 && j < bs.nb && d <= bs.order) v[p] = val;
             }
+        } else if (!DERIV) {
+            const float dead = bspline_dead(bs.order, xb);
+#pragma unroll
+            for (int p = 0; p < KAN_PMAX; ++p)
+                if (p >= hb && p < hb + bs.nb) v[p] = dead;
         }
     } else if (KIND == KAN_BASIS_RBF) {
         // utils/utils.py:33  exp(-((x - c)/d)^2)
@@ -271,12 +284,13 @@ __device__ __forceinline__ void kan_planes_each(const DevBasis& bs, const float*
     if (KIND == KAN_BASIS_BSPLINE) {
         int j0 = 0; float N[4];
         const bool ok = bspline_uniform<DERIV>(bs.order, xb, tabs, nb + bs.order + 1, bs.inv_h, j0, N);
+        const float dead = DERIV ? 0.f : bspline_dead(bs.order, xb);
 #pragma unroll 1
         for (int j = 0; j < nb; ++j) {
             const int d = j - j0;
             float val = 0.f;
             val = d == 0 ? N[0] : val; val = d == 1 ? N[1] : val; val = d == 2 ? N[2] : val; val = d == 3 ? N[3] : val;
-            emit(hb + j, (ok && d >= 0 && d <= bs.order) ? val : 0.f);
+            emit(hb + j, (ok && d >= 0 && d <= bs.order) ? val : dead);
         }
     } else if (KIND == KAN_BASIS_RBF) {
         const float dn = bs.p0;
@@ -369,7 +383,7 @@ __device__ __forceinline__ void kan_planes_each(const DevBasis& bs, const float*
         // = k U_{k-1}(t) (1 - t0^2), zero where the clamp is active (clamp passes gradient on [lo, hi]).
         // One loop over the true degree k with a conditional emit, as the recurrence families above.
         const float t0 = tanhf(xb);
-        const float t = fminf(fmaxf(t0, bs.p0), bs.p1);
+        const float t = t0 < bs.p0 ? bs.p0 : t0 > bs.p1 ? bs.p1 : t0;      // torch.clamp passes a NaN on (fminf / fmaxf would return the bound)
         const bool inside = (t0 >= bs.p0) && (t0 <= bs.p1);
         const float chain = inside ? (1.0f - t0 * t0) : 0.f;
         float Tm = 1.f, Tc = t;              // T_{k-1}, T_k   at k = 1
