@@ -123,6 +123,8 @@ SIGNATURES = {
     "kan_adamw_step_segments_dev_clip": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _D, _D, _D, _D, _P, _P]),
     "kan_nonfinite_count": (_I, [_P, _LL, _P, _P, _P]),
     "kan_adamw_guard": (_I, [_P, _I, _P, _I, _P, _P, _P]),
+    "kan_grad_accumulate": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _I, _I, _P, _P]),
+    "kan_accum_gate": (_I, [_P, _I, _P, _I, _P, _P]),
     "kan_xent_workspace_bytes": (_LL, [_I]),
     "kan_xent_metrics_bytes": (_LL, [_I]),
     "kan_xent_fwd": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P]),

@@ -29,6 +29,13 @@ a recorded step.
 and one ``kan_adamw_guard`` launch decides ON THE DEVICE whether any gradient holds an inf or a NaN; if so the step kernels are handed an
 all-zero address table and touch no parameter, no moment and no step count.  ``opt.last_step_skipped`` / ``opt.skipped_steps`` are device views,
 ``opt.guard_report()`` is one read.  The watchdog the reference keeps on the host (train.py:431); ``AnomalyProbe`` says where the value was born.
+
+``opt.accumulate_steps = k`` (default 1: nothing changes) makes every ``step()`` call a MICRO-step of a window of k: ``kan_grad_accumulate`` per group
+adds the gradients into a flat fp32 accumulator row (the first call of a window overwrites it, the last one turns the sum into the mean), one
+``kan_accum_gate`` moves the window's counter, and the unchanged statistics / guard / advance / step kernels read a GATED address table -- the
+accumulator addresses on the k-th call, zeros otherwise.  ``capturable=True`` keeps the counter on the device, so a recorded step is ONE graph
+replayed per micro-batch and every k-th replay updates; the classic mode counts on the host.  The reference's loop (evaluations.py:44-72) has no
+accumulation; k micro-batches give the update k data-parallel ranks compute (mean of the shard gradients, one step).
 """
 from __future__ import annotations
 
@@ -54,6 +61,8 @@ class FusedAdamW(torch.optim.Optimizer):
         self._clip = None
         self._skip_nonfinite = False                 # a settable attribute, not a keyword: see skip_nonfinite
         self._guard = None
+        self._accum_k = 1                            # a settable attribute, not a keyword: see accumulate_steps
+        self._accum = None
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         self._flat = []
         for group in self.param_groups:
@@ -69,6 +78,8 @@ class FusedAdamW(torch.optim.Optimizer):
                 self._clip = self._build_clip()
             if self._guard is not None:              # and the guard's tables; the counters carry over
                 self._guard = self._build_guard(self._guard)
+            if self._accum is not None:              # and the accumulators: a new layout starts a fresh window
+                self._accum = self._build_accum(self._accum_k)
 
     # ------------------------------------------------------------------ layout
     @staticmethod
@@ -183,8 +194,9 @@ class FusedAdamW(torch.optim.Optimizer):
             clip["out"][2:3].fill_(self._max_grad_norm)                    # a fill launch carrying the value: no host memory is read later
             clip["host"] = self._max_grad_norm
 
-    def _launch_norm(self, lib, clip, work):
-        """The first pass of a clipping (or guarded) step: every group's address table, one chunk launch per group, one finish."""
+    def _launch_norm(self, lib, clip, work, src=None):
+        """The first pass of a clipping (or guarded) step: every group's address table, one chunk launch per group, one finish.  ``src``: None, or
+        per group the table to read instead of ``seg_grad`` (the gated tables of an accumulating step, which filled ``seg_grad`` already)."""
         if self.capturable:
             for _, group, flat, _, _ in work:                              # refuse a stale lr before anything is launched
                 self._sync_lr(group, flat)
@@ -194,12 +206,13 @@ class FusedAdamW(torch.optim.Optimizer):
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         with torch.cuda.device(dev):
             for _, _, flat, ptrs, _ in work:
-                self._fill_table(lib, flat, ptrs)
+                if src is None:
+                    self._fill_table(lib, flat, ptrs)
             if len(work) != sum(f is not None for f in self._flat):        # a group without any gradient launches nothing: its partials are 0
                 clip["partial"].zero_()
             for gi, _, flat, _, _ in work:
                 tab, c0 = flat["tab"], clip["chunk0"][gi]
-                L.check(lib.kan_grad_sqnorm_chunks(C.c_void_p(tab["seg_grad"].data_ptr()), C.c_void_p(tab["seg_n"].data_ptr()),
+                L.check(lib.kan_grad_sqnorm_chunks(C.c_void_p((tab["seg_grad"] if src is None else src[gi]).data_ptr()), C.c_void_p(tab["seg_n"].data_ptr()),
                                                    C.c_void_p(tab["chunk_seg"].data_ptr()), C.c_void_p(tab["chunk_start"].data_ptr()),
                                                    tab["chunk_seg"].numel(), _CHUNK, C.c_void_p(clip["partial"].data_ptr() + 8 * c0), stream),
                         "kan_grad_sqnorm_chunks")
@@ -282,12 +295,151 @@ class FusedAdamW(torch.optim.Optimizer):
         g = self._need_guard("reset_guard()")
         g["buf"][:5 + g["flags"].numel()].zero_()
 
-    def _launch_guard(self, lib, stats):
+    def _launch_guard(self, lib, stats, groups=None):
+        """``groups``: None, or the descriptors to use instead of the guard's own (an accumulating step: the gated tables are the source it masks)."""
         g = self._guard
         with torch.cuda.device(g["buf"].device):
-            L.check(lib.kan_adamw_guard(C.c_void_p(stats["seg_sq"].data_ptr()), stats["seg_sq"].numel(), C.c_void_p(g["groups"].data_ptr()),
+            L.check(lib.kan_adamw_guard(C.c_void_p(stats["seg_sq"].data_ptr()), stats["seg_sq"].numel(),
+                                        C.c_void_p((g["groups"] if groups is None else groups).data_ptr()),
                                         g["n_groups"], C.c_void_p(g["counters"].data_ptr()), C.c_void_p(g["flags"].data_ptr()),
                                         C.c_void_p(torch.cuda.current_stream(g["buf"].device).cuda_stream)), "kan_adamw_guard")
+
+    # ------------------------------------------------------------------ gradient accumulation
+    @property
+    def accumulate_steps(self):
+        """1 (default: every ``step()`` call is a step, nothing is allocated and the launches are the ones described under ``step``) or k > 1: every
+        ``step()`` call is micro-step m of a window of k, and only the k-th applies an update -- ONE AdamW step with the MEAN of the k gradients.
+        Settable, like ``skip_nonfinite``; not a constructor keyword and not a ``param_groups`` entry (a ``state_dict`` keeps loading into
+        ``torch.optim.AdamW``).  Anything but an int >= 1: ValueError.  Changing it inside an open window (``micro_step != 0``; see
+        ``reset_accumulation()``) or while the stream is capturing: ``KanConvError``.  k is a kernel argument: a recorded step freezes it.
+
+        Inside a window ``max_grad_norm`` clips by the norm of the MEAN (``grad_norm`` reads 0 and ``clip_scale`` 1 after a call that is no
+        boundary; ``p.grad`` is never modified), the guard skips the window's update if ANY micro-gradient was non-finite (the first call of the
+        next window overwrites the accumulator: nothing leaks), a parameter without a gradient in the whole window is skipped as torch skips it, and
+        step counts advance once per window.  ``state_dict()`` is unchanged: an OPEN WINDOW IS NOT CHECKPOINTED -- save on a boundary, or the
+        micro-steps of the open window are lost on resume.  ``snapshot()`` / ``restore()`` do cover it."""
+        return self._accum_k
+
+    @accumulate_steps.setter
+    def accumulate_steps(self, value):
+        if isinstance(value, bool) or not isinstance(value, int) or value < 1:
+            raise ValueError(f"FusedAdamW.accumulate_steps must be an int >= 1, got {value!r}")
+        if value == self._accum_k:
+            return
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise L.KanConvError("FusedAdamW.accumulate_steps cannot change while the stream is capturing: set it before recording")
+        if self.micro_step != 0:
+            raise L.KanConvError(f"FusedAdamW.accumulate_steps cannot change inside an open window (micro_step = {self.micro_step} of "
+                                 f"{self._accum_k}): finish the window or call reset_accumulation()")
+        self._accum = self._build_accum(value) if value > 1 and hasattr(self, "_flat") else None
+        self._accum_k = value
+
+    def _build_accum(self, k):
+        """Everything accumulation owns (the flat blocks and their tables stay as they are): per group ONE fp32 accumulator row with the layout of
+        the flat block, and ONE int64 buffer holding the window's state -- the counter (int32, word 0) and one int32 ``seen`` flag per parameter --,
+        then the group descriptors of ``kan_accum_gate``, per group the table of accumulator addresses and the gated table."""
+        live = [f for f in self._flat if f is not None]
+        dev = live[0]["block"].device if live else torch.device("cpu")
+        if any(f["block"].device != dev for f in live):
+            raise L.KanConvError("FusedAdamW.accumulate_steps: one window counter needs every parameter group on one device")
+        ns = [0 if f is None else len(f["params"]) for f in self._flat]
+        seen_words = [(n + 1) // 2 for n in ns]                            # int32 flags in 8-byte words: every table stays 8-byte aligned
+        n_state = 1 + sum(seen_words)
+        buf = torch.zeros(n_state + 4 * len(live) + 2 * sum(ns), dtype=torch.int64, device=dev)
+        rows, seen, addr, gated, desc, addr_host = [], [], [], [], [], []
+        at_seen, at = 1, n_state + 4 * len(live)
+        for f, n, w in zip(self._flat, ns, seen_words):
+            if f is None:
+                rows.append(None); seen.append(None); addr.append(None); gated.append(None); addr_host.append(None)
+                continue
+            rows.append(torch.zeros(f["n"], dtype=torch.float32, device=dev))
+            seen.append(buf[at_seen:at_seen + w].view(torch.int32)[:n])
+            addr.append(buf[at:at + n]); gated.append(buf[at + n:at + 2 * n])
+            addr_host.append([rows[-1].data_ptr() + 4 * o for o in f["tab"]["seg_off"].tolist()])       # (one read, at build time)
+            addr[-1].copy_(torch.tensor(addr_host[-1], dtype=torch.int64))
+            desc += [addr[-1].data_ptr(), gated[-1].data_ptr(), seen[-1].data_ptr(), n]
+            at_seen, at = at_seen + w, at + 2 * n
+        groups = buf[n_state:n_state + 4 * len(live)]
+        if desc:
+            groups.copy_(torch.tensor(desc, dtype=torch.int64))
+        return dict(k=k, buf=buf, state=buf[:n_state], micro=buf[:1].view(torch.int32)[:1], rows=rows, seen=seen, addr=addr, gated=gated,
+                    groups=groups, n_groups=len(live), addr_host=addr_host, micro_host=0, seen_host=[[False] * n for n in ns], gated_host=[None] * len(ns),
+                    guard_groups=None)
+
+    @property
+    def micro_step(self):
+        """The index m of the NEXT ``step()`` call within its window, an int in [0, accumulate_steps); 0 = no window is open.  ``capturable=True``:
+        ONE device read (the counter lives on the device); it is never read on the step path."""
+        if self._accum is None:
+            return 0
+        return int(self._accum["micro"].item()) if self.capturable else self._accum["micro_host"]
+
+    def reset_accumulation(self):
+        """Drop an open window: the next ``step()`` call is micro-step 0 and overwrites the accumulators.  Never while the stream is capturing."""
+        if self._accum is None:
+            return
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise L.KanConvError("FusedAdamW.reset_accumulation() while the stream is capturing: call it before recording")
+        a = self._accum
+        a["state"].zero_()
+        a["micro_host"], a["seen_host"] = 0, [[False] * len(s) for s in a["seen_host"]]
+
+    def _guard_groups(self, acc):
+        """The guard's group descriptors with the gated tables as the source it masks (built once per guard layout)."""
+        g = self._guard
+        if acc["guard_groups"] is None or acc["guard_groups"][0] is not g:
+            desc = []
+            for gated, masked in zip(acc["gated"], g["masked"]):
+                if gated is not None:
+                    desc += [gated.data_ptr(), masked.data_ptr(), gated.numel()]
+            acc["guard_groups"] = (g, torch.tensor(desc, dtype=torch.int64).to(g["buf"].device))
+        return acc["guard_groups"][1]
+
+    def _launch_accumulate(self, lib, acc, work, micro_dev, m):
+        for gi, _, flat, ptrs, _ in work:
+            tab = flat["tab"]
+            with torch.cuda.device(flat["block"].device):
+                self._fill_table(lib, flat, ptrs)
+                L.check(lib.kan_grad_accumulate(C.c_void_p(acc["rows"][gi].data_ptr()), C.c_void_p(tab["seg_grad"].data_ptr()),
+                                                C.c_void_p(tab["seg_off"].data_ptr()), C.c_void_p(tab["seg_n"].data_ptr()),
+                                                C.c_void_p(tab["chunk_seg"].data_ptr()), C.c_void_p(tab["chunk_start"].data_ptr()),
+                                                tab["chunk_seg"].numel(), _CHUNK, micro_dev, m, acc["k"], C.c_void_p(acc["seen"][gi].data_ptr()),
+                                                C.c_void_p(torch.cuda.current_stream(flat["block"].device).cuda_stream)), "kan_grad_accumulate")
+
+    def _accumulate_capturable(self, lib, acc, work, guard):
+        """Micro-step of the capturable mode: the accumulate launch of every group, then the gate.  The device decides what the launches behind it see."""
+        for _, group, flat, _, _ in work:                                  # refuse a stale lr before anything is launched
+            self._sync_lr(group, flat)
+        if guard is not None:
+            self._guard_groups(acc)                                        # (an upload: never between recorded launches)
+        self._launch_accumulate(lib, acc, work, C.c_void_p(acc["micro"].data_ptr()), 0)
+        dev = acc["buf"].device
+        with torch.cuda.device(dev):
+            L.check(lib.kan_accum_gate(C.c_void_p(acc["groups"].data_ptr()), acc["n_groups"], C.c_void_p(acc["micro"].data_ptr()), acc["k"],
+                                       C.c_void_p(guard["counters"].data_ptr() if guard is not None else 0),
+                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)), "kan_accum_gate")
+
+    def _accumulate_classic(self, lib, acc, work):
+        """Micro-step of the classic mode: the host counts.  Inside a window only the accumulate kernel is launched (returns []); on the boundary
+        the ordinary step is handed the accumulator addresses of the parameters the window saw, through the gated tables."""
+        m, k = acc["micro_host"], acc["k"]
+        self._launch_accumulate(lib, acc, work, None, m)
+        for gi, _, _, ptrs, _ in work:
+            acc["seen_host"][gi] = [s or bool(a) for s, a in zip(acc["seen_host"][gi], ptrs)]
+        if m + 1 < k:
+            acc["micro_host"] = m + 1
+            return []
+        out = []
+        for gi, group, flat, _, keep in work:
+            ptrs = [a if s else 0 for a, s in zip(acc["addr_host"][gi], acc["seen_host"][gi])]
+            if ptrs != acc["gated_host"][gi]:                              # (the same parameters window after window: usually nothing)
+                acc["gated"][gi].copy_(torch.tensor(ptrs, dtype=torch.int64), non_blocking=False)
+                acc["gated_host"][gi] = ptrs
+            if any(ptrs):
+                out.append((gi, group, flat, ptrs, keep))
+        acc["state"].zero_()                                               # the kernel's seen flags: the host keeps its own
+        acc["micro_host"], acc["seen_host"] = 0, [[False] * len(s) for s in acc["seen_host"]]
+        return out
 
     # ------------------------------------------------------------------ torch.optim surface
     @torch.no_grad()
@@ -316,7 +468,13 @@ class FusedAdamW(torch.optim.Optimizer):
         copy of the address table, zeros if the step is to be skipped -- and ``kan_adamw_advance`` and the step kernels read that copy: a skipped
         step changes no parameter, no moment and no step count.  One decision per step over all groups, taken from device memory: a recorded
         step decides anew at every replay.  On a skipped step ``grad_norm`` / ``clip_scale`` / ``grad_norms()`` show the non-finite values that
-        caused it.  Version counters are bumped either way.  Under DP every rank sees the reduced gradients and decides alike."""
+        caused it.  Version counters are bumped either way.  Under DP every rank sees the reduced gradients and decides alike.
+
+        ``accumulate_steps = k`` (default 1, and the launches are the ones above): the call is a micro-step.  The address tables are filled as
+        always, then ONE ``kan_grad_accumulate`` per group and -- capturable -- ONE ``kan_accum_gate``, and everything above runs unchanged on the
+        GATED tables: the accumulator addresses on the k-th call, zeros (no parameter, moment or step count touched; ``grad_norm`` 0,
+        ``clip_scale`` 1; neither a guarded nor a skipped step) on the others.  The classic mode counts on the host and launches only the
+        accumulate kernel inside a window.  See ``accumulate_steps``."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -343,27 +501,36 @@ class FusedAdamW(torch.optim.Optimizer):
                     g = g.to(device=blk.device, dtype=torch.float32).contiguous()
                     keep.append(g)
                 ptrs.append(g.data_ptr())
-            if any(ptrs):
+            if any(ptrs) or self._accum is not None:                       # an accumulating call runs every group: the window may hold its gradient
                 work.append((gi, group, flat, ptrs, keep))
         clip = self._clip if self._max_grad_norm is not None else None
         guard = self._guard if self._skip_nonfinite and self.capturable else None
+        acc = self._accum if work else None
+        if acc is not None and not self.capturable:
+            work = self._accumulate_classic(lib, acc, work)                # the boundary's work (accumulator addresses), or [] inside a window
+            if not work and clip is not None:                              # no step: the statistics read what the capturable mode computes there,
+                clip["out"][0:1].zero_()                                   # norm 0 and coefficient 1 (two fill launches, only when clipping)
+                clip["out"][1:2].fill_(1.0)
+        elif acc is not None:
+            self._accumulate_capturable(lib, acc, work, guard)
+        src = acc["gated"] if acc is not None else None                    # what everything below reads where it read seg_grad
         if guard is not None and work:
             stats = clip if clip is not None else guard["stats"]           # the statistics pass runs with or without clipping
-            self._launch_norm(lib, stats, work)
-            self._launch_guard(lib, stats)
+            self._launch_norm(lib, stats, work, src)
+            self._launch_guard(lib, stats, self._guard_groups(acc) if acc is not None else None)
         elif clip is not None and work:
-            self._launch_norm(lib, clip, work)
+            self._launch_norm(lib, clip, work, src)
         scale = C.c_void_p(clip["out"].data_ptr() + 4) if clip is not None else None
         for gi, group, flat, ptrs, _ in work:
             with torch.cuda.device(flat["block"].device):
                 if self.capturable:
-                    self._step_capturable(lib, group, flat, ptrs, scale, guard["masked"][gi] if guard is not None else None)
+                    self._step_capturable(lib, group, flat, ptrs, scale, guard["masked"][gi] if guard is not None else src[gi] if acc is not None else None)
                 else:
-                    self._step_classic(lib, group, flat, ptrs, scale)
+                    self._step_classic(lib, group, flat, ptrs, scale, src[gi] if acc is not None else None)
             for p, a in zip(flat["params"], ptrs):                         # the kernel wrote through raw pointers: tell autograd (and the packed-
-                if a:                                                      # weight cache of ops.py) that the values changed.  Host-only, legal
-                    torch.autograd.graph.increment_version(p)              # under capture; a replay bumps them in after_replay()
-        del work
+                if a or (acc is not None and self.capturable):             # weight cache of ops.py) that the values changed.  Host-only, legal
+                    torch.autograd.graph.increment_version(p)              # under capture; a replay bumps them in after_replay().  (A capturable
+        del work                                                           # accumulating call does not know the boundary: it bumps every time.)
         return loss
 
     def _fill_table(self, lib, flat, ptrs):
@@ -383,9 +550,10 @@ class FusedAdamW(torch.optim.Optimizer):
             tab["seg_grad"].copy_(torch.tensor(ptrs, dtype=torch.int64), non_blocking=False)
             tab["grad_ptrs"] = ptrs
 
-    def _step_classic(self, lib, group, flat, ptrs, scale):
+    def _step_classic(self, lib, group, flat, ptrs, scale, table=None):
+        """``table``: None, or the device table that already holds ``ptrs`` (an accumulating step's gated table), read instead of ``seg_grad``."""
         blk, tab = flat["block"], flat["tab"]
-        if scale is None:
+        if scale is None and table is None:
             self._fill_table(lib, flat, ptrs)                              # (a clipping step filled every table in its first pass)
         b1, b2 = group["betas"]
         steps = flat["steps"]                                              # torch counts steps per parameter
@@ -400,7 +568,7 @@ class FusedAdamW(torch.optim.Optimizer):
         row = lambda r: C.c_void_p(blk.data_ptr() + 4 * r * flat["n"])
         fn, name = (lib.kan_adamw_step_segments, "kan_adamw_step_segments") if scale is None else \
                    (lib.kan_adamw_step_segments_clip, "kan_adamw_step_segments_clip")
-        L.check(fn(row(0), row(1), row(2), C.c_void_p(tab["seg_grad"].data_ptr()), C.c_void_p(tab["seg_off"].data_ptr()),
+        L.check(fn(row(0), row(1), row(2), C.c_void_p((tab["seg_grad"] if table is None else table).data_ptr()), C.c_void_p(tab["seg_off"].data_ptr()),
                    C.c_void_p(tab["seg_n"].data_ptr()), C.c_void_p(tab["chunk_seg"].data_ptr()), C.c_void_p(tab["chunk_start"].data_ptr()),
                    C.c_void_p(bias.data_ptr() if bias is not None else 0), tab["chunk_seg"].numel(), _CHUNK, group["lr"], b1, b2, group["eps"],
                    group["weight_decay"], group["step"], 1.0 if scale is None else scale,
@@ -415,8 +583,8 @@ class FusedAdamW(torch.optim.Optimizer):
             self._upload_lr(group, flat)
 
     def _step_capturable(self, lib, group, flat, ptrs, scale, masked=None):
-        """``masked``: None, or the guard's copy of the group's address table (all zeros on a skipped step), which both launches then read
-        instead of ``seg_grad``."""
+        """``masked``: None, or the guard's copy of the group's address table (all zeros on a skipped step) -- or, accumulating without a guard, the
+        gated table --, which both launches then read instead of ``seg_grad``."""
         blk, tab = flat["block"], flat["tab"]
         self._sync_lr(group, flat)
         if scale is None and masked is None:                               # (the statistics pass of a clipping or guarded step filled every table)
@@ -483,15 +651,25 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def snapshot(self):
         """Copies of everything a step changes on the device (parameters, both moments, the step counts; behind them, once the optimizer has been
-        guarded, the guard's counters and flags) -- ``restore()`` puts them back."""
+        guarded, the guard's counters and flags; behind those, with ``accumulate_steps > 1``, a dict holding the accumulator rows and the window's
+        counter and ``seen`` flags) -- ``restore()`` puts them back.  With ``accumulate_steps == 1`` the list is what it always was."""
         self._need_capturable("snapshot()")
         saved = [None if flat is None else (flat["block"].clone(), flat["tab"]["seg_step"].clone()) for flat in self._flat]
         if self._guard is not None:
             saved.append(self._guard["buf"][:5 + self._guard["flags"].numel()].clone())
+        if self._accum is not None:
+            saved.append(dict(accum_rows=[None if r is None else r.clone() for r in self._accum["rows"]], accum_state=self._accum["state"].clone()))
         return saved
 
     @torch.no_grad()
     def restore(self, saved):
+        if saved and isinstance(saved[-1], dict):                          # the window of an accumulating optimizer
+            saved, window = saved[:-1], saved[-1]
+            if self._accum is not None and window["accum_state"].numel() == self._accum["state"].numel():
+                self._accum["state"].copy_(window["accum_state"])
+                for row, r in zip(self._accum["rows"], window["accum_rows"]):
+                    if row is not None:
+                        row.copy_(r)
         if self._guard is not None and len(saved) > len(self._flat):
             self._guard["buf"][:saved[-1].numel()].copy_(saved[-1])
         for flat, s in zip(self._flat, saved):

@@ -25,7 +25,10 @@ from .optim import FusedAdamW
 def train_step(model: nn.Module, data: torch.Tensor, target: torch.Tensor, optimizer: torch.optim.Optimizer,
                criterion: Optional[nn.Module] = None, reducer=None, split_precision: bool = False) -> torch.Tensor:
     """One batch: returns the (detached, device-resident) loss.  ``split_precision``: OPT-IN, the forward and backward of this step run inside
-    ``ops.split_precision_training()`` (the conv launches of the layers in its scope in split precision; everything else exact)."""
+    ``ops.split_precision_training()`` (the conv launches of the layers in its scope in split precision; everything else exact).
+    With ``optimizer.accumulate_steps = k > 1`` (``FusedAdamW``) the call is a micro-step: the gradients are still zeroed and recomputed per call --
+    the optimizer accumulates them itself -- and only every k-th call updates; the loss returned is the micro-batch's.  Folding the reducer's
+    ``no_sync()`` into this is not built: with a reducer every micro-step still all-reduces, which is correct (the mean of means) but wasteful."""
     criterion = criterion if criterion is not None else nn.CrossEntropyLoss()
     optimizer.zero_grad()
     with _split_context(split_precision):
@@ -51,7 +54,10 @@ class GraphedStep:
     single layers (BASELINE config 2: 0.23 ms replayed against 0.43-0.48 ms eager, bit-identical); KAN-VGG11 at bs 256 keeps the GPU busy either way.
     The weight packs are recorded unconditionally (``ops.always_pack``): the replay reads the weights as they are at replay time, so an optimizer may
     update them in place between replays.  ``split_precision=True`` (OPT-IN) warms up and records inside ``ops.split_precision_training()``.
-    Do not call ``zero_grad`` between replays: the recorded backward assigns ``p.grad`` (static tensors) rather than accumulating.
+    Do not call ``zero_grad`` between replays: the recorded backward assigns ``p.grad`` (static tensors) rather than accumulating.  To accumulate,
+    set ``optimizer.accumulate_steps = k`` before this object is built: the recorded ``step()`` is then a micro-step whose window counter lives on
+    the device -- ONE graph, replayed per micro-batch, and every k-th replay updates; the warm-up's micro-steps are undone with the rest, so the
+    first replay is micro-step 0 of a fresh window.  ``loss`` stays the micro-batch's loss.
     The criterion inside a recorded step is torch's: ``convkan_amd.CrossEntropyLoss`` (the device-side counters of ``ClassMetrics``) is refused here --
     recording it is not supported yet; ``train_step`` takes it.
 
@@ -151,19 +157,24 @@ class _BatchRunner:
 def train_model_generic(model: nn.Module, train_batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], device="cuda",
                         learning_rate: float = 1e-3, weight_decay: float = 1e-4, gamma: float = 0.8, epochs: int = 15,
                         reducer=None, split_precision: bool = False, graphed: bool = False, max_grad_norm=None,
-                        skip_nonfinite: bool = False) -> List[float]:
+                        skip_nonfinite: bool = False, accumulate_steps: int = 1) -> List[float]:
     """generic_train.py:19-30 without the dataset / metric / checkpoint plumbing; returns the average loss per epoch.
     ``train_batches`` is re-iterated every epoch (a list of (data, target) pairs or a DataLoader).  ``split_precision``: handed to every ``train_step``.
     ``graphed``: the optimizer is a capturable ``FusedAdamW`` and the whole step of every full-size batch is one graph replay (``_BatchRunner``).
     ``max_grad_norm``: None (off), or the global-norm clip the reference asks for at evaluations.py:33, done inside the optimizer step.
     ``skip_nonfinite``: sets ``FusedAdamW.skip_nonfinite`` (needs ``graphed=True``: ValueError otherwise) -- a step whose gradients hold an inf or a
     NaN changes nothing; the guard's counters are read with the epoch's loss, and an epoch that skipped steps issues ONE ``warnings.warn`` with the
-    count and the parameter indices."""
+    count and the parameter indices.
+    ``accumulate_steps``: sets ``FusedAdamW.accumulate_steps`` before anything is recorded -- every batch is a micro-batch and every k-th one
+    updates with the mean gradient, graphed or not.  The losses averaged per epoch stay the micro-batches' losses; a window left open at the end of
+    an epoch carries into the next one (the scheduler moves lr between its micro-steps, and the update uses the lr of its boundary call); one left
+    open at the very end is dropped with the optimizer.  With a ``reducer`` every micro-step still all-reduces: correct, but wasteful."""
     if skip_nonfinite and not graphed:
         raise ValueError("skip_nonfinite=True needs graphed=True (a capturable FusedAdamW)")
     model.to(device).train()
     optimizer = FusedAdamW(model.parameters(), lr=learning_rate, weight_decay=weight_decay, capturable=graphed, max_grad_norm=max_grad_norm)
     optimizer.skip_nonfinite = bool(skip_nonfinite)
+    optimizer.accumulate_steps = accumulate_steps
     scheduler = torch.optim.lr_scheduler.ExponentialLR(optimizer, gamma=gamma)
     criterion = nn.CrossEntropyLoss()
     run = _BatchRunner(model, optimizer, criterion, reducer, split_precision, graphed)
@@ -220,7 +231,8 @@ def train_and_test_models(model: nn.Module, train_batches: Iterable[Tuple[torch.
     test loss, accuracy, precision, recall, F1 and the learning rate each epoch started with.  Checkpoints (``torch.save``), early stopping
     (``patience``), plots and timing are not carried over.  ``graphed``: ``optimizer`` must be a ``FusedAdamW(capturable=True)``; every full-size
     training batch is then one replay of a recorded step, optimizer included (``_BatchRunner``), the evaluation stays eager.  The optimizer is the
-    caller's: set ``optimizer.skip_nonfinite = True`` before the call for guarded steps, and read ``optimizer.guard_report()`` after it."""
+    caller's: set ``optimizer.skip_nonfinite = True`` before the call for guarded steps, and read ``optimizer.guard_report()`` after it; set
+    ``optimizer.accumulate_steps = k`` before the call for accumulation (a window left open at the end of an epoch carries into the next)."""
     device = next(model.parameters()).device
     run = _BatchRunner(model, optimizer, criterion, reducer, split_precision, graphed)
     train_loss, test_loss, accuracy, precision, recall, f1, rates = [], [], [], [], [], [], []

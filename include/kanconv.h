@@ -535,6 +535,44 @@ int kan_nonfinite_count(const float* x, long long n, const long long* tick, long
 int kan_adamw_guard(const double* seg_sq, int n_seg, const unsigned long long* groups, int n_groups, long long* counters, long long* flags,
                     void* stream);
 
+/* ---- Gradient accumulation decided on the device (OPT-IN: FusedAdamW.accumulate_steps = k > 1; with k == 1 neither entry point is launched).
+ * The loop these extend is evaluations.py:44-72 -- one `optimizer.zero_grad()` / `loss.backward()` / `optimizer.step()` per batch.  The reference
+ * has NO accumulation: its effective batch is its loader's batch.  A window of k micro-steps here computes what k data-parallel ranks compute: the
+ * mean of the k shard gradients (the reducer's AVG), then ONE AdamW step.  Both entry points run on `stream`, allocate nothing, read no host memory
+ * after they return and may be stream-captured.
+ *
+ * One micro-step of one parameter group, on the grid and chunk tables of kan_adamw_step_segments (n_chunks workgroups of 256 threads; seg_grad,
+ * seg_off, seg_n, chunk_seg, chunk_start as there).  acc is a flat fp32 row with the layout of the optimizer's flat block (segment s at
+ * [seg_off[s], seg_off[s] + seg_n[s]); the alignment padding between segments is never read or written).  m, the index of this micro-step within
+ * the window of k, is micro_dev[0] (DEVICE int32, read at run time: a recorded launch sees the m of its replay) or, with micro_dev == NULL, the
+ * argument m in [0, k):
+ *   m == 0          acc = g              a copy: the bits survive (-0.0 stays -0.0) and what the previous window left is never read; a segment whose
+ *                                        seg_grad[s] is 0 is zero-filled
+ *   0 < m < k - 1   acc = acc + g        one fp32 add per element; a segment whose address is 0 is left alone
+ *   m == k - 1      acc = (acc + g) * s  s = (float)(1.0 / k): acc then holds the mean, to be read as an ordinary gradient; a segment whose address is
+ *                                        0 in this call becomes acc * s (it may have had a gradient earlier in the window)
+ * With k == 1 every call is the first row.  float4 accesses where the gradient address is 16-byte aligned, scalar ones otherwise (bucket views, odd
+ * offsets).  seen[s] (int32, DEVICE) is set to 1 for every segment whose address is not 0; nothing clears it here.  HBM-bound: 12 bytes per
+ * element, 8 at m == 0.  Null pointers (micro_dev excepted), n_chunks < 1, a chunk_elems that is not a positive multiple of 4, k < 1, an m outside
+ * [0, k) when micro_dev is NULL, an acc that is not 16-byte aligned and tables that are not aligned to their element size are refused before any
+ * launch. */
+int kan_grad_accumulate(float* acc, const unsigned long long* seg_grad, const long long* seg_off, const int* seg_n, const int* chunk_seg,
+                        const int* chunk_start, int n_chunks, int chunk_elems, const int* micro_dev /* nullable */, int m, int k, int* seen,
+                        void* stream);
+
+/* The gate: ONE launch per optimizer call (evaluations.py:72 `optimizer.step()`, which the reference reaches on every batch), behind the
+ * accumulate launches of all groups and in front of any statistics launch.  groups[g] = { address of group g's table of accumulator addresses
+ * (acc + seg_off[s], 8-byte words), address of its GATED table, address of its seen flags (int32), number of segments } (DEVICE, 4 x n_groups 8-byte
+ * words); micro is the window's counter (DEVICE int32, one per optimizer).
+ *   micro[0] + 1 == k   gated[s] = seen[s] ? accumulator address : 0 for every segment of every group; seen is cleared; micro[0] = 0
+ *   otherwise           gated[s] = 0 everywhere; micro[0] += 1
+ * kan_grad_sqnorm_chunks, kan_adamw_guard (as the source it masks), kan_adamw_advance and the dev step are handed the gated table where they are
+ * handed seg_grad otherwise: off the boundary they see no gradient and change nothing -- the norm reads 0, the coefficient 1.  guard_counters: NULL, or
+ * the counters of the kan_adamw_guard launch that follows in the same call; that launch counts one guarded step, so off the boundary the gate
+ * subtracts one from guard_counters[0] in advance and the guard's ordinals count windows.  One workgroup, ordinary stores, no atomics.  Null groups
+ * or micro, n_groups < 1, k < 1, groups or guard_counters not 8-byte aligned and a micro that is not 4-byte aligned are refused before any launch. */
+int kan_accum_gate(const unsigned long long* groups, int n_groups, int* micro, int k, long long* guard_counters /* nullable */, void* stream);
+
 /* ---------------------------------------------------------------------------------------------- cross-entropy loss and test metrics
  * The criterion of the training script (generic_train.py:26 `nn.CrossEntropyLoss()`, called at evaluations.py:61 and :131: mean reduction, no
  * class weights, no ignore_index, no label smoothing) and what the evaluation loop collects per batch (evaluations.py:131-136: the batch loss,
