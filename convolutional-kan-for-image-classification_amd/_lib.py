@@ -18,7 +18,7 @@ KAN_MAX_TABLE = 32
 KAN_FP_WORDS = 192
 BASIS_BSPLINE, BASIS_RBF, BASIS_CHEBY, BASIS_POLY, BASIS_FOURIER, BASIS_RELU, BASIS_GRAM = 0, 1, 2, 3, 4, 5, 6
 ACT_NONE, ACT_IDENTITY, ACT_GELU, ACT_SILU, ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_GELU_TANH = -1, 0, 1, 2, 3, 4, 5, 6
-ORDER_QUAD_FWD, ORDER_ROWBLK8_FWD, ORDER_QUAD_BWD_DATA, ORDER_FWD_WEIGHT_SIDE = 1, 2, 4, 8        # kan_tile_orders bits (KAN_ORDER_*)
+ORDER_QUAD_FWD, ORDER_ROWBLK8_FWD, ORDER_QUAD_BWD_DATA, ORDER_FWD_WEIGHT_SIDE, ORDER_POS8_BWD_DATA = 1, 2, 4, 8, 16        # kan_tile_orders bits (KAN_ORDER_*)
 
 
 class KanGeom(C.Structure):

@@ -432,6 +432,12 @@ int plan_conv(const KanGeom* g, const KanBasis* b, ConvPlan* cp) {
     // 8x8 planes: row blocks on half-plane tiles of 4 images (k_conv_fwd_halo<4, 8, 4, 4>) instead of whole planes of 2: the same B / 2 tiles, splits
     // and slabs, again invisible in KanPlan (row_blocks stays 0 for these geometries)
     c.rowblk8_fwd = halo && g->H == 8 && g->W == 8 && c.fc.TO == 256 && g->B % 4 == 0 && !tuning_off("KAN_ROWBLK8_FWD");
+    // 8x8 planes, bwd-data: tiles of 32 images x 4 adjacent columns of one plane row, fed from dz_pm when the caller passes it (the plan does not ask for the
+    // copy: dz_pm_wanted stays 0; ops builds it where kan_tile_orders reports this bit).  The same B / 2 tiles, splits and slabs; exactly the 484 of 576
+    // (position, tap) blocks with a source are issued.  The epilogue moves x and dx 16 bytes at a time.
+    c.pos8_bd = !tuning_off("KAN_POS8_BD") && fast_has(f, ON_ROWBLK_BWD_DATA) && !c.pm_bwd_data && !dw && g->H == 8 && g->W == 8 && g->Ho == 8 && g->Wo == 8 &&
+                g->kh == 3 && g->kw == 3 && g->sh == 1 && g->sw == 1 && g->ph == 1 && g->pw == 1 && g->dh == 1 && g->dw == 1 && g->B % 32 == 0 &&
+                g->O % 16 == 0 && g->x_bstride % 4 == 0 && (long long)g->O * 64 * g->B * 4 < (1ll << 31);
     // 2x2 planes under 3x3 / s1 / p1 / d1: the expanded forward puts the four output positions on the weight side of its tiles (32 outputs x 4
     // positions x 128 images: the same 32 tiles per split) and stores whole 16-byte groups z[b][o][0..3]; same steps per split, same slabs
     // bit for bit (0.212 -> 0.153 ms per launch on 512 -> 512); -DKAN_TUNING_KNOBS + KAN_PMDMA_FWD_WQ=0 runs the other order

@@ -947,6 +947,43 @@ __device__ __forceinline__ void wave_reduce_scatter(float (&v)[M], int lane, int
         }                                                                                                                          \
     } while (0)
 
+// RB = 3 (8x8 planes, 3x3 / stride 1 / pad 1, B a multiple of 32, dz given as dz_pm[(o * 64 + position) * B + image]): RB = 2 carried over with another wave
+// layout.  The tile is 32 images x 4 adjacent columns of one plane row (h, w0 .. w0 + 3, w0 in {0, 4}), tile = image group * 16 + 2 h + w0 / 4 (the same B / 2
+// tiles), column n = block * 32 + image, block j = position (h, w0 + j); sG[block][16 outputs][32 images] is filled as for RB = 2.  The tap rows whose source
+// row h + 1 - r leaves the plane (h = 0 and h = 7: three taps each) are dead for the whole tile: their steps are skipped outright (no copies, no barrier) and
+// the split ranges are cut over the live steps.  The tap columns kill block 0 of the w0 = 0 tiles (t = 2) and block 3 of the w0 = 4 tiles (t = 0): exactly 484
+// of the 576 (position, tap) blocks are issued.  Each wave owns 32 ROWS x all four blocks (one A read and four B reads per k-pair; the accumulators are the
+// same 64 registers, acc[j >> 1][j & 1] = block j), so between two barriers every wave skips the same block: no wave waits for another.  Epilogue: thread
+// (image = tid & 31, channel = tid >> 5) contracts its channel's planes for the four positions and moves x and dx as one float4 each.  Dispatch: the 9-tap
+// tiles (rows 1-6) first, then all h = 0 tiles, then all h = 7 tiles (each class walks wd in step with itself), the image group being slot % groups so that
+// with 8 groups an XCD keeps one group's dz_pm and x in its L2; B / 2 tiles exceed TilePerm's 64 entries, so the order is arithmetic.  tools/probe/pos8_bwd_emul.py restates this index arithmetic in numpy.
+#define LDS_READ5(ra, r0, r1, r2, r3, addrA, addrB, oA, oB)                                                                              \
+    asm volatile("ds_read_b32 %0, %5 offset:%7\n\tds_read_b32 %1, %6 offset:%8\n\tds_read_b32 %2, %6 offset:%9\n\t"                    \
+                 "ds_read_b32 %3, %6 offset:%10\n\tds_read_b32 %4, %6 offset:%11"                                                        \
+                 : "=&v"(ra), "=&v"(r0), "=&v"(r1), "=&v"(r2), "=&v"(r3)                                                                \
+                 : "v"(addrA), "v"(addrB), "n"(oA), "n"(oB), "n"((oB) + 512 * 4), "n"((oB) + 1024 * 4), "n"((oB) + 1536 * 4) : "memory")
+#define LDS_WAIT5(ra, r0, r1, r2, r3, N) asm volatile("s_waitcnt lgkmcnt(" #N ")" : "+v"(ra), "+v"(r0), "+v"(r1), "+v"(r2), "+v"(r3) :: "memory")
+// One step on that tile for a wave of 32 rows x 4 blocks: l0 / l3 = the outer blocks alive (wave-uniform, the same in every wave of the workgroup)
+#define KAN_MFMA_STEP_POS8(NK, addrA, LDA, addrB, l0, l3)                                                                           \
+    do {                                                                                                                           \
+        float fa_[2], fb_[2][4];                                                                                                   \
+        LDS_READ5(fa_[0], fb_[0][0], fb_[0][1], fb_[0][2], fb_[0][3], addrA, addrB, 0, 0);                                         \
+        _Pragma("unroll") for (int kk = 0; kk < (NK); ++kk) {                                                                       \
+            const int c_ = kk & 1, n_ = c_ ^ 1;                                                                                    \
+            if (kk + 1 < (NK)) {                                                                                                   \
+                LDS_READ5(fa_[n_], fb_[n_][0], fb_[n_][1], fb_[n_][2], fb_[n_][3], addrA, addrB, (2 * (kk + 1)) * (LDA) * 4,       \
+                          (2 * (kk + 1)) * 32 * 4);                                                                                \
+                LDS_WAIT5(fa_[c_], fb_[c_][0], fb_[c_][1], fb_[c_][2], fb_[c_][3], 5);                                             \
+            } else {                                                                                                               \
+                LDS_WAIT5(fa_[c_], fb_[c_][0], fb_[c_][1], fb_[c_][2], fb_[c_][3], 0);                                             \
+            }                                                                                                                      \
+            if (l0) acc[0][0] = MFMA32(fa_[c_], fb_[c_][0], acc[0][0]);                                                            \
+            acc[0][1] = MFMA32(fa_[c_], fb_[c_][1], acc[0][1]);                                                                    \
+            acc[1][0] = MFMA32(fa_[c_], fb_[c_][2], acc[1][0]);                                                                    \
+            if (l3) acc[1][1] = MFMA32(fa_[c_], fb_[c_][3], acc[1][1]);                                                            \
+        }                                                                                                                          \
+    } while (0)
+
 template <int KIND, int FAST, int RB = 0>
 __global__ __launch_bounds__(256, 4) void k_conv_bwd_data(
     const float* __restrict__ dz, const float* __restrict__ x, const float* __restrict__ xn, const float* __restrict__ wd,
@@ -968,11 +1005,21 @@ __global__ __launch_bounds__(256, 4) void k_conv_bwd_data(
     const int px_tile0 = (perm.n ? (int)perm.idx[blk.x] : blk.x) * TP, ct = blk.y - grp * n_ct;
     const int ncol = n_ct * 128;
     const int pxl = (wave & 1) * 64 + lane, ol0 = wave >> 1;
-    const bool idle_rows = (ct * 2 + w_r) * CH >= g.C;        // this wave's 64-row half lies wholly in the channel padding (last tile)
+    // this wave's 64-row half lies wholly in the channel padding (last tile); (RB == 3) likewise its 32-row quarter of the half
+    const bool idle_rows = RB == 3 ? (ct * 2 + w_r) * CH * P + w_p * 32 >= g.C * P || w_p * 32 >= CH * P : (ct * 2 + w_r) * CH >= g.C;
+    // (RB == 3) the tile: dispatch slot blk.x -> tile (9-tap rows first, then the h = 0 tiles, then the h = 7 tiles), tile -> (image group, row, column half)
+    int p8_tile = blk.x;
+    if (RB == 3) {
+        const int ng = (int)gridDim.x >> 4, nmid = 12 * ng;
+        // (image group = slot % ng: with 8 groups every XCD -- workgroups are dealt to them round-robin -- keeps ONE group's dz_pm and x in its L2)
+        if (blk.x < nmid) { const int k = blk.x / ng; p8_tile = (blk.x - k * ng) * 16 + 2 + k; }
+        else { const int y = blk.x - nmid, cls = y >= 2 * ng ? 1 : 0, y2 = y - cls * 2 * ng, k = y2 / ng; p8_tile = (y2 - k * ng) * 16 + cls * 14 + k; }
+    }
+    const int p8_b0 = (p8_tile >> 4) * 32, p8_h = (p8_tile >> 1) & 7, p8_w0 = (p8_tile & 1) * 4;
     {
         const size_t xo = (size_t)grp * g.C * HW;
         x += xo; xn += xo; dx += xo; if (dxn) dxn += xo;
-        dz += (size_t)grp * g.O * HoWo * ((g.pix_major || RB == 2) ? g.B : 1);
+        dz += (size_t)grp * g.O * HoWo * ((g.pix_major || RB >= 2) ? g.B : 1);
         wd += (size_t)grp * (g.kh * g.kw) * Opad16 * ncol;
     }
 
@@ -1120,6 +1167,30 @@ __global__ __launch_bounds__(256, 4) void k_conv_bwd_data(
         }
     };
 
+    // (RB == 3) wave wv copies block wv = position (p8_h, p8_w0 + wv): dead under t = 0 in column 7, under t = 2 in column 0 (dead tap ROWS are skipped as
+    // whole steps below); the same per-lane offset with 64 positions per output
+    const int p8_col = p8_w0 + wv;
+    const unsigned p8_voff = (unsigned)((lane >> 3) * 64 * g.B + (lane & 7) * 4) * 4u;
+    auto issue_p8 = [&](int ch, int buf) {
+        const int tap = ch / n_ob, o0 = (ch - tap * n_ob) * KD;                       // scalar
+        pend_tap = tap;
+        float* dW = smem + buf * (2 * KD * 128);
+        float* dG = dW + KD * 128 + wv * 512;
+        const int r = tap / 3, t = tap - r * 3;
+        if ((unsigned)(p8_col + 1 - t) < 8u) {                                         // uniform: a dead block's copy is not issued
+            const unsigned so = (unsigned)((o0 * 64 + (p8_h + 1 - r) * 8 + (p8_col + 1 - t)) * g.B + p8_b0) * 4u;      // scalar part: (output block, source position, image group)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(dz_rs, (__attribute__((address_space(3))) void*)dG, 16, (int)p8_voff, (int)so, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(dz_rs, (__attribute__((address_space(3))) void*)(dG + 256), 16, (int)p8_voff,
+                                                     (int)(so + (unsigned)(8 * 64 * g.B) * 4u), 0, 0);
+        }
+        const char* wsrc = (const char*)(wd + ((size_t)tap * Opad16 + o0) * ncol + ct * 128);      // scalar
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int blk2 = j * 4 + wv;
+            glds16((const float*)(wsrc + (size_t)blk2 * 2 * ncol * 4 + wlane), dW + blk2 * 256);
+        }
+    };
+
     f32x16 acc[2][2];
 #pragma unroll
     for (int a = 0; a < 2; ++a)
@@ -1131,15 +1202,21 @@ __global__ __launch_bounds__(256, 4) void k_conv_bwd_data(
     int ch0 = blk.z * chunks_per_split;
     int ch1 = min(n_chunks, ch0 + chunks_per_split);
     unsigned tapmask = 0xffffffffu;                        // taps alive for some pixel position of this tile
-    if (g.pix_major) {
+    const bool skip_taps = g.pix_major || RB == 3;
+    if (skip_taps) {
         tapmask = 0;
         const int T = g.kh * g.kw;
-        const int hwA = px_tile0 / g.B, hwB = min(px_tile0 + TP - 1, Min - 1) / g.B;
-        for (int hw = hwA; hw <= hwB; ++hw)
-            for (int tap = 0; tap < T; ++tap) tapmask |= (tap_alive_in(g, hw, tap) ? 1u : 0u) << tap;
+        if (RB == 3) {                                     // tap rows whose source row h + 1 - r lies in the plane
+            for (int r = 0; r < 3; ++r) tapmask |= ((unsigned)(p8_h + 1 - r) < 8u ? 7u : 0u) << (3 * r);
+        } else {
+            const int hwA = px_tile0 / g.B, hwB = min(px_tile0 + TP - 1, Min - 1) / g.B;
+            for (int hw = hwA; hw <= hwB; ++hw)
+                for (int tap = 0; tap < T; ++tap) tapmask |= (tap_alive_in(g, hw, tap) ? 1u : 0u) << tap;
+        }
         auto seg = [&](int tap) { return tap * n_ob; };     // steps are (tap, output block)
         const int L = live_step_count(tapmask, T, n_chunks, seg);
-        const int S = min((int)gridDim.z, max(1, (L + chunks_per_split - 1) / chunks_per_split));   // ~chunks_per_split live steps each
+        // ~chunks_per_split live steps each; (RB == 3) every slab of the plan an equal share of the tile's live steps
+        const int S = RB == 3 ? min((int)gridDim.z, max(1, L)) : min((int)gridDim.z, max(1, (L + chunks_per_split - 1) / chunks_per_split));
         if (blk.z >= S) { ch0 = ch1 = n_chunks; }
         else {
             ch0 = blk.z == 0 ? 0 : live_step_pos(tapmask, T, n_chunks, (int)((long long)L * blk.z / S), seg);
@@ -1147,7 +1224,7 @@ __global__ __launch_bounds__(256, 4) void k_conv_bwd_data(
         }
     }
     auto next_live = [&](int ch) -> int {                  // steps are (tap, output block): skip dead taps whole
-        if (!g.pix_major) return ch;
+        if (!skip_taps) return ch;
         while (ch < ch1) {
             const int tap = ch / n_ob;
             if ((tapmask >> tap) & 1u) return ch;
@@ -1155,8 +1232,11 @@ __global__ __launch_bounds__(256, 4) void k_conv_bwd_data(
         }
         return ch1;
     };
+    auto issue_step = [&](int ch, int buf) {
+        if (RB == 3) issue_p8(ch, buf); else if (RB == 2) issue_q(ch, buf); else if (RB) issue_rb(ch, buf); else issue(ch, buf);
+    };
     int ch = next_live(ch0);
-    if (ch < ch1) { if (RB == 2) issue_q(ch, 0); else if (RB) issue_rb(ch, 0); else issue(ch, 0); }
+    if (ch < ch1) issue_step(ch, 0);
     const int ar = w_r * 64 + (lane & 31), bp = w_p * 64 + (lane & 31), kh2 = lane >> 5;
     for (int cur = 0; ch < ch1; cur ^= 1) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's async copies of the step have landed ...
@@ -1164,11 +1244,17 @@ __global__ __launch_bounds__(256, 4) void k_conv_bwd_data(
         const bool mixed_now = pend_mixed;
         const int tap_now = pend_tap;
         ch = next_live(ch + 1);
-        if (ch < ch1) { if (RB == 2) issue_q(ch, cur ^ 1); else if (RB) issue_rb(ch, cur ^ 1); else issue(ch, cur ^ 1); }
+        if (ch < ch1) issue_step(ch, cur ^ 1);
         const float* cW = smem + cur * (2 * KD * 128);
         const float* cG = cW + KD * 128;
         const unsigned aw = lds_addr(cW + kh2 * 128 + ar), ag = lds_addr(cG + kh2 * TP + bp);
-        if (RB == 2) {
+        if (RB == 3) {
+            // rows wave * 32 .. + 31 x the four blocks: block 0 has no source under t = 2 in the w0 = 0 tiles, block 3 none under t = 0 in the w0 = 4 tiles
+            const unsigned aw8 = lds_addr(cW + kh2 * 128 + wave * 32 + (lane & 31)), ag8 = lds_addr(cG + kh2 * 32 + (lane & 31));
+            const int t_now = tap_now % 3;
+            const bool l0 = !(p8_w0 == 0 && t_now == 2), l3 = !(p8_w0 == 4 && t_now == 0);
+            if (!idle_rows) KAN_MFMA_STEP_POS8(KD / 2, aw8, 128, ag8, l0, l3);
+        } else if (RB == 2) {
             const unsigned agq = lds_addr(cG + (2 * w_p) * 512 + kh2 * 32 + (lane & 31));
             const bool l0 = ((q_live0 >> tap_now) & 1u) != 0, l1 = ((q_live1 >> tap_now) & 1u) != 0;
             if (!idle_rows) KAN_MFMA_STEP_QUAD(KD / 2, aw, 128, agq, l0, l1);
@@ -1202,6 +1288,48 @@ __global__ __launch_bounds__(256, 4) void k_conv_bwd_data(
         // the two inputs of one half at a time.
         constexpr FastSpec S = fast_spec(FAST);
         constexpr int FP = S.planes, FCH = 64 / FP, NIT = (FCH + 1) / 2, NPF = S.xn_bwd ? 1 : 2;      // NPF: halves prefetched at once
+        if constexpr (RB == 3) {
+            // thread = (image, channel): the four positions of its channel are 16 contiguous bytes of x and of dx (the host checked the alignment); a
+            // wave's G rows are (wave & 1) * 32 .. + 31 of its half, all 128 columns
+            constexpr int NQ = (FCH + 7) / 8;
+            const int img = tid & 31, cl0 = tid >> 5;
+            const size_t pix = (size_t)(p8_b0 + img) * g.xbs + (size_t)(p8_h * 8 + p8_w0);
+            float4 xq[2][NQ]; unsigned okq = 0;
+#pragma unroll
+            for (int half = 0; half < 2; ++half)
+#pragma unroll
+                for (int it = 0; it < NQ; ++it) {
+                    const int cl = cl0 + 8 * it, c = (ct * 2 + half) * FCH + cl;
+                    const bool v = cl < FCH && c < g.C;
+                    xq[half][it] = v ? *reinterpret_cast<const float4*>(x + pix + (size_t)c * HW) : make_float4(0.f, 0.f, 0.f, 0.f);
+                    okq |= (v ? 1u : 0u) << (half * NQ + it);
+                }
+#pragma unroll
+            for (int half = 0; half < 2; ++half) {
+                __syncthreads();                           // previous readers of smem are done
+                if (w_r == half) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) smem[(w_p * 32 + mfma_row(r, lane)) * TP + j * 32 + (lane & 31)] = acc[j >> 1][j & 1][r];
+                }
+                __syncthreads();
+#pragma unroll
+                for (int it = 0; it < NQ; ++it) {
+                    if (!((okq >> (half * NQ + it)) & 1u)) continue;
+                    const int cl = cl0 + 8 * it, c = (ct * 2 + half) * FCH + cl;
+                    const float4 xa = xq[half][it];
+                    const float* Gc = smem + (cl * FP) * TP + img;
+                    float4 d;
+                    d.x = stage_unit_grad<KIND, FAST>(bs, sTab, xa.x, xa.x, Gc, TP).dx;
+                    d.y = stage_unit_grad<KIND, FAST>(bs, sTab, xa.y, xa.y, Gc + 32, TP).dx;
+                    d.z = stage_unit_grad<KIND, FAST>(bs, sTab, xa.z, xa.z, Gc + 64, TP).dx;
+                    d.w = stage_unit_grad<KIND, FAST>(bs, sTab, xa.w, xa.w, Gc + 96, TP).dx;
+                    *reinterpret_cast<float4*>(dxs + pix + (size_t)c * HW) = d;
+                }
+            }
+            return;
+        }
         float xv[NPF][NIT], nv[NIT]; unsigned ok = 0;
         // (a macro: as a by-reference lambda the same loop cost every spec ~30 instructions and, in some formulations, spills)
 #define KAN_FETCH(half, slot)                                                                                              \
@@ -3154,7 +3282,7 @@ int kan_tile_orders(const KanGeom* g, const KanBasis* b) {
     if (plan_conv(g, b, &cp)) return 0;
     const bool halo = cp.fwd == Route::HALO;
     return (halo && cp.quad_fwd ? KAN_ORDER_QUAD_FWD : 0) | (halo && cp.rowblk8_fwd ? KAN_ORDER_ROWBLK8_FWD : 0) | (cp.quad_bd ? KAN_ORDER_QUAD_BWD_DATA : 0) |
-           (cp.fwd_wq ? KAN_ORDER_FWD_WEIGHT_SIDE : 0);
+           (cp.fwd_wq ? KAN_ORDER_FWD_WEIGHT_SIDE : 0) | (cp.pos8_bd ? KAN_ORDER_POS8_BWD_DATA : 0);
 }
 
 int kan_pack_cacheable(const KanGeom* g, const KanBasis* b) {
@@ -3372,15 +3500,19 @@ static int conv_bwd_data_impl(const float* dz, const float* x, const float* xn, 
     const bool rb = !dg.pix_major && cp.rowblk_bwd_data;
     // ... with whole 32-image groups and the position-major copy of dz at hand: quadrant tiles fed from dz_pm (same tile count, splits and slabs)
     const bool quad = rb && cp.quad_bd && dz_pm && x == xn && !dxn;
-    const unsigned dz_bytes = (unsigned)((long long)g->B * g->y_bstride * 4);
+    // 8x8 planes, same conditions: tiles of 32 images x 4 columns of a plane row fed from dz_pm, dead tap rows and columns skipped (the kernel's RB = 3); its
+    // epilogue moves x and dx 16 bytes at a time (the planner checked the batch stride, the pointers are checked here)
+    const bool pos8 = cp.pos8_bd && !dg.pix_major && dz_pm && x == xn && !dxn && !dpar && ((uintptr_t)x | (uintptr_t)dx) % 16 == 0;
+    const unsigned dz_bytes = pos8 ? (unsigned)((long long)g->O * g->Ho * g->Wo * g->B * 4) : (unsigned)((long long)g->B * g->y_bstride * 4);
     auto launch = [&](auto kind, auto fast, auto rbv) {
         hipLaunchKernelGGL((k_conv_bwd_data<decltype(kind)::value, decltype(fast)::value, decltype(rbv)::value>), grid, dim3(256), 0, st,
-                           decltype(rbv)::value == 2 ? dz_pm : dz, x, xn, wd,
+                           decltype(rbv)::value >= 2 ? dz_pm : dz, x, xn, wd,
                            dx, dxn, dg, db, c.CH, c.tiles_c, c.n_ob, c.Opad32, c.chunks, cps, pl.bwd_data_slab_elems, dz_bytes, perm, dpar);
     };
     const bool launched = dispatch_fast<ON_TAP_MAJOR>(fast, [&](auto fv) {
         constexpr int F = decltype(fv)::value;
         if constexpr (fast_has(F, ON_ROWBLK_BWD_DATA)) {
+            if (pos8) return launch(IC<fast_kind(F)>{}, fv, IC<3>{});
             if (quad) return launch(IC<fast_kind(F)>{}, fv, IC<2>{});
             if (rb) return launch(IC<fast_kind(F)>{}, fv, IC<1>{});
         }

@@ -256,6 +256,12 @@ def _row_blocks8_forward(geom, plan) -> bool:
     return geom.H == 8 and geom.W == 8 and bool(getattr(plan, "tile_orders", 0) & L.ORDER_ROWBLK8_FWD)
 
 
+def _pos8_bwd_data(geom, plan) -> bool:
+    """bwd-data on 8x8 planes can run tiles of 32 images x 4 columns of a plane row fed from dz_pm (kan_plan.hip, plan_conv: `c.pos8_bd`): exactly the 484 of
+    576 (position, tap) blocks with a source are issued.  `plan.dz_pm_wanted` stays 0 for these layers; `_conv_backward` builds the copy where this holds."""
+    return bool(getattr(plan, "tile_orders", 0) & L.ORDER_POS8_BWD_DATA)
+
+
 def _executed_flops(geom, plan, which: str, have_dz_pm: bool = False) -> float:
     """Dense count minus the dead (position, tap) products a position-major launch skips (plan.*_target > 0 marks one)."""
     target = {"fwd": plan.fwd_target, "bwd_data": plan.bwd_data_target, "bwd_weight": plan.bwd_weight_target}[which]
@@ -270,6 +276,8 @@ def _executed_flops(geom, plan, which: str, have_dz_pm: bool = False) -> float:
             return dense * (5.0 / 6.0)
         if which == "fwd" and _row_blocks8_forward(geom, plan):
             return dense * (11.0 / 12.0)
+        if which == "bwd_data" and have_dz_pm and _pos8_bwd_data(geom, plan):
+            return dense * (484.0 / 576.0)
         return dense
     return dense * _live_fraction(which, g.H, g.W, g.Ho, g.Wo, g.kh, g.kw, g.sh, g.sw, g.ph, g.pw, g.dh, g.dw)
 
@@ -812,7 +820,8 @@ def _conv_backward(spec: ConvSpec, x, xn, packed, dz, need_x: bool, need_xn: boo
     split_x = need_x and wcd is not None
     exact_w = need_w and not split_w                     # ... and which exact ones are left: only they read dz_pm
     exact_x = (need_x or need_xn) and not split_x
-    dz_pm = _position_major(dz, 0, Ot) if (plan.dz_pm_wanted and xn is None and (exact_w or exact_x)) else None
+    # ... or exact bwd-data alone, on the 8x8 planes whose row-segment tiles are fed from it (the copy's time is inside the step)
+    dz_pm = _position_major(dz, 0, Ot) if (xn is None and ((plan.dz_pm_wanted and (exact_w or exact_x)) or (exact_x and _pos8_bwd_data(geom, plan)))) else None
     if split_w:                                          # opt-in split-precision weight gradient: no packed slabs, no unpack; same tensors, same sinks
         sb, ss = (_sink_for(wids[0], (Og, Cg, kh, kw), x.device), _sink_for(wids[1], (Og, Cg * spec.n_basis, kh, kw), x.device)) if wids else (None, None)
         dwb = sb if sb is not None else torch.empty((Og, Cg, kh, kw), device=x.device, dtype=torch.float32)

@@ -148,11 +148,16 @@ int kan_plan(const KanGeom* geom, const KanBasis* basis, KanPlan* plan);
  *   KAN_ORDER_FWD_WEIGHT_SIDE 2x2 planes, 3x3 / stride 1 / pad 1 / dilation 1, y_bstride % 4 == 0: the expanded forward (plan.fwd_expanded) runs tiles of
  *                          32 outputs x the 4 output positions x 128 images instead of 128 outputs x 1 position x 128 images and stores z[b][o][0..3] as one
  *                          16-byte group; the slabs are bit for bit those of the other order
+ *   KAN_ORDER_POS8_BWD_DATA 8x8 planes, 3x3 / stride 1 / pad 1 / dilation 1, B % 32 == 0, O % 16 == 0, x_bstride % 4 == 0: bwd-data runs tiles of 32 images x
+ *                          4 adjacent columns of one plane row and issues exactly the 484 of 576 (position, tap) blocks with a source, when it is given dz_pm
+ *                          (which KanPlan.dz_pm_wanted does not ask for on these planes: build it where this bit is set), one input tensor and 16-byte
+ *                          aligned x and dx; otherwise it runs the plane-major tiles
  * 0 for a geometry the planner rejects. */
 #define KAN_ORDER_QUAD_FWD 1
 #define KAN_ORDER_ROWBLK8_FWD 2
 #define KAN_ORDER_QUAD_BWD_DATA 4
 #define KAN_ORDER_FWD_WEIGHT_SIDE 8
+#define KAN_ORDER_POS8_BWD_DATA 16
 int kan_tile_orders(const KanGeom* geom, const KanBasis* basis);
 
 /* Pack the reference-layout weights of one group into the GEMM layouts of the kernels:
