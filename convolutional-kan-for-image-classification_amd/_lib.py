@@ -19,6 +19,7 @@ KAN_FP_WORDS = 192
 BASIS_BSPLINE, BASIS_RBF, BASIS_CHEBY, BASIS_POLY, BASIS_FOURIER, BASIS_RELU, BASIS_GRAM = 0, 1, 2, 3, 4, 5, 6
 ACT_NONE, ACT_IDENTITY, ACT_GELU, ACT_SILU, ACT_RELU, ACT_TANH, ACT_SIGMOID, ACT_GELU_TANH = -1, 0, 1, 2, 3, 4, 5, 6
 ORDER_QUAD_FWD, ORDER_ROWBLK8_FWD, ORDER_QUAD_BWD_DATA, ORDER_FWD_WEIGHT_SIDE, ORDER_POS8_BWD_DATA = 1, 2, 4, 8, 16        # kan_tile_orders bits (KAN_ORDER_*)
+ORDER_POS8_BWD_WEIGHT = 32
 
 
 class KanGeom(C.Structure):
@@ -72,6 +73,9 @@ SIGNATURES = {
     "kan_last_error": (C.c_char_p, []),
     "kan_plan": (_I, [_GP, _BP, C.POINTER(KanPlan)]),
     "kan_tile_orders": (_I, [_GP, _BP]),
+    "kan_bwd_weight_rowgroup_slabs": (_I, [_GP, _BP]),
+    "kan_conv_bwd_weight_rowgroups": (_I, [_P, _P, _P, _GP, _BP, _P]),
+    "kan_unpack_wgrad_rowgroups": (_I, [_P, _P, _P, _GP, _BP, _P]),
     "kan_pack_weights": (_I, [_P, _P, _P, _P, _GP, _BP, _P]),
     "kan_pack_weights_iod": (_I, [_P, _P, _P, _GP, _BP, _P]),
     "kan_pack_cacheable": (_I, [_GP, _BP]),

@@ -180,6 +180,7 @@ struct ConvPlan {
     bool quad_fwd;                        // ... B a multiple of 32: the halo forward takes quadrant tiles instead (exact tap skipping)
     bool quad_bd;                         // ... and bwd-data takes quadrant tiles when the caller passes dz_pm (single-tensor specs)
     bool pos8_bd;                         // 8x8 planes, B a multiple of 32: bwd-data takes tiles of 32 images x 4 columns of a plane row when the caller passes dz_pm (484/576 issued)
+    bool pos8_bw;                         // 8x8 planes, even B: kan_conv_bwd_weight_rowgroups is offered -- image-pair bands, nine taps per wave, 484/576 issued; its tiles and slabs are p8
     bool rowblk8_fwd;                     // 8x8 planes, 256-output tiles, B a multiple of 4: the halo forward takes half-plane tiles in row order (1/12 skipped)
     bool fwd_wq;                          // 2x2 planes, 3x3 / s1 / p1 / d1: the expanded forward keeps the four output positions on the weight side of a tile
     bool pmdma_xcd, pm_lpt, pm_xcd;       // expanded launches: XCD order of the forward, longest-first and XCD order of the weight gradient
@@ -187,6 +188,7 @@ struct ConvPlan {
     BdCfg bd;                             // bwd-data tiles
     BwCfg bw;                             // tap-major / expanded weight-gradient tiles
     BwHaloCfg bwh;                        // halo weight-gradient bands (Route::HALO)
+    BwHaloCfg p8;                         // kan_conv_bwd_weight_rowgroups (pos8_bw): row groups, 128-output tiles, image-pair bands, its own slab count
     KanBandCfg band;                      // band kernels (fwd or bwd_weight Route::BAND)
 };
 int plan_conv(const KanGeom* g, const KanBasis* b, ConvPlan* cp);       // 0, or the checks' error (message set)

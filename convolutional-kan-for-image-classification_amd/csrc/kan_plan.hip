@@ -275,6 +275,40 @@ BwHaloCfg bw_halo_cfg(const KanGeom* g, const KanPlan& pl) {
     c.bands_per_split = ceil_div(c.n_bands, best);
     return c;
 }
+// Weight gradient on 8x8 planes with exact tap skipping (k_conv_bwd_weight_pos8): default B-spline specs, 3x3 / stride 1 / pad 1 / dilation 1,
+// even B (a band is an image pair), any C and O.  A workgroup is one row group (32 (c, p) pairs under all nine taps) x 128 outputs; 144
+// accumulators leave two workgroups per CU, so the round model fills 512 slots, not 1024.  A step here is one plane row of an image pair:
+// ~60 MFMAs per wave against the 32 of a halo step, counted as two.  Every split takes at least two bands where there are two.
+// Kept out: launches of more than 8 bands that fill under one workgroup per CU at their split count -- the plan's own route cuts those
+// finer (16 -> 128 at B = 32: 352 workgroups on the halo kernel's one-image bands, 40 here).
+bool pos8_bw_cfg(const KanGeom* g, int f, bool dw, BwHaloCfg* out) {
+    if (tuning_off("KAN_POS8_BW") || !fast_has(f, ON_HALO_BWD_WEIGHT) || fast_kind(f) != KAN_BASIS_BSPLINE || dw) return false;
+    if (g->H != 8 || g->W != 8 || g->Ho != 8 || g->Wo != 8 || g->kh != 3 || g->kw != 3 || g->sh != 1 || g->sw != 1 || g->ph != 1 || g->pw != 1 ||
+        g->dh != 1 || g->dw != 1) return false;
+    if (g->B % 2 != 0 || g->C > 65535 / 81) return false;
+    if ((long long)g->B * g->x_bstride * 4 >= (1ll << 31) || (long long)g->B * g->y_bstride * 4 >= (1ll << 31)) return false;
+    BwHaloCfg c;
+    const int P = fast_planes(f), Opad = round_up(g->O, 64);
+    c.R = 8; c.nimg = 2; c.spb = 8;
+    c.n_bands = g->B / 2;
+    c.tiles_r = ceil_div(g->C * P, 32);
+    c.tiles_o = ceil_div(Opad, 128);
+    const long long tiles = (long long)c.tiles_r * c.tiles_o * ngroups(g);
+    const double slab_bytes = 4.0 * g->C * 9 * P * Opad * ngroups(g);
+    int best = 1; double best_cost = -1;
+    for (int sp = 1; sp <= c.n_bands && sp <= 1024; ++sp) {
+        const int bps = ceil_div(c.n_bands, sp);
+        if (ceil_div(c.n_bands, bps) != sp || (bps < 2 && c.n_bands >= 2)) continue;
+        const long long rounds = (tiles * sp + 511) / 512;
+        const double cost = (double)(rounds * (bps * c.spb * 2 + 6)) + sp * slab_cost_steps(slab_bytes);
+        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = sp; }
+    }
+    c.splits = best;
+    c.bands_per_split = ceil_div(c.n_bands, best);
+    if (c.n_bands > 8 && tiles * c.splits < 256) return false;
+    *out = c;
+    return true;
+}
 BwCfg bw_cfg(const KanGeom* g, const KanPlan& pl, bool big, bool pm_bw) {
     BwCfg c;
     c.TO = (big && !pm_bw) ? 256 : (pl.Opad % 128 == 0) ? 128 : 64;
@@ -378,6 +412,9 @@ int plan_conv(const KanGeom* g, const KanBasis* b, ConvPlan* cp) {
     const bool halo_bw = halo_bwd_weight(g, f, pmdma_bw);
     c.pm_bwd_weight = want_pm_bw && !halo_bw;
     const bool band_bw = band && c.band.bw_ok && !want_pm_bw && !tuning_off("KAN_BAND_BW");
+    // the weight gradient's own entry on 8x8 planes (kan_conv_bwd_weight_rowgroups): offered beside the plan's route, with its own slab count, so that
+    // nothing in KanPlan moves (kan_tile_orders reports it)
+    c.pos8_bw = pos8_bw_cfg(g, f, dw, &c.p8);
     c.rowblk_bwd_data = rowblk_bwd_data(g, f, c.pm_bwd_data);
     c.pmdma_xcd = tuning_on("KAN_PMDMA_XCD");
     c.pm_lpt = !tuning_off("KAN_PM_LPT");

@@ -1849,6 +1849,193 @@ __global__ __launch_bounds__(256, 4) void k_conv_bwd_weight_halo(
         }
 }
 
+// ============================================================================ backward weight on 8x8 planes: nine taps per wave, dead taps skipped
+// The halo kernel above issues all 576 (position, tap) products of a plane although only 484 have a source inside it: its 32-row MFMA
+// blocks mix three or four taps and its k-pairs are two neighbouring pixels, so no (block, k-pair) is ever wholly dead.  Here
+//   * a wave owns one ROW GROUP -- 32 consecutive (c, p) pairs, index c*9 + p -- under ALL nine taps: nine 32x32 blocks (144 accumulators)
+//     against 32 outputs; the four waves of a workgroup share the group and split 128 outputs.  The nine A operands of a lane are one
+//     halo address plus the tap shifts r*(W+2) + t, immediates.  Row (c, tap, p) of a block lands in slab row (c*9 + tap)*9 + p as before;
+//   * a band is two whole images and a k-pair is the SAME position of both, so every MFMA has one plane position and its taps are live
+//     or dead at compile time (4 in the corners, 6 on the edges, 9 inside): the dead ones and their ds_read are not emitted, the same
+//     for every wave.  A step is one plane row (8 positions x 2 images = 16 dz words per output); the rows come in three bodies;
+//   * the halo tile sH[5 channels x 9 planes][2 images x 100 cells] is single-buffered (36 KB; two would not leave room for two
+//     workgroups per CU): the next band's inputs wait in registers and are expanded behind one extra barrier per band (64 MFMA k-pairs);
+//   * dz arrives as in the halo kernel (4-byte LDS-DMA, [o][16 words], word = px ^ ((o >> 1) & 15)) with px = 2*column + image.
+// tools/probe/pos8_bw_emul.py restates this index arithmetic in numpy (coverage, live taps, bank sets).
+#define P8_READ(dst, addr, off) asm volatile("ds_read_b32 %0, %1 offset:%2" : "=&v"(dst) : "v"(addr), "n"(off) : "memory")
+#define P8_WAIT(reg, N) asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(reg) : "n"(N) : "memory")
+#define P8_TIE(reg) asm volatile("" : "+v"(reg))
+constexpr int P8_W = 8, P8_HWC = P8_W + 2, P8_HIMG = P8_HWC * P8_HWC, P8_CELLS = 2 * P8_HIMG;
+constexpr int P8_PS = P8_CELLS + 1;                      // plane stride: odd, so the 32 consecutive planes of a lane half hit 32 banks (the halves never conflict)
+constexpr int P8_NCH = 5, P8_ZB = 16 * 128;              // channels a row group can touch; floats per dz buffer
+__host__ __device__ constexpr bool pos8_col_live(int w, int t) { return w + t - 1 >= 0 && w + t - 1 < P8_W; }
+__host__ __device__ constexpr int pos8_col_reads(int w, int rows) { return 1 + rows * ((w == 0 || w == P8_W - 1) ? 2 : 3); }
+
+// One plane row: RK = 0 top (tap row 0 dead), 1 middle, 2 bottom (tap row 2 dead); ZPAR = dz buffer.  a_row = the lane's halo address of
+// (plane row h, column 0) under tap (0, 0).  The operands of column w + 1 are read while the MFMAs of column w issue.
+template <int RK, int ZPAR>
+__device__ __forceinline__ void pos8_row(f32x16 (&acc)[9], unsigned a_row, const unsigned (&bB)[8]) {
+    constexpr int R0 = RK == 0 ? 1 : 0, R1 = RK == 2 ? 1 : 2, NR = R1 - R0 + 1;
+    float fa[2][9], fb[2];
+#define P8_READS(w_, s_)                                                                                                          \
+    do {                                                                                                                         \
+        P8_READ(fb[s_], bB[w_], ZPAR * P8_ZB * 4);                                                                              \
+        _Pragma("unroll") for (int r = R0; r <= R1; ++r)                                                                         \
+            _Pragma("unroll") for (int t = 0; t < 3; ++t)                                                                        \
+                if (pos8_col_live(w_, t)) P8_READ(fa[s_][r * 3 + t], a_row, (r * P8_HWC + t + (w_)) * 4);                        \
+    } while (0)
+    P8_READS(0, 0);
+#pragma unroll
+    for (int w = 0; w < P8_W; ++w) {
+        const int c_ = w & 1, n_ = c_ ^ 1;
+        if (w + 1 < P8_W) {
+            P8_READS(w + 1, n_);
+            P8_WAIT(fb[c_], pos8_col_reads(w + 1 < P8_W ? w + 1 : 0, NR));
+        } else {
+            P8_WAIT(fb[c_], 0);
+        }
+#pragma unroll
+        for (int r = R0; r <= R1; ++r)
+#pragma unroll
+            for (int t = 0; t < 3; ++t)
+                if (pos8_col_live(w, t)) {
+                    P8_TIE(fa[c_][r * 3 + t]);
+                    acc[r * 3 + t] = MFMA32(fa[c_][r * 3 + t], fb[c_], acc[r * 3 + t]);
+                }
+    }
+#undef P8_READS
+}
+
+template <int FAST>
+__global__ __launch_bounds__(256, 2) void k_conv_bwd_weight_pos8(
+    const float* __restrict__ dz, const float* __restrict__ x, float* __restrict__ dwp, DevGeom g, DevBasis bs, int Krows, int Opad,
+    int n_bands, int bands_per_split, long long slab_elems, unsigned x_bytes, unsigned dz_bytes, int tiles_o) {
+    constexpr int KIND = fast_kind(FAST);
+    constexpr int P = fast_planes(FAST), T = 9, NT = 256;
+    constexpr int HB = P8_NCH * P * P8_PS;                   // floats of the halo tile
+    constexpr int NU = P8_NCH * 2 * P8_W * P8_W;             // expansions per band: 5 channels x 2 images x 64 pixels (the border cells stay zero)
+    constexpr int SLOTS = (NU + NT - 1) / NT;
+    static_assert(P == 9, "row groups of 32 (c, p) pairs: nine planes per channel");
+    __shared__ float sH[HB];
+    __shared__ __attribute__((aligned(16))) float sZ[2 * P8_ZB];
+    __shared__ float sTab[KAN_MAX_TABLE];
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int kh2 = lane >> 5;
+    const BlockId blk = xcd_block_order(true);
+    const int grp = blk.y / tiles_o;
+    const int q0 = blk.x * 32, o_tile0 = (blk.y - grp * tiles_o) * 128;      // first (c, p) pair of the row group, first output of the tile
+    x += (size_t)grp * g.C * 64;
+    dz += (size_t)grp * g.O * 64;
+    dwp += (size_t)grp * Krows * Opad;
+    const int c0 = q0 / P;
+
+    if (tid < KAN_MAX_TABLE) sTab[tid] = bs.tab[tid];
+    for (int i = tid; i < HB; i += NT) sH[i] = 0.f;          // borders (and the planes of channels past C) stay zero for good
+    float* const dump = sH + P8_CELLS;                        // the pad word of plane 0, which no read touches
+
+    // ---- expansion units of this thread (fixed): unit -> (channel of the tile, image of the band, pixel)
+    int u_src[SLOTS], u_dst[SLOTS], u_ch[SLOTS]; unsigned u_ok = 0;
+#pragma unroll
+    for (int k = 0; k < SLOTS; ++k) {
+        const int idx = tid + k * NT;
+        const int ch = idx >> 7, img = (idx >> 6) & 1, pos = idx & 63, h = pos >> 3, w = pos & 7;
+        u_src[k] = (c0 + ch) * 64 + img * (int)g.xbs + pos;                  // + the band's first image per band
+        u_dst[k] = ch * (P * P8_PS) + img * P8_HIMG + (h + 1) * P8_HWC + w + 1;
+        u_ch[k] = c0 + ch;
+        u_ok |= ((idx < NU && c0 + ch < g.C) ? 1u : 0u) << k;
+    }
+    const kan_rsrc x_rs = make_rsrc(x, x_bytes), dz_rs = make_rsrc(dz, dz_bytes);
+
+    // ---- A-operand address: this lane's (c, p) pair -> plane of the tile (+ image of its k-half); taps, rows and columns are immediates
+    const unsigned aA = lds_addr(sH + (q0 + (lane & 31) - c0 * P) * P8_PS + kh2 * P8_HIMG);
+    // ---- B-operand addresses: one per k-pair = column (XOR swizzle: not additive), the buffer is an immediate
+    unsigned bB[8];
+    {
+        const int ol = wave * 32 + (lane & 31), sw = (ol >> 1) & 15;
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk) bB[kk] = lds_addr(sZ + ol * 16 + ((2 * kk + kh2) ^ sw));
+    }
+    // ---- dz DMA: wave w copies chunks m = 8 w .. 8 w + 7 (64 words = 4 output rows x 16 words); lane -> (row, swizzled word = 2*column + image)
+    unsigned zoff[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+        const int ol = 4 * (wave * 8 + j) + (lane >> 4), q = (lane & 15) ^ ((ol >> 1) & 15);
+        zoff[j] = o_tile0 + ol < g.O ? (unsigned)((o_tile0 + ol) * 64 + (q >> 1) + (q & 1) * (int)g.ybs) * 4u : KAN_OOB;
+    }
+    auto issue_dz = [&](int band, int st, int zb) {           // plane row st of the band's two images
+        const int soff = __builtin_amdgcn_readfirstlane((2 * band * (int)g.ybs + st * P8_W) * 4);
+        float* dst = sZ + zb * P8_ZB + wave * (8 * 64);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(dz_rs, (__attribute__((address_space(3))) void*)(dst + j * 64), 4, (int)zoff[j], soff, 0, 0);
+    };
+    float xv[SLOTS];
+    auto load_band = [&](int band) {
+        const int sbase = 2 * band * (int)g.xbs;
+#pragma unroll
+        for (int k = 0; k < SLOTS; ++k) xv[k] = buf_load(x_rs, ((u_ok >> k) & 1u) ? (unsigned)(sbase + u_src[k]) * 4u : KAN_OOB);
+    };
+    auto expand_band = [&]() {
+#pragma unroll
+        for (int k = 0; k < SLOTS; ++k)
+            if ((u_ok >> k) & 1u) stage_unit<KIND, FAST>(bs, sTab, true, xv[k], xv[k], sH + u_dst[k], P8_PS, dump, u_ch[k]);
+    };
+
+    f32x16 acc[9];
+#pragma unroll
+    for (int a = 0; a < 9; ++a)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[a][r] = 0.f;
+
+    const int nb0 = blk.z * bands_per_split, nb1 = min(n_bands, nb0 + bands_per_split);
+    __syncthreads();                                          // sTab, zero fill
+    if (nb0 < nb1) {
+        load_band(nb0);
+        expand_band();
+        issue_dz(nb0, 0, 0);
+    }
+    for (int band = nb0; band < nb1; ++band) {
+        const bool more = band + 1 < nb1;
+        auto step = [&](int st) {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this step's dz landed (own DMAs), the next band's inputs arrived
+            __syncthreads();                                  // ... everybody's; halo of this band visible; previous step's reads done
+            if (st + 1 < P8_W) issue_dz(band, st + 1, (st + 1) & 1);
+            else if (more) issue_dz(band + 1, 0, 0);
+            if (st == 0 && more) load_band(band + 1);
+        };
+        step(0);
+        pos8_row<0, 0>(acc, aA, bB);
+#pragma unroll 1
+        for (int st = 1; st < P8_W - 1; st += 2) {
+            step(st);
+            pos8_row<1, 1>(acc, aA + (unsigned)(st * P8_HWC * 4), bB);
+            step(st + 1);
+            pos8_row<1, 0>(acc, aA + (unsigned)((st + 1) * P8_HWC * 4), bB);
+        }
+        step(P8_W - 1);
+        pos8_row<2, 1>(acc, aA + (unsigned)((P8_W - 1) * P8_HWC * 4), bB);
+        if (more) {
+            __syncthreads();                                  // every wave has read this band's halo
+            expand_band();
+        }
+    }
+
+    float* out = dwp + (size_t)blk.z * slab_elems;
+    const int o = o_tile0 + wave * 32 + (lane & 31);
+    if (o < Opad) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int q = q0 + mfma_row(r, lane);
+            if (q >= g.C * P) continue;
+            const int c = q / P, p = q - c * P;
+#pragma unroll
+            for (int tap = 0; tap < T; ++tap) out[(size_t)((c * T + tap) * P + p) * Opad + o] = acc[tap][r];
+        }
+    }
+}
+
 // ============================================================================ position-major, expanded: small planes
 // On 4x4 / 2x2 planes a launch sees only B*16 / B*4 pixels against up to 85 MB of weights; the position-major launches of
 // the tap-major kernels (which skip the taps that read padding) ran at 0.49 - 0.55 matrix-pipe busy with 2.6 - 3.2 vector
@@ -3282,7 +3469,8 @@ int kan_tile_orders(const KanGeom* g, const KanBasis* b) {
     if (plan_conv(g, b, &cp)) return 0;
     const bool halo = cp.fwd == Route::HALO;
     return (halo && cp.quad_fwd ? KAN_ORDER_QUAD_FWD : 0) | (halo && cp.rowblk8_fwd ? KAN_ORDER_ROWBLK8_FWD : 0) | (cp.quad_bd ? KAN_ORDER_QUAD_BWD_DATA : 0) |
-           (cp.fwd_wq ? KAN_ORDER_FWD_WEIGHT_SIDE : 0) | (cp.pos8_bd ? KAN_ORDER_POS8_BWD_DATA : 0);
+           (cp.fwd_wq ? KAN_ORDER_FWD_WEIGHT_SIDE : 0) | (cp.pos8_bd ? KAN_ORDER_POS8_BWD_DATA : 0) |
+           (cp.pos8_bw ? KAN_ORDER_POS8_BWD_WEIGHT : 0);
 }
 
 int kan_pack_cacheable(const KanGeom* g, const KanBasis* b) {
@@ -3311,9 +3499,17 @@ int kan_pack_weights_cached(const float* w_base, const float* w_basis, float* wp
 }
 
 // `iod`: dw_basis is the [C][O][n_basis] gradient of an MLP KAN head's coefficients (kan_unpack_wgrad_iod).
-static int unpack_wgrad_impl(const float* dwp, float* dw_base, float* dw_basis, const KanGeom* g, const KanBasis* b, void* stream, bool iod) {
+// `pos8`: dwp holds the slabs of kan_conv_bwd_weight_rowgroups (channel-major rows, its own slab count) instead of the plan's route's.
+static int unpack_wgrad_impl(const float* dwp, float* dw_base, float* dw_basis, const KanGeom* g, const KanBasis* b, void* stream, bool iod, bool pos8 = false) {
     ConvPlan cp;
     if (int rc = plan_conv(g, b, &cp)) return rc;
+    if (pos8) {
+        if (!cp.pos8_bw) return fail("this geometry / basis does not offer the 8x8 tap-skipping weight gradient (kan_tile_orders)");
+        cp.bwd_weight = Route::HALO;                          // the layout of its slabs: channel-major flat rows, K of them
+        cp.pub.bwd_weight_band = 0;
+        cp.pub.bwd_weight_splits = cp.p8.splits;
+        cp.pub.bwd_weight_slab_elems = (long long)ngroups(g) * cp.pub.K * cp.pub.Opad;
+    }
     const KanPlan& pl = cp.pub;
     const int hb = b->act != KAN_ACT_NONE;
     if ((hb && !dw_base) || !dw_basis || !dwp) return fail("null weight-gradient pointer");
@@ -3341,6 +3537,10 @@ static int unpack_wgrad_impl(const float* dwp, float* dw_base, float* dw_basis, 
 
 int kan_unpack_wgrad(const float* dwp, float* dw_base, float* dw_basis, const KanGeom* g, const KanBasis* b, void* stream) {
     return unpack_wgrad_impl(dwp, dw_base, dw_basis, g, b, stream, false);
+}
+
+int kan_unpack_wgrad_rowgroups(const float* dwp, float* dw_base, float* dw_basis, const KanGeom* g, const KanBasis* b, void* stream) {
+    return unpack_wgrad_impl(dwp, dw_base, dw_basis, g, b, stream, false, true);
 }
 
 int kan_unpack_wgrad_iod(const float* dwp, float* dcoeffs, const KanGeom* g, const KanBasis* b, void* stream) {
@@ -3589,6 +3789,33 @@ int kan_conv_bwd_weight(const float* dz, const float* x, const float* xn, float*
     });
     if (!fast) dispatch_kind(b->kind, [&](auto kind) { tiles(kind, IC<FAST_GENERIC>{}); });
     return launch_ok("conv_bwd_weight");
+}
+
+int kan_bwd_weight_rowgroup_slabs(const KanGeom* g, const KanBasis* b) {
+    ConvPlan cp;
+    if (plan_conv(g, b, &cp)) return 0;
+    return cp.pos8_bw ? cp.p8.splits : 0;
+}
+
+int kan_conv_bwd_weight_rowgroups(const float* dz, const float* x, float* dwp, const KanGeom* g, const KanBasis* b, void* stream) {
+    ConvPlan cp;
+    if (int rc = plan_conv(g, b, &cp)) return rc;
+    const KanPlan& pl = cp.pub;
+    if (!dz || !x || !dwp) return fail("null tensor pointer");
+    if (!cp.pos8_bw) return fail("this geometry / basis does not offer the 8x8 tap-skipping weight gradient (kan_tile_orders)");
+    const BwHaloCfg& hc = cp.p8;
+    const DevGeom dgh = dev_geom(g); const DevBasis dbh = dev_basis(b);
+    if ((long long)hc.tiles_o * ngroups(g) > 65535) return fail("groups * output tiles exceed the grid limit");
+    const unsigned x_bytes = (unsigned)((long long)g->B * g->x_bstride * 4), dz_bytes = (unsigned)((long long)g->B * g->y_bstride * 4);
+    const long long slab_elems = (long long)ngroups(g) * pl.K * pl.Opad;
+    dim3 grid(hc.tiles_r, hc.tiles_o * ngroups(g), hc.splits);
+    dispatch_fast<ON_HALO_BWD_WEIGHT>(cp.fast, [&](auto fv) {
+        constexpr int F = decltype(fv)::value;
+        if constexpr (fast_kind(F) == KAN_BASIS_BSPLINE)
+            hipLaunchKernelGGL((k_conv_bwd_weight_pos8<F>), grid, dim3(256), 0, (hipStream_t)stream, dz, x, dwp, dgh, dbh, pl.K, pl.Opad, hc.n_bands,
+                               hc.bands_per_split, slab_elems, x_bytes, dz_bytes, hc.tiles_o);
+    });
+    return launch_ok("conv_bwd_weight_pos8");
 }
 
 int kan_position_major_expanded(const float* x, float* e_pm, const KanGeom* g, const KanBasis* b, void* stream) {

@@ -111,6 +111,7 @@ def _plan_cached(spec: ConvSpec, B: int, Cg: int, H: int, W: int, Og: int, C_tot
         bp = L.KanBasis.from_buffer_copy(b)
         bp.chan_table = 1
     L.check(L.load().kan_plan(C.byref(g), C.byref(bp), C.byref(p)), "kan_plan")
+    p.pos8_bw_slabs = L.load().kan_bwd_weight_rowgroup_slabs(C.byref(g), C.byref(bp))      # slabs of kan_conv_bwd_weight_rowgroups (0: not offered)
     p.tile_orders = L.load().kan_tile_orders(C.byref(g), C.byref(bp))      # the launchers' pixel order inside a tile: not a KanPlan field (kanconv.h)
     return g, b, p
 
@@ -260,6 +261,12 @@ def _pos8_bwd_data(geom, plan) -> bool:
     """bwd-data on 8x8 planes can run tiles of 32 images x 4 columns of a plane row fed from dz_pm (kan_plan.hip, plan_conv: `c.pos8_bd`): exactly the 484 of
     576 (position, tap) blocks with a source are issued.  `plan.dz_pm_wanted` stays 0 for these layers; `_conv_backward` builds the copy where this holds."""
     return bool(getattr(plan, "tile_orders", 0) & L.ORDER_POS8_BWD_DATA)
+
+
+def _pos8_bwd_weight(geom, plan) -> bool:
+    """The weight gradient on 8x8 planes has an entry of its own that issues exactly the 484 of 576 (position, tap) blocks with a source
+    (kan_conv_bwd_weight_rowgroups; kan_plan.hip: `c.pos8_bw`), with its own slab count: `plan` stays the other route's."""
+    return bool(getattr(plan, "tile_orders", 0) & L.ORDER_POS8_BWD_WEIGHT)
 
 
 def _executed_flops(geom, plan, which: str, have_dz_pm: bool = False) -> float:
@@ -829,8 +836,14 @@ def _conv_backward(spec: ConvSpec, x, xn, packed, dz, need_x: bool, need_xn: boo
         kan_conv_bwd_weight_split(spec, x, dz, out=(dwb, dws))
         dw_base, dw_basis = list(dwb.unsqueeze(0).unbind(0)), list(dws.unsqueeze(0).unbind(0))       # views, as the exact path returns them
     elif exact_w:
-        dwp = torch.empty(plan.bwd_weight_splits * plan.bwd_weight_slab_elems, device=x.device, dtype=torch.float32)
-        if plan.bwd_weight_expanded and xn is None and dz_pm is not None:
+        pos8 = xn is None and spec.w_layout != W_IOD and _pos8_bwd_weight(geom, plan)
+        slabs = plan.pos8_bw_slabs * G * plan.K * plan.Opad if pos8 else plan.bwd_weight_splits * plan.bwd_weight_slab_elems
+        dwp = torch.empty(slabs, device=x.device, dtype=torch.float32)
+        if pos8:
+            name, dense, _, tag = _sample("bwd_weight", geom, plan, False)
+            _launch(("k_conv_bwd_weight_pos8/" + name.split("/")[1], dense, dense * (484.0 / 576.0), tag), x,
+                    lambda: lib.kan_conv_bwd_weight_rowgroups(_ptr(dz), _ptr(x), _ptr(dwp), C.byref(geom), C.byref(basis), st))
+        elif plan.bwd_weight_expanded and xn is None and dz_pm is not None:
             # small padded planes: expanded position-major operand, DMA + MFMA weight gradient (kanconv.h)
             e_pm = x_pm if (plan.fwd_expanded and not plan.x_pm_wanted and x_pm is not None and mode == 0) else _expand_pm(x, geom, basis, plan, st)   # the forward's copy, if it kept one (value planes only)
             _launch(_sample("bwd_weight", geom, plan, True, expanded=True), x,
@@ -849,7 +862,8 @@ def _conv_backward(spec: ConvSpec, x, xn, packed, dz, need_x: bool, need_xn: boo
             dwb = (sb.unsqueeze(0) if sb is not None else
                    torch.empty((G, Og, Cg, kh, kw), device=x.device, dtype=torch.float32)) if spec.has_base else None
             dws = ss.unsqueeze(0) if ss is not None else torch.empty((G, Og, Cg * spec.n_basis, kh, kw), device=x.device, dtype=torch.float32)
-            L.check(lib.kan_unpack_wgrad(_ptr(dwp), _ptr(dwb), _ptr(dws), C.byref(geom), C.byref(basis), st), "kan_unpack_wgrad")
+            unpack = lib.kan_unpack_wgrad_rowgroups if pos8 else lib.kan_unpack_wgrad
+            L.check(unpack(_ptr(dwp), _ptr(dwb), _ptr(dws), C.byref(geom), C.byref(basis), st), "kan_unpack_wgrad")
             dw_basis = list(dws.unbind(0))
             if spec.has_base:
                 dw_base = list(dwb.unbind(0))

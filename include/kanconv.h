@@ -152,12 +152,16 @@ int kan_plan(const KanGeom* geom, const KanBasis* basis, KanPlan* plan);
  *                          4 adjacent columns of one plane row and issues exactly the 484 of 576 (position, tap) blocks with a source, when it is given dz_pm
  *                          (which KanPlan.dz_pm_wanted does not ask for on these planes: build it where this bit is set), one input tensor and 16-byte
  *                          aligned x and dx; otherwise it runs the plane-major tiles
+ *   KAN_ORDER_POS8_BWD_WEIGHT 8x8 planes, 3x3 / stride 1 / pad 1 / dilation 1, default B-spline specs, even B: the weight gradient has an entry of its own,
+ *                          kan_conv_bwd_weight_rowgroups (below), which issues exactly the 484 of 576 (position, tap) blocks with a source; kan_conv_bwd_weight
+ *                          keeps running the plan's route and nothing in KanPlan moves
  * 0 for a geometry the planner rejects. */
 #define KAN_ORDER_QUAD_FWD 1
 #define KAN_ORDER_ROWBLK8_FWD 2
 #define KAN_ORDER_QUAD_BWD_DATA 4
 #define KAN_ORDER_FWD_WEIGHT_SIDE 8
 #define KAN_ORDER_POS8_BWD_DATA 16
+#define KAN_ORDER_POS8_BWD_WEIGHT 32
 int kan_tile_orders(const KanGeom* geom, const KanBasis* basis);
 
 /* Pack the reference-layout weights of one group into the GEMM layouts of the kernels:
@@ -258,6 +262,16 @@ int kan_conv_fwd_expanded(const float* e_pm, const float* wp, float* z, const Ka
 int kan_conv_fwd_expanded_order(const float* e_pm, const float* wp, float* z, const KanGeom* geom, const KanBasis* basis, void* stream, int order);
 int kan_conv_bwd_weight_expanded(const float* dz_pm, const float* e_pm, float* dwp,
                                  const KanGeom* geom, const KanBasis* basis, void* stream);
+
+/* The weight gradient on 8x8 planes with exact tap skipping, where kan_tile_orders reports KAN_ORDER_POS8_BWD_WEIGHT (an error elsewhere): computes what
+ * kan_conv_bwd_weight computes from the image-major x and dz (one input tensor), in another order of summation -- row groups of 32 (channel, plane) pairs
+ * under all nine taps, bands of two images, a k-pair = one plane position of both images.  dwp receives kan_bwd_weight_rowgroup_slabs() partial slabs of
+ * groups * plan.K * plan.Opad floats each (rows (c * taps + tap) * P + p: not the plan's slab count, and not its layout where the plan's route is the
+ * band kernel); kan_unpack_wgrad_rowgroups sums and scatters them as kan_unpack_wgrad does for the plan's route.  kan_bwd_weight_rowgroup_slabs is 0 where the
+ * entry is not offered. */
+int kan_bwd_weight_rowgroup_slabs(const KanGeom* geom, const KanBasis* basis);
+int kan_conv_bwd_weight_rowgroups(const float* dz, const float* x, float* dwp, const KanGeom* geom, const KanBasis* basis, void* stream);
+int kan_unpack_wgrad_rowgroups(const float* dwp, float* dw_base, float* dw_basis, const KanGeom* geom, const KanBasis* basis, void* stream);
 
 /* Sum the dwp slabs and scatter back to the reference layouts (inverse of kan_pack_weights; stacked [G,...] when
  * geom->groups = G).  dw_base may be NULL iff there is no base branch.  dwp is scratch: with >= 32 slabs the sum is
