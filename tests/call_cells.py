@@ -5,7 +5,7 @@ asking for a gradient, a contiguous incoming gradient, one backward.  This matri
 under a condition and compares it with THE SAME subject under the canonical call -- the call the existing matrices already judge against
 fp64 -- so the op, the shapes and the launch plan are the same on both sides and the expected result is bit equality (`torch.equal`).
 
-Subjects: one per code path of ops.py, each of them a row of an existing table (route_cells.ROUTE_CASES looked up by key and index, the
+Subjects: one per code path of ops.py, each of them a row of an existing table (route_cells.ROUTE_CASES and order_cells.ORDER_CASES looked up by key and index, the
 fixtures of tests/golden/heads, tests/golden/mlp_tiny, a wav_cells row, the two smallest draws of test_gpu_fuzz's 1-D and 3-D tests), so
 the canonical call is oracle-checked by an existing test; tests/test_call_matrix.py holds the table to that on the CPU.
 
@@ -74,12 +74,29 @@ SUBJECTS = [
     _s("xent-5x10-metrics", "loss", "_CrossEntropy with ClassMetrics", shape=(5, 10), metrics=True, stateful=True),
     _s("xent-257x100", "loss", "_CrossEntropy, more than one block", shape=(257, 100), metrics=False),
     _s("xent-257x100-metrics", "loss", "_CrossEntropy with ClassMetrics, more than one block", shape=(257, 100), metrics=True, stateful=True),
+    # 13: the 8x8 tile orders KanPlan does not show, rows of order_cells.ORDER_CASES (key: spec class, orders, groups, the three routes): the smallest row
+    # whose forward runs half-plane row blocks and whose weight gradient takes its own 8x8 entry (B 4, C 2, O 256), and the smallest row whose bwd-data runs
+    # the 32-image row-segment tiles from a dz_pm that `_conv_backward` builds for them alone (B 32, C 1, O 16), the latter under the BatchNorm tail
+    _s("kan8-rowblk-pos8bw", "order", "k_conv_fwd_halo row blocks; kan_conv_bwd_weight_rowgroups + kan_unpack_wgrad_rowgroups",
+       key="FAST_BSPLINE_SILU POS8_BWD_WEIGHT+ROWBLK8_FWD G1 HALO TAP HALO", index=0, shape=(4, 2, 256, 8, 1)),
+    _s("kan8-pos8bd-bn", "order", "dz_pm built for bwd-data alone (_pos8_bwd_data); BatchNorm tail, batch statistics",
+       key="FAST_BSPLINE_SILU POS8_BWD_DATA G1 BAND TAP BAND", index=0, shape=(32, 1, 16, 8, 1), bn=True, training=True, stateful=True),
 ]
 SUBJECT = {s["id"]: s for s in SUBJECTS}
 
 
+def order_row_key(subject):
+    """The order_cells key an `order` subject names: "spec orders G<n> fwd bwd-data bwd-weight"."""
+    spec, orders, grouped, *routes = subject["key"].split()
+    return (spec, tuple(sorted(orders.split("+"))), grouped != "G1") + tuple(routes)
+
+
 def route_row(subject):
-    """The ROUTE_CASES row of a `route` subject: the `index`-th row whose key is `key`."""
+    """The ROUTE_CASES row of a `route` subject, the ORDER_CASES row of an `order` subject: the `index`-th row whose key is `key`."""
+    if subject["kind"] == "order":
+        from order_cells import ORDER_CASES
+        rows = [c for c in ORDER_CASES if c["key"] == order_row_key(subject)]
+        return rows[subject["index"]]
     from route_cells import ROUTE_CASES
     rows = [c for c in ROUTE_CASES if c["key"] == tuple(subject["key"].split())]
     return rows[subject["index"]]
@@ -189,7 +206,7 @@ def build(subject):
     kind = subject["kind"]
     torch.manual_seed(0)
     gen = torch.Generator().manual_seed(1)
-    if kind == "route":
+    if kind in ("route", "order"):
         from route_cells import LAYERS, SHAPES, case_layer
         case = dict(route_row(subject))
         if subject.get("affine"):
@@ -830,6 +847,7 @@ EXCLUSIONS = (
     [(v, s, "the incoming gradient of the loss is a scalar: it has no layout") for v in ("go-permuted", "go-cols2", "go-bstride0") for s in _LOSS]
     + [("checkpoint", "kan-bn-train", "the forward runs twice, so the running statistics update twice, as torch's would"),
        ("checkpoint", "batch-norm", "the forward runs twice, so the running statistics update twice, as torch's would"),
+       ("checkpoint", "kan8-pos8bd-bn", "the forward runs twice, so the running statistics update twice, as torch's would"),
        ("checkpoint", "xent-5x10-metrics", "the forward runs twice, so the counters add the batch twice"),
        ("checkpoint", "xent-257x100-metrics", "the forward runs twice, so the counters add the batch twice")]
     + [(v, s, "the loss has no parameters to step") for v in ("stale-w", "stale-refwd", "refuse-cpu-weights") for s in _LOSS]
@@ -854,11 +872,11 @@ STALE = {
     # phased stage saves its basis weights (views of the Parameters), the wavelet stage its weights, the norm op gamma
     "stale-w": {"*": "consistent", "relu-phases": "raises", "gram-coeffs": "raises", "wav": "raises", "instance-norm": "raises", "batch-norm": "raises"},
     # the cached layouts are re-packed in place by the second forward, with a version bump (`_pack`): the first graph raises.  Every
-    # fresh() pack leaves the first graph its own layouts (the grouped layers, the W_IOD heads, the MLP layer with its host-applied
+    # fresh() pack leaves the first graph its own layouts (the grouped layers, the one-channel band layer kan8-pos8bd-bn, the W_IOD heads, the MLP layer with its host-applied
     # activation and second input); the subjects that raise under stale-w raise here for the same reason.  The 3-D subject has one depth
     # tap: its weight slice is a contiguous view of the Parameter, so it takes the cached path
     "stale-refwd": {"*": "consistent", "kan-silu": "raises", "kan-silu-affine": "raises", "kan-bn-train": "raises", "kan-bn-eval": "raises",
-                    "kan-3d": "raises", "relu-phases": "raises", "gram-coeffs": "raises", "wav": "raises", "instance-norm": "raises",
+                    "kan8-rowblk-pos8bw": "raises", "kan-3d": "raises", "relu-phases": "raises", "gram-coeffs": "raises", "wav": "raises", "instance-norm": "raises",
                     "batch-norm": "raises"},
 }
 

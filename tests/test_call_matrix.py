@@ -61,6 +61,34 @@ def test_route_subject_is_its_row_and_plans_to_its_path(sid):
         raise AssertionError(sid)
 
 
+@pytest.mark.parametrize("sid", [s["id"] for s in SUBJECTS if s["kind"] == "order"])
+def test_order_subject_is_its_row_and_plans_to_its_path(sid):
+    """The two subjects on the 8x8 tile orders: each is the row of order_cells.ORDER_CASES it names, the smallest row that has its orders, and its layer
+    still plans to them -- so that its canonical call is the one tests/test_gpu_order_matrix.py judges against fp64."""
+    from convkan_amd import ops
+    from order_cells import ORDER_CASES, order_key, work
+    from route_cells import case_structs
+    s = SUBJECT[sid]
+    case = CC.route_row(s)
+    assert any(case is c for c in ORDER_CASES) and case["key"] == CC.order_row_key(s)
+    assert (case["B"], case["C"], case["O"], case["H"], case["G"]) == s["shape"] and case["W"] == case["H"] == 8
+    want = {"kan8-rowblk-pos8bw": lambda o: set(o) == {"ROWBLK8_FWD", "POS8_BWD_WEIGHT"}, "kan8-pos8bd-bn": lambda o: "POS8_BWD_DATA" in o}[sid]
+    assert want(case["key"][1]) and work(case) == min(work(c) for c in ORDER_CASES if want(c["key"][1]))
+    layer, x = CC.build(s)
+    assert tuple(x.shape) == (case["B"], case["C"], 8, 8)
+    g, b, p = case_structs(case, layer)
+    assert order_key(g, b, p) == case["key"]
+    spec = layer.conv_spec()
+    # the halo layouts are kept between calls; the band layouts of the one-channel layer have pad rows to clear and are packed afresh on every call
+    assert spec.groups == 1 and spec.has_base and ops._cacheable(ops._plan_key(spec, x.shape, case["O"])) == (sid == "kan8-rowblk-pos8bw")
+    assert CC.STALE["stale-refwd"].get(sid, "consistent") == ("raises" if sid == "kan8-rowblk-pos8bw" else "consistent")
+    assert type(layer.layer_norm[0]) is (nn.BatchNorm2d if s.get("bn") else nn.InstanceNorm2d) and layer.training == bool(s.get("training", True))
+    if sid == "kan8-rowblk-pos8bw":                              # the weight gradient bypasses the plan's halo route; no dz_pm is ever built
+        assert ops._row_blocks8_forward(g, p) and ops._pos8_bwd_weight(g, p) and not ops._pos8_bwd_data(g, p) and not p.dz_pm_wanted and p.pos8_bw_slabs == 1
+    else:                                                        # dz_pm is built for bwd-data alone: not when x asks for no gradient
+        assert ops._pos8_bwd_data(g, p) and not ops._pos8_bwd_weight(g, p) and not p.dz_pm_wanted
+
+
 def test_fuzz_subjects_are_the_smallest_draws():
     for sid, draw, seeds in (("kan-1d", CC.fuzz_1d, range(0, 24, 4)), ("kan-3d", CC.fuzz_3d, range(0, 18, 7))):
         sizes = {seed: CC.fuzz_size(draw(seed)) for seed in seeds}

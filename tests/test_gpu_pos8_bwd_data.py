@@ -7,7 +7,8 @@ channel tiles, the second ragged; three output blocks), 16 -> 32 at B = 64 insid
 cuts the depth into six slabs (the 16-output shapes have one slab, 20 -> 48 three, 16 -> 32 two). Checked: the layer against the fp64 oracle (helpers.check_vs_oracle, TOL_DX); the launch with dz_pm against the same
 launch without it (the plane-major tiles): torch.equal where the plan has one slab -- only exact zeros are dropped, the order of the sum stays -- and the
 TOL_DX rule on the summed slabs where it has several (the slabs are cut over the live steps); guard words either side of the slabs and in the channels
-the launch does not own; and a geometry out of scope, which must give the plane-major bits with dz_pm passed."""
+the launch does not own; the one-slab bit equality for GELU as well (the kernel's second instantiation); a two-group launch (14 channels and 16 outputs per
+group) against its groups launched alone, each on its own weights, dz_pm and channels of the same tensors, bit for bit; and a geometry out of scope, which must give the plane-major bits with dz_pm passed."""
 import ctypes as C
 
 import pytest
@@ -30,30 +31,38 @@ def _plan(layer, B, Cn, On, Ct, Ot, H=8):
     return ops._plan_cached(layer.conv_spec(), B, Cn, H, H, On, Ct, Ot)
 
 
-def _run(layer, geom, basis, plan, x, dz, with_pm):
-    """One kan_conv_bwd_data launch into guarded slabs: returns the [S, B, Ct, H, W] slabs (channels the launch does not own keep the sentinel)."""
+def _run(layer, geom, basis, plan, x, dz, with_pm, grp=None):
+    """One kan_conv_bwd_data launch into guarded slabs: returns the owned channels of the [S, B, Ct, H, W] slabs (channels the launch does not own keep
+    the sentinel).  A grouped geometry owns the channels of all its groups.  `grp`: a single-group geometry launched as group `grp` of the grouped `layer`
+    -- that group's weights packed alone, x, dz and dx at the group's channels of the wider tensors, dz_pm the position-major copy of its outputs."""
     from convkan_amd import _lib as L
     from convkan_amd import ops
     lib = L.load()
     st = ops._stream(x)
     basis = ops._with_table(basis, layer.conv_spec(), x.device)
-    wb = torch.stack([m.weight.detach() for m in layer.base_conv]).contiguous()
-    ws = torch.stack([m.weight.detach() for m in layer.spline_conv]).contiguous()
+    G = max(1, geom.groups)
+    assert G == 1 or grp is None
+    mods = slice(None) if grp is None else slice(grp, grp + 1)
+    wb = torch.stack([m.weight.detach() for m in layer.base_conv[mods]]).contiguous()
+    ws = torch.stack([m.weight.detach() for m in layer.spline_conv[mods]]).contiguous()
+    assert tuple(wb.shape) == (G, geom.O, geom.C, 3, 3)
     wp = torch.empty(plan.packed_weight_bytes // 4, device=x.device)
     wd = torch.empty(plan.bwd_data_weight_bytes // 4, device=x.device)
     L.check(lib.kan_pack_weights(ops._ptr(wb), ops._ptr(ws), ops._ptr(wp), ops._ptr(wd), C.byref(geom), C.byref(basis), st), "kan_pack_weights")
-    dz_pm = ops._position_major(dz, 0, geom.O) if with_pm else None
+    c0, own, o0 = (grp or 0) * geom.C, G * geom.C, (grp or 0) * geom.O      # first owned channel, owned channels, first output
+    assert c0 + own <= x.shape[1] and o0 + G * geom.O <= dz.shape[1]
+    dz_pm = ops._position_major(dz, o0, G * geom.O) if with_pm else None
     S, n = plan.bwd_data_splits, plan.bwd_data_slab_elems
     assert n == x.numel()
     big = torch.full((S * n + 2 * PAD,), SENTINEL, device=x.device)
-    L.check(lib.kan_conv_bwd_data(ops._ptr(dz), ops._ptr(x), ops._ptr(x), ops._ptr(wd), ops._ptr(big, PAD), None, C.byref(geom), C.byref(basis),
-                                  ops._ptr(dz_pm), st), "kan_conv_bwd_data")
+    L.check(lib.kan_conv_bwd_data(ops._ptr(dz, o0 * 64), ops._ptr(x, c0 * 64), ops._ptr(x, c0 * 64), ops._ptr(wd), ops._ptr(big, PAD + c0 * 64), None,
+                                  C.byref(geom), C.byref(basis), ops._ptr(dz_pm), st), "kan_conv_bwd_data")
     torch.cuda.synchronize()
     assert bool((big[:PAD] == SENTINEL).all()) and bool((big[PAD + S * n:] == SENTINEL).all()), with_pm
     slabs = big[PAD:PAD + S * n].view(S, *x.shape)
-    assert bool((slabs[:, :, geom.C:] == SENTINEL).all()), with_pm          # the tensor's other channels, between the images of every slab
-    assert bool((slabs[:, :, :geom.C] != SENTINEL).all()), with_pm          # every owned element of every slab is written
-    return slabs[:, :, :geom.C]
+    assert bool((slabs[:, :, :c0] == SENTINEL).all()) and bool((slabs[:, :, c0 + own:] == SENTINEL).all()), with_pm      # the tensor's other channels (another group's; padding), between the images of every slab
+    assert bool((slabs[:, :, c0:c0 + own] != SENTINEL).all()), with_pm      # every owned element of every slab is written
+    return slabs[:, :, c0:c0 + own]
 
 
 @pytest.mark.parametrize("Cn,On,B,Ct,Ot", SHAPES, ids=IDS)
@@ -76,6 +85,58 @@ def test_pos8_dx_equals_the_plane_major_tiles_and_writes_nothing_else(Cn, On, B,
         assert torch.equal(new, old)
     else:
         assert err <= TOL_DX
+
+
+@pytest.mark.parametrize("Cn,On,B,Ct,Ot", SHAPES[:2], ids=IDS[:2])
+def test_pos8_dx_gelu_equals_the_plane_major_tiles_bit_for_bit(Cn, On, B, Ct, Ot, gpu_lib):
+    """The kernel's other instantiation (FAST_BSPLINE_GELU: the epilogue's base derivative is GELU's), on the two one-slab shapes."""
+    from convkan_amd import _lib as L
+    from convkan_amd import ops
+    torch.manual_seed(Cn + On + B + 1)
+    layer = K.KANConv2DLayer(Cn, On, 3, padding=1, base_activation=nn.GELU).cuda()
+    geom, basis, plan = _plan(layer, B, Cn, On, Ct, Ot)
+    assert plan.tile_orders & L.ORDER_POS8_BWD_DATA and ops._pos8_bwd_data(geom, plan) and plan.bwd_data_splits == 1
+    x = (torch.randn(B, Ct, 8, 8) * 1.5).cuda()
+    dz = torch.randn(B, Ot, 8, 8).cuda()
+    new, old = _run(layer, geom, basis, plan, x, dz, True), _run(layer, geom, basis, plan, x, dz, False)
+    assert bool(old.abs().max() > 0) and torch.equal(new, old)
+
+
+def test_pos8_dx_of_a_grouped_launch_equals_its_groups_launched_alone(gpu_lib):
+    """Two groups of 14 channels and 16 outputs at B = 32 in one launch -- the kernel's own group arithmetic: the group of a block, x and dx at
+    grp * C * 64, the weights of the group, dz_pm at grp * O * HoWo * B -- against one single-group launch per group: that group's weights packed alone, its
+    dz_pm = _position_major(dz, g * Og, Og), x, dz and dx at the group's channels of the same 28- / 32-channel tensors.  The same slab count gives the same
+    sum order: bit equality; otherwise TOL_DX on the summed slabs.  Guard words, and after a single-group launch the other group's channels still hold the
+    sentinel (_run).  The grouped launch with dz_pm against the same launch without it, as for one group."""
+    from convkan_amd import _lib as L
+    from convkan_amd import ops
+    G, Cg, Og, B = 2, 14, 16, 32
+    torch.manual_seed(G + Cg + Og + B)
+    grouped = K.KANConv2DLayer(G * Cg, G * Og, 3, padding=1, groups=G, base_activation=nn.SiLU).cuda()
+    alone = K.KANConv2DLayer(Cg, Og, 3, padding=1, base_activation=nn.SiLU)
+    gg, bg, pg = _plan(grouped, B, Cg, Og, G * Cg, G * Og)
+    g1, b1, p1 = _plan(alone, B, Cg, Og, G * Cg, G * Og)
+    assert gg.groups == G and max(1, g1.groups) == 1
+    for plan, geom in ((pg, gg), (p1, g1)):
+        assert plan.tile_orders & L.ORDER_POS8_BWD_DATA and ops._pos8_bwd_data(geom, plan) and not plan.dz_pm_wanted
+    x = (torch.randn(B, G * Cg, 8, 8) * 1.5).cuda()
+    dz = torch.randn(B, G * Og, 8, 8).cuda()
+    new, old = _run(grouped, gg, bg, pg, x, dz, True), _run(grouped, gg, bg, pg, x, dz, False)
+    assert tuple(new.shape) == (pg.bwd_data_splits, B, G * Cg, 8, 8) and bool(old.sum(0).abs().max() > 0)
+    if pg.bwd_data_splits == 1:
+        assert torch.equal(new, old)
+    else:
+        assert relerr(new.sum(0), old.sum(0)) <= TOL_DX
+    for g in range(G):
+        part = _run(grouped, g1, b1, p1, x, dz, True, grp=g)
+        mine = new[:, :, g * Cg:(g + 1) * Cg]
+        err = relerr(mine.sum(0), part.sum(0))
+        print(f"[pos8 bwd-data G=2] group {g}: slabs {pg.bwd_data_splits} grouped, {p1.bwd_data_splits} alone; max-normalised difference {err:.3e}")
+        assert bool(part.sum(0).abs().max() > 0)
+        if pg.bwd_data_splits == p1.bwd_data_splits:
+            assert torch.equal(mine, part), g
+        else:
+            assert err <= TOL_DX, g
 
 
 @pytest.mark.parametrize("Cn,On,B", [(s[0], s[1], s[2]) for s in SHAPES], ids=IDS)

@@ -7,7 +7,8 @@ Shapes (C -> O, B): 4 -> 32, B = 2 (one full and one partial row group, one band
 2 + 1).  Checked: the layer against the fp64 oracle (helpers.check_vs_oracle: max(TOL_DW, 4 x the fp32 oracle's own error)); the raw launch
 (kan_conv_bwd_weight_rowgroups + kan_unpack_wgrad_rowgroups) against the plan's route (kan_conv_bwd_weight + kan_unpack_wgrad, which this change leaves alone) at
 max-normalised <= 1e-6 on the unpacked gradients; guard words either side of the slabs; padded strides against the same values in dense tensors, bit for
-bit; single products (one input position, one dz position) landing in exactly their tap, bit-equal to the plan's route; odd B, where the entry is not
+bit; the same against the plan's route for GELU (the kernel's second instantiation); a two-group launch (11 channels and 40 outputs per group, B = 4 and
+B = 6) against its groups launched alone through padded strides, bit for bit, with group 0's gradients exact zeros when only group 1 has a dz; single products (one input position, one dz position) landing in exactly their tap, bit-equal to the plan's route; odd B, where the entry is not
 offered, and ops with the entry withheld running the plan's route."""
 import ctypes as C
 
@@ -31,8 +32,10 @@ def _geom(layer, B, Cn, On, Ct, Ot):
     return geom, basis
 
 
-def _run(layer, geom, basis, x, dz, off=False):
-    """One weight-gradient launch into guarded slabs + its unpack: the 8x8 entry, or (off) the plan's route.  (plan, slabs, tile orders, dw_base, dw_spline)."""
+def _run(layer, geom, basis, x, dz, off=False, x_off=0, dz_off=0):
+    """One weight-gradient launch into guarded slabs + its unpack: the 8x8 entry, or (off) the plan's route.  (plan, slabs, tile orders, dw_base, dw_spline);
+    the gradients are [O, ..] of a single-group geometry and [G, O, ..] of a grouped one.  `x_off`, `dz_off`: the launch reads x and dz from that many
+    floats into the tensors (the channels of one group of a wider tensor: padded batch strides)."""
     from convkan_amd import _lib as L
     from convkan_amd import ops
     lib = L.load()
@@ -46,26 +49,37 @@ def _run(layer, geom, basis, x, dz, off=False):
     assert S >= 1
     big = torch.full((S * n + 2 * PAD,), SENTINEL, device=x.device)
     if off:
-        L.check(lib.kan_conv_bwd_weight(ops._ptr(dz), ops._ptr(x), ops._ptr(x), ops._ptr(big, PAD), C.byref(geom), C.byref(basis), None, None, st),
+        L.check(lib.kan_conv_bwd_weight(ops._ptr(dz, dz_off), ops._ptr(x, x_off), ops._ptr(x, x_off), ops._ptr(big, PAD), C.byref(geom), C.byref(basis), None, None, st),
                 "kan_conv_bwd_weight")
     else:
-        L.check(lib.kan_conv_bwd_weight_rowgroups(ops._ptr(dz), ops._ptr(x), ops._ptr(big, PAD), C.byref(geom), C.byref(basis), st), "kan_conv_bwd_weight_rowgroups")
+        L.check(lib.kan_conv_bwd_weight_rowgroups(ops._ptr(dz, dz_off), ops._ptr(x, x_off), ops._ptr(big, PAD), C.byref(geom), C.byref(basis), st),
+                "kan_conv_bwd_weight_rowgroups")
     torch.cuda.synchronize()
     assert bool((big[:PAD] == SENTINEL).all()) and bool((big[PAD + S * n:] == SENTINEL).all()), off
     assert bool((big[PAD:PAD + S * n] != SENTINEL).all()), off                     # every word of every slab is written
-    dwb = torch.empty((1, geom.O, geom.C, 3, 3), device=x.device)
-    dws = torch.empty((1, geom.O, geom.C * 8, 3, 3), device=x.device)
+    dwb = torch.full((groups, geom.O, geom.C, 3, 3), SENTINEL, device=x.device)
+    dws = torch.full((groups, geom.O, geom.C * 8, 3, 3), SENTINEL, device=x.device)
     unpack = lib.kan_unpack_wgrad if off else lib.kan_unpack_wgrad_rowgroups
     L.check(unpack(ops._ptr(big, PAD), ops._ptr(dwb), ops._ptr(dws), C.byref(geom), C.byref(basis), st), "kan_unpack_wgrad")
     torch.cuda.synchronize()
-    return plan, S, orders, dwb[0], dws[0]
+    return (plan, S, orders, dwb[0], dws[0]) if groups == 1 else (plan, S, orders, dwb, dws)
 
 
 @pytest.mark.parametrize("Cn,On,B,Ct,Ot", SHAPES, ids=IDS)
 def test_pos8_dw_against_the_route_it_replaces_and_guard_words(Cn, On, B, Ct, Ot, gpu_lib):
+    _against_the_plans_route(nn.SiLU, Cn, On, B, Ct, Ot)
+
+
+@pytest.mark.parametrize("Cn,On,B,Ct,Ot", SHAPES, ids=IDS)
+def test_pos8_dw_gelu_against_the_route_it_replaces_and_guard_words(Cn, On, B, Ct, Ot, gpu_lib):
+    """The kernel's other instantiation (FAST_BSPLINE_GELU): the base plane is GELU(x)."""
+    _against_the_plans_route(nn.GELU, Cn, On, B, Ct, Ot)
+
+
+def _against_the_plans_route(act, Cn, On, B, Ct, Ot):
     from convkan_amd import _lib as L
     torch.manual_seed(Cn + On + B)
-    layer = K.KANConv2DLayer(Cn, On, 3, padding=1, base_activation=nn.SiLU).cuda()
+    layer = K.KANConv2DLayer(Cn, On, 3, padding=1, base_activation=act).cuda()
     geom, basis = _geom(layer, B, Cn, On, Ct, Ot)
     x = (torch.randn(B, Ct, 8, 8) * 1.5).cuda()
     dz = torch.randn(B, Ot, 8, 8).cuda()
@@ -81,6 +95,44 @@ def test_pos8_dw_against_the_route_it_replaces_and_guard_words(Cn, On, B, Ct, Ot
         gd, bd = _geom(layer, B, Cn, On, Cn, On)
         _, _, _, db, ds = _run(layer, gd, bd, x[:, :Cn].contiguous(), dz[:, :On].contiguous())
         assert torch.equal(nb, db) and torch.equal(ns, ds)
+
+
+@pytest.mark.parametrize("B", [4, 6], ids=["b4_one_slab", "b6_two_slabs"])
+def test_pos8_dw_of_a_grouped_launch_equals_its_groups_launched_alone(B, gpu_lib):
+    """Two groups of 11 channels and 40 outputs (an odd channel count; an output tail inside one 64-pad) in one launch -- the kernel's own group arithmetic:
+    grp = blk.y / tiles_o, x += grp * C * 64, dz += grp * O * 64, dwp += grp * K * Opad, slabs of G * K * Opad -- against one single-group launch of the same
+    entry per group on the same tensors (22 / 80 channels wide, the pointers moved to the group's channels).  The same slab count gives the same sum order:
+    bit equality; otherwise the 1e-6 max-normalised bound between two weight-gradient routes.  Guard words either side of S * G * K * Opad and every slab
+    word written (_run); against the plan's grouped route; and with dz zero outside group 1's outputs, group 0's gradients are exact zeros."""
+    from convkan_amd import _lib as L
+    G, Cg, Og = 2, 11, 40
+    torch.manual_seed(B)
+    grouped = K.KANConv2DLayer(G * Cg, G * Og, 3, padding=1, groups=G, base_activation=nn.SiLU).cuda()
+    alone = K.KANConv2DLayer(Cg, Og, 3, padding=1, base_activation=nn.SiLU)
+    gg, bg = _geom(grouped, B, Cg, Og, G * Cg, G * Og)
+    g1, b1 = _geom(alone, B, Cg, Og, G * Cg, G * Og)
+    assert gg.groups == G and max(1, g1.groups) == 1 and (g1.C, g1.O, g1.x_bstride, g1.y_bstride) == (gg.C, gg.O, gg.x_bstride, gg.y_bstride)
+    x = (torch.randn(B, G * Cg, 8, 8) * 1.5).cuda()
+    dz = torch.randn(B, G * Og, 8, 8).cuda()
+    plan, S, orders, nb, ns = _run(grouped, gg, bg, x, dz)
+    assert orders & L.ORDER_POS8_BWD_WEIGHT and S == (2 if B == 6 else 1) and tuple(nb.shape) == (G, Og, Cg, 3, 3) and tuple(ns.shape) == (G, Og, Cg * 8, 3, 3)
+    assert bool((nb != SENTINEL).all()) and bool((ns != SENTINEL).all())                  # the unpack wrote both groups
+    for g in range(G):
+        _, S1, o1, ab, as_ = _run(alone, g1, b1, x, dz, x_off=g * Cg * 64, dz_off=g * Og * 64)
+        assert o1 & L.ORDER_POS8_BWD_WEIGHT and bool(ab.abs().max() > 0) and bool(as_.abs().max() > 0)
+        eb, es = relerr(nb[g], ab), relerr(ns[g], as_)
+        print(f"[pos8 bwd-weight G=2 B={B}] group {g}: slabs {S} grouped, {S1} alone; base {eb:.3e} spline {es:.3e}")
+        if S1 == S:
+            assert torch.equal(nb[g], ab) and torch.equal(ns[g], as_), g
+        else:
+            assert eb <= 1e-6 and es <= 1e-6, g
+    _, _, _, ob, os_ = _run(grouped, gg, bg, x, dz, off=True)
+    assert relerr(nb, ob) <= 1e-6 and relerr(ns, os_) <= 1e-6
+    dz1 = dz.clone()
+    dz1[:, :Og] = 0.0
+    _, _, _, zb, zs = _run(grouped, gg, bg, x, dz1)
+    assert bool((zb[0] == 0).all()) and bool((zs[0] == 0).all())
+    assert torch.equal(zb[1], nb[1]) and torch.equal(zs[1], ns[1])
 
 
 @pytest.mark.parametrize("Cn,On,B", [s[:3] for s in SHAPES[:3]], ids=IDS[:3])
