@@ -59,6 +59,13 @@ class KanWavRoute(C.Structure):
                                        "CU", "XP", "UP", "bands", "items", "items_per_chunk", "lds_bytes", "px_per_chunk")]
 
 
+class KanBandRoute(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("fwd_band", "fast", "P", "NG", "NPLE", "NGR", "MO", "WP", "TO", "TP", "NT", "tiles_o", "tiles_p", "n_phase", "empty_phase",
+                                       "n_steps", "HC", "span_r", "cells", "slots", "lds_bytes", "fwd_splits", "max_images")] + \
+               [("phase_taps", C.c_int * 16)] + \
+               [(n, C.c_int) for n in ("bw_band", "bw_WR", "bw_NI", "bw_slots", "bw_TPI", "bw_ptiles", "bw_row_tiles", "bw_cells", "bw_lds_bytes", "bw_splits")]
+
+
 WAV_BI_TAPS9, WAV_BI_STRIDE1, WAV_BI_STRIDED = 0, 1, 2
 WAV_PAR_TILED, WAV_PAR_PIXEL = 0, 1
 
@@ -73,6 +80,7 @@ SIGNATURES = {
     "kan_last_error": (C.c_char_p, []),
     "kan_plan": (_I, [_GP, _BP, C.POINTER(KanPlan)]),
     "kan_tile_orders": (_I, [_GP, _BP]),
+    "kan_band_route": (_I, [_GP, _BP, C.POINTER(KanBandRoute)]),
     "kan_bwd_weight_rowgroup_slabs": (_I, [_GP, _BP]),
     "kan_conv_bwd_weight_rowgroups": (_I, [_P, _P, _P, _GP, _BP, _P]),
     "kan_unpack_wgrad_rowgroups": (_I, [_P, _P, _P, _GP, _BP, _P]),

@@ -585,6 +585,7 @@ static void band_cfg_pass(const KanGeom* g, const KanBasis* b, int fast, KanBand
         if (nimg > 2) vr += (nimg - 2) * (g->Ho + c->span_r);
         if (nimg > 1) vr += h1 + 1 + c->span_r;
         vr_max = vr > vr_max ? vr : vr_max;
+        c->img_max = nimg > c->img_max ? nimg : c->img_max;
     }
     c->cells = vr_max * c->HC;
     c->slots = ceil_div((long long)c->NG * c->cells, c->NT);

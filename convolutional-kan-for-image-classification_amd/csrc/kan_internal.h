@@ -130,6 +130,7 @@ typedef struct KanBandCfg {
     int n_phase, n_taps, n_steps; /* n_steps = NGR * n_taps weight steps of NPLE rows */
     int HC, span_r, OR0, OC0;     /* halo row length in cells, extra rows per image, smallest row / column offset of any tap */
     int cells;                    /* halo cells allocated per tile (largest tile) */
+    int img_max;                  /* most images any one pixel tile touches (informational: kan_band_route) */
     int slots;                    /* expansion units per thread: ceil(NG * cells / NT) */
     int TS;                       /* taps per barrier step of the forward (2 where one tap is under ~36 MFMAs per wave) */
     int lds_bytes, wgs_per_cu;

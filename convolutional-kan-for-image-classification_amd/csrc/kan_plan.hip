@@ -518,3 +518,28 @@ int plan_conv(const KanGeom* g, const KanBasis* b, ConvPlan* cp) {
     pl->row_blocks = (rowblk_fwd ? 1 : 0) | (c.rowblk_bwd_data ? 2 : 0);
     return 0;
 }
+
+// What the band launchers will run for (geom, basis): a copy out of the KanBandCfg they read, nothing decided here.
+int kan_band_route(const KanGeom* g, const KanBasis* b, KanBandRoute* r) {
+    static_assert(KAN_BAND_ROUTE_PHASES == KAN_BAND_MAX_PHASES, "phase_taps holds one entry per band phase");
+    if (!r) return fail("null route in kan_band_route");
+    memset(r, 0, sizeof(*r));
+    ConvPlan cp;
+    if (int rc = plan_conv(g, b, &cp)) return rc;
+    const KanBandCfg& c = cp.band;
+    if (cp.fwd == Route::BAND) {
+        r->fwd_band = 1;
+        r->fast = c.fast; r->P = c.P; r->NG = c.NG; r->NPLE = c.NPLE; r->NGR = c.NGR;
+        r->MO = c.MO; r->WP = c.WP; r->TO = c.TO; r->TP = c.TP; r->NT = c.NT; r->tiles_o = c.tiles_o; r->tiles_p = c.tiles_p;
+        r->n_phase = c.n_phase; r->empty_phase = c.n_phase < g->sh * g->sw ? 1 : 0; r->n_steps = c.n_steps;
+        for (int ph = 0; ph < c.n_phase; ++ph) r->phase_taps[ph] = c.ph_tap0[ph + 1] - c.ph_tap0[ph];
+        r->HC = c.HC; r->span_r = c.span_r; r->cells = c.cells; r->slots = c.slots; r->lds_bytes = c.lds_bytes;
+        r->fwd_splits = c.fwd_splits; r->max_images = c.img_max;
+    }
+    if (cp.bwd_weight == Route::BAND) {
+        r->bw_band = 1;
+        r->bw_WR = c.bw_WR; r->bw_NI = c.bw_NI; r->bw_slots = c.bw_slots; r->bw_TPI = c.bw_TPI; r->bw_ptiles = c.bw_ptiles;
+        r->bw_row_tiles = c.bw_row_tiles; r->bw_cells = c.bw_cells; r->bw_lds_bytes = c.bw_lds_bytes; r->bw_splits = c.bw_splits;
+    }
+    return 0;
+}

@@ -164,6 +164,31 @@ int kan_plan(const KanGeom* geom, const KanBasis* basis, KanPlan* plan);
 #define KAN_ORDER_POS8_BWD_WEIGHT 32
 int kan_tile_orders(const KanGeom* geom, const KanBasis* basis);
 
+/* Informational, for tests and profiling tools: what the band kernels (plan.fwd_band / plan.bwd_weight_band) run for this geometry -- the kernel
+ * instantiation and the run-time switches of a launch, copied from the configuration kan_conv_fwd and kan_conv_bwd_weight launch from.  Pure host
+ * arithmetic, no device work (like kan_norm_route and kan_wav_route).
+ *   forward (fwd_band = 1; all forward fields 0 otherwise)
+ *     fast: compile-time basis spec (1 B-spline SiLU, 2 B-spline GELU, 3 FastKAN 8 centres, 4 ChebyKAN degree 4, 5 ChebyKAN degree 3, 6 recurrence
+ *     families degree 3);  P planes per channel;  NG channels per group (k_band_fwd<.., NG, 2, MO, WP, ..>), NPLE = even(NG P) rows per step, NGR
+ *     channel groups;  MO 32-output MFMA blocks per wave, WP waves along the pixels: tile TO = 64 MO outputs x TP = 64 WP pixels, NT threads,
+ *     tiles_o x tiles_p tiles;  n_phase stride phases that hold a tap, phase_taps[i] taps in phase i, empty_phase = 1 when some of the sh sw phases
+ *     hold none (stride > kernel);  n_steps = NGR taps weight steps;  HC cells per halo row, span_r extra halo rows per image, cells per tile;
+ *     slots: live expansion units per thread (1 .. 6);  lds_bytes of dynamic LDS (above 65536: the raised limit);  fwd_splits slabs;  max_images:
+ *     the most images any one pixel tile covers (tiles are TP consecutive pixels in (image, row, column) order)
+ *   weight gradient (bw_band = 1; all bw_ fields 0 otherwise)
+ *     k_band_bwd_weight<.., NG, bw_WR, bw_NI, bw_slots>: bw_WR waves of 32 rows, bw_NI 32-output blocks per wave, 3 or 6 expansion slots;  bw_TPI
+ *     128-pixel tiles per image, bw_ptiles of them in all;  bw_row_tiles row tiles of 32 bw_WR rows;  bw_cells halo cells per tile;  bw_lds_bytes;
+ *     bw_splits slabs
+ * Returns 0 with every field 0 where the plan takes neither band route, and kan_plan's error for a geometry the planner rejects. */
+#define KAN_BAND_ROUTE_PHASES 16
+typedef struct KanBandRoute {
+    int fwd_band, fast, P, NG, NPLE, NGR, MO, WP, TO, TP, NT, tiles_o, tiles_p, n_phase, empty_phase, n_steps, HC, span_r, cells, slots, lds_bytes,
+        fwd_splits, max_images;
+    int phase_taps[KAN_BAND_ROUTE_PHASES];
+    int bw_band, bw_WR, bw_NI, bw_slots, bw_TPI, bw_ptiles, bw_row_tiles, bw_cells, bw_lds_bytes, bw_splits;
+} KanBandRoute;
+int kan_band_route(const KanGeom* geom, const KanBasis* basis, KanBandRoute* route);
+
 /* Pack the reference-layout weights of one group into the GEMM layouts of the kernels:
  *   wp (forward):   wp[k(item,p)][o],  item = tap*C + c (tap-major), T = kh*kw,
  *                   k = (item / IPC)*KC + (item % IPC)*P + p;  plane p = 0 is the base branch
